@@ -1,6 +1,6 @@
 """Headline benchmark: images/sec @640x640, batch 32 per GPU, MSPA-C2f + GD-neck YOLOv8n (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N --steps K --warmup W] [--dtype bf16|f32] [--mode infer|train]
+    python bench.py [--gpus N --steps K --warmup W] [--dtype bf16|f32] [--mode infer|train] [--full] [--dump-outputs DIR]
 
 N > 1 without a launcher: this process starts `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a CHILD before it
 touches the GPU and exits with the child's code (one rank per GPU over RCCL); under torchrun the ranks read RANK / WORLD_SIZE.
@@ -13,8 +13,14 @@ batches ("weak" scaling); the only collective is the MAX of the per-rank times.
 mode train (BASELINE configs[2]): a step = DetectionTrainer.step on a resident uint8 batch with synthetic labels: train-mode forward,
 fused assigner + loss, HIP reverse pass, bucketed RCCL all-reduce of the flat gradient buffer, clip + SGD + EMA.
 
-Prints ONE JSON line on rank 0, with `roofline` (dominant kernel, HIP-event timed) and `cpu_baseline` (the CPU oracle - a port of the
-reference's path - timed on this box's host cores with the protocol of SURVEY 8(d) / BASELINE.md section 3).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`); `roofline`,
+`cpu_baseline` and `config.ms_per_step_one_batch_at_a_time` are null.  --full adds what takes runs of its own: the check of the batches in
+flight against their serial replay and the one-batch-at-a-time latency, `roofline` (dominant kernel, HIP-event timed) and `cpu_baseline` (the
+CPU oracle - a port of the reference's path - timed on the host cores with the protocol of SURVEY 8(d) / BASELINE.md section 3).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64): inference
+`detections` [B, max_det, 6], `kept_anchor` [B, max_det] and `counts` [B] (rows past counts[i], which the kernel leaves unwritten, are
+written as 0 / -1); training `loss`, `loss_items` and `params` (the flat fp32 parameter + buffer vector after the step, at most 4 M
+elements: a fixed seeded sample of a larger model).  Inputs and weights are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E peak (spec)
 MFMA_PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3, 'fp8': 5000.0}   # fp8: the dtype's dense peak (block-scaled K=128 form); the non-scaled 16x16x32 e4m3 form used here runs at the bf16 rate
 N_RESIDENT = 8                 # resident input batches cycled through (8 x 78.6 MB bf16 = 629 MB > the 256 MiB Infinity Cache)
+DUMP_CAP = 1 << 22             # elements per array written by --dump-outputs (16 MB of fp32; the inference outputs are far smaller)
 
 
 def parse():
@@ -51,7 +58,24 @@ def parse():
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--resident', type=int, default=N_RESIDENT)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run the serial-replay check and one-batch-at-a-time latency of the batches in flight, the roofline pass and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the timed path's outputs of its last step as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+def dump_outputs(path, arrays):
+    """name -> numpy array -> path/<name>.npy.  An array of more than DUMP_CAP elements is written as a sample of its flattened values at
+    fixed seeded indices (the same in every run), which keeps the files of one run below 64 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > DUMP_CAP:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_CAP, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def launch_ranks(args):
@@ -267,6 +291,7 @@ def main():
         raise SystemExit('bench.py: --dtype fp8 is an inference configuration (BASELINE configs[4])')
     tdt = torch.float32 if args.dtype == 'f32' else torch.bfloat16
     graph_used = False
+    serial_ref = None                  # --full, batches in flight: what every captured graph gives on its own serial replay
 
     if args.mode == 'train':
         from mgdt_yolo_amd.yolo.engine.trainer import DetectionTrainer
@@ -283,9 +308,10 @@ def main():
             img = (seeded_images(args.batch, args.imgsz, args.imgsz, seed=parallel.shard_seed(100 + 17 * r, rank)) * 255).round().clamp_(0, 255).to(torch.uint8)
             batches.append(dict(img=img.to(dev), **lab))
         it = [0]
+        last = [None]                   # (loss * B, loss items) of the latest step
 
         def run():
-            tr.step(batches[it[0] % R])
+            last[0] = tr.step(batches[it[0] % R])
             it[0] += 1
 
         def step_eager():               # instrumented pass: per-launch events need the launches themselves
@@ -354,7 +380,6 @@ def main():
                 graph_used = True
         it = [0]
         lanes = [torch.cuda.Stream() for _ in range(S)] if (graph_used and S > 1) else []
-        serial_ref = None
         if lanes:
             # what every graph must produce: its own serial replay (counts, detections and kept anchors of the valid rows)
             def snapshot():
@@ -363,10 +388,11 @@ def main():
                     valid = torch.arange(o[1].shape[1], device=dev)[None, :] < o[2][:, None]
                     res.append((o[2].clone(), o[0][valid].clone(), o[1][valid].clone()))
                 return res
-            for g in graphs:
-                g.replay()
-            torch.cuda.synchronize()
-            serial_ref = snapshot()
+            if args.full:
+                for g in graphs:
+                    g.replay()
+                torch.cuda.synchronize()
+                serial_ref = snapshot()
 
             def run():
                 r = it[0] % R
@@ -402,6 +428,16 @@ def main():
         barrier()
         return parallel.max_over_ranks(t1 - t0, dev)
 
+    def last_outputs():
+        """What the timed path returned in its last step, as numpy arrays (float32 / float64)."""
+        if args.mode == 'train':
+            total, items = (torch.as_tensor(t).detach().float().reshape(-1).cpu().numpy() for t in last[0])
+            return {'loss': total, 'loss_items': items, 'params': tr.state.data.detach().cpu().numpy()}
+        det, kept, counts = outs[(it[0] - 1) % R] if graph_used else out
+        valid = torch.arange(det.shape[1], device=dev)[None, :] < counts[:, None]
+        return {'detections': torch.where(valid[..., None], det, 0.0).cpu().numpy(),
+                'kept_anchor': torch.where(valid, kept, -1).double().cpu().numpy(), 'counts': counts.double().cpu().numpy()}
+
     elapsed = timed(run)
     serial_ms = None
     if args.mode == 'infer':
@@ -419,21 +455,23 @@ def main():
                 workload = workload.replace(f', {S} batches in flight (one captured graph per resident batch, replayed round-robin on {S} streams)', '')
                 lanes, S = [], 1
                 elapsed = timed(run_serial)
-            else:                               # one batch at a time, for the latency side of the trade
-                it[0] = 0
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(2 * R):
-                    run_serial()
-                torch.cuda.synchronize()
-                serial_ms = (time.perf_counter() - t0) / (2 * R) * 1e3
         n_det = int(out[2].sum().item())
+    if args.dump_outputs and rank == 0:          # before anything else replays the graphs
+        dump_outputs(args.dump_outputs, last_outputs())
+    if serial_ref is not None and not bad:       # one batch at a time, for the latency side of the trade
+        it[0] = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(2 * R):
+            run_serial()
+        torch.cuda.synchronize()
+        serial_ms = (time.perf_counter() - t0) / (2 * R) * 1e3
 
     # ---- roofline of the dominant kernel: eager launches bracketed by HIP events on the launch stream
     # Per-kernel durations only mean something when kernels run one after the other: the instrumented pass uses ONE stream (no parallel branch),
     # and its event pairs are rescaled to the replay of a graph captured the same way - one batch, one stream - not to the overlapped timed region.
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = 3
         ref_ms = elapsed / args.steps * 1e3
         side_was = ops.SIDE_STREAM
@@ -485,7 +523,7 @@ def main():
             roof['step_hbm_frac'] = round(by / (ms_step * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)
             roof['step_mfma_frac'] = round(fl / (ms_step * 1e-3) / (MFMA_PEAK_TFLOPS[args.dtype] * 1e12), 4)
             roof['step_algorithmic'] = {'bytes_per_step': round(by), 'flops_per_step': round(fl), 'source': 'SURVEY.md 8(d): 22.04 M elements and 5.278 GFLOP per 640x640 image (layer granularity)'}
-        if not args.no_cpu_baseline and world == 1 and args.mode == 'infer':
+        if args.full and not args.no_cpu_baseline and world == 1 and args.mode == 'infer':
             line['cpu_baseline'] = cpu_baseline(cfg, model, args)
         else:
             line['cpu_baseline'] = None

@@ -355,8 +355,22 @@ def ref_ckpt():
     print(f'ref_last.pt: {os.path.getsize(path) / 1024:.1f} KiB, pickled with {pickle_module.__name__}')
 
 
+# ------------------------------------------------------------------ the reference's model YAML files, parsed (CPU graph tests)
+def ref_yaml():
+    """yaml.safe_load of the reference's models/v8/<name>.yaml for every built-in graph that has one, one model per line of ref_yaml.json:
+    what tests/test_host_logic.py compares the built-in graphs with and parses through DetectionModel."""
+    import json
+    import yaml
+    from mgdt_yolo_amd.models import CONFIGS
+    graphs = {n: yaml.safe_load(open(REFY + n + '.yaml')) for n in CONFIGS if os.path.exists(REFY + n + '.yaml')}
+    path = os.path.join(HERE, 'ref_yaml.json')
+    with open(path, 'w') as f:
+        f.write('{\n' + ',\n'.join(f'{json.dumps(n)}: {json.dumps(d)}' for n, d in graphs.items()) + '\n}\n')
+    print(f'ref_yaml.json: {sorted(graphs)}')
+
+
 if __name__ == '__main__':
-    what = sys.argv[1:] or ['train', 'ref_ckpt', 'e2e', 'modules', 'boxes', 'assigner', 'loss', 'nms', 'val_match', 'optim_groups', 'metrics_ap', 'boxes2', 'letterbox']
+    what = sys.argv[1:] or ['train', 'ref_ckpt', 'e2e', 'modules', 'boxes', 'assigner', 'loss', 'nms', 'val_match', 'optim_groups', 'metrics_ap', 'boxes2', 'letterbox', 'ref_yaml']
     models = {}
     if 'e2e' in what or 'nms' in what:
         for tag, yname in E2E_MODELS.items():
@@ -385,3 +399,5 @@ if __name__ == '__main__':
         train()
     if 'ref_ckpt' in what:
         ref_ckpt()
+    if 'ref_yaml' in what:
+        ref_yaml()

@@ -1,5 +1,6 @@
 """CPU-only checks of the host side: the C ABI loads and exports what include/mgdt.h declares, the YAML -> graph rules,
 state_dict compatibility with the reference, argument validation, and the N>1 (gloo, world_size 2) bench path."""
+import json
 import os
 import re
 
@@ -13,7 +14,9 @@ from mgdt_yolo_amd.models import CONFIGS, get_config
 from mgdt_yolo_amd.nn import tasks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_YAML = '/root/reference/models/v8'
+# the reference's models/v8/<name>.yaml, parsed (tests/golden/gen_golden.py:ref_yaml)
+with open(os.path.join(ROOT, 'tests', 'golden', 'ref_yaml.json')) as _f:
+    REF_YAML = json.load(_f)
 
 
 def test_c_abi_loads_and_exports_every_declared_symbol():
@@ -39,25 +42,21 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
 
 @pytest.mark.parametrize('name', [n for n in CONFIGS if not n.endswith('_hidc128')])     # *_hidc128: our own s-scale variant, no reference file
 def test_builtin_graphs_equal_reference_yaml_files(name):
-    import yaml
-    path = os.path.join(REF_YAML, name + '.yaml')
-    if not os.path.exists(path):
-        pytest.skip('reference tree not present on this box')
-    ref = yaml.safe_load(open(path))
+    ref = REF_YAML[name]
     mine = get_config(name)
     for k in ('nc', 'scales', 'backbone', 'head'):
         assert ref[k] == mine[k]
 
 
-def test_parse_reference_yaml_files():
-    """yaml_model_load + parse_model on the reference's own files (scale from the file stem, tasks.py:702-735)."""
-    path = os.path.join(REF_YAML, 'mspa_c2f_gd_yolov8n.yaml')
-    if not os.path.exists(os.path.join(REF_YAML, 'mspa_c2f_gd_yolov8.yaml')):
-        pytest.skip('reference tree not present on this box')
-    m = tasks.DetectionModel(path, verbose=False)
+def test_parse_reference_yaml_files(tmp_path):
+    """yaml_model_load + parse_model on the reference's own files (scale from the file stem, tasks.py:702-735), written back as YAML."""
+    import yaml
+    with open(tmp_path / 'mspa_c2f_gd_yolov8.yaml', 'w') as f:
+        yaml.safe_dump(REF_YAML['mspa_c2f_gd_yolov8'], f)
+    m = tasks.DetectionModel(str(tmp_path / 'mspa_c2f_gd_yolov8n.yaml'), verbose=False)
     assert m.yaml['scale'] == 'n' and sum(p.numel() for p in m.parameters()) == 1314298       # SURVEY App. A.1
     assert m.save == [2, 2, 4, 4, 6, 6, 9, 11, 15] and m.stride.tolist() == [8.0]
-    s = tasks.DetectionModel(os.path.join(REF_YAML, 'mspa_c2f_gd_yolov8s.yaml'), verbose=False)
+    s = tasks.DetectionModel(str(tmp_path / 'mspa_c2f_gd_yolov8s.yaml'), verbose=False)
     assert sum(p.numel() for p in s.parameters()) == 4149424
 
 

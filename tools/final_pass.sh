@@ -3,15 +3,15 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; T=$1
 cd $R
 python -m pytest tests -m gpu -x -q > $O/${T}_gputests.log 2>&1; tail -1 $O/${T}_gputests.log
-python bench.py > $O/${T}_bench_line.json 2> /dev/null && echo default ok
-python bench.py --dtype f32 --no-cpu-baseline > $O/${T}_bench_f32.json 2> /dev/null
-python bench.py --dtype fp8 --no-cpu-baseline > $O/${T}_bench_fp8_b32.json 2> /dev/null
-python bench.py --dtype fp8 --batch 64 --no-cpu-baseline > $O/${T}_bench_fp8_b64.json 2> /dev/null
-python bench.py --batch 64 --no-cpu-baseline > $O/${T}_bench_bf16_b64.json 2> /dev/null
-python bench.py --mode train --steps 30 --warmup 5 > $O/${T}_train_bf16.json 2> /dev/null
-python bench.py --mode train --dtype f32 --steps 30 --warmup 5 > $O/${T}_train_f32.json 2> /dev/null
-python bench.py --model mspa_c2f_gd_tood_yolov8_hidc128 --scale s --imgsz 1280 --batch 8 --no-cpu-baseline > $O/${T}_tood_s_1280_b8_infer.json 2> /dev/null
-python bench.py --model mspa_c2f_gd_tood_yolov8_hidc128 --scale s --imgsz 1280 --batch 8 --mode train --steps 20 --warmup 3 > $O/${T}_tood_s_1280_b8_train.json 2> /dev/null
+python bench.py --full > $O/${T}_bench_line.json 2> /dev/null && echo default ok
+python bench.py --full --dtype f32 --no-cpu-baseline > $O/${T}_bench_f32.json 2> /dev/null
+python bench.py --full --dtype fp8 --no-cpu-baseline > $O/${T}_bench_fp8_b32.json 2> /dev/null
+python bench.py --full --dtype fp8 --batch 64 --no-cpu-baseline > $O/${T}_bench_fp8_b64.json 2> /dev/null
+python bench.py --full --batch 64 --no-cpu-baseline > $O/${T}_bench_bf16_b64.json 2> /dev/null
+python bench.py --full --mode train --steps 30 --warmup 5 > $O/${T}_train_bf16.json 2> /dev/null
+python bench.py --full --mode train --dtype f32 --steps 30 --warmup 5 > $O/${T}_train_f32.json 2> /dev/null
+python bench.py --full --model mspa_c2f_gd_tood_yolov8_hidc128 --scale s --imgsz 1280 --batch 8 --no-cpu-baseline > $O/${T}_tood_s_1280_b8_infer.json 2> /dev/null
+python bench.py --full --model mspa_c2f_gd_tood_yolov8_hidc128 --scale s --imgsz 1280 --batch 8 --mode train --steps 20 --warmup 3 > $O/${T}_tood_s_1280_b8_train.json 2> /dev/null
 echo lines done
 python tools/profile_ops.py > $O/${T}_per_launch_bf16_b32.txt 2>&1
 bash tools/prof_bench.sh ${T} > /dev/null && echo prof bf16 ok
