@@ -172,7 +172,7 @@ __global__ void bilinear_bwd_kernel(const mgdt_view gy, const mgdt_view gx, int 
         Lerp lx = lerp_of(ox, gx.w, gy.w);
         float wx = (lx.i0 == w ? lx.l0 : 0.f) + (lx.i1 == w ? lx.l1 : 0.f);
         if (wx == 0.f) continue;
-        acc += wy * wx * (float)AT(const T, gy, n, oy, ox, c);
+        acc = fmaf(wy * wx, (float)AT(const T, gy, n, oy, ox, c), acc);     // as mgdt_v4_bilinear_bwd
       }
     }
     if (accumulate) acc += (float)AT(const T, gx, n, h, w, c);
@@ -757,7 +757,8 @@ __global__ void grn_bwd_apply_kernel(const mgdt_view g, const mgdt_view t, const
   long total = (long)t.n * t.h * t.w * t.c;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     DECODE_NHWC(i, t, n, h, w, c)
-    float v = (float)AT(const T, g, n, h, w, c) * scale[n * t.c + c] + coef[n * t.c + c] * (float)AT(const T, t, n, h, w, c);
+    // one fma, as mgdt_v4_grn_bwd_apply: left to the compiler, the two products were packed into one v_pk_mul_f32 and added (no fma), one ulp apart
+    float v = fmaf((float)AT(const T, g, n, h, w, c), scale[n * t.c + c], coef[n * t.c + c] * (float)AT(const T, t, n, h, w, c));
     AT(T, dt, n, h, w, c) = (T)v;
   }
 }

@@ -1,7 +1,9 @@
 // Channel-vectorised forms (4 channels, 8 / 16 bytes per access) of the element-wise and gather kernels of the training path; each
 // mgdt_v4_* returns false when a view does not qualify (channels not a multiple of 4, strides or base not 4-element aligned) and the
 // caller runs its scalar kernel.  Same arithmetic per element as the scalar kernels in train.hip / train_gd.hip (same order of the
-// gather sums), so both give the same bits.
+// gather sums, the same fma where the compiler would otherwise contract the two forms differently), so both give the same bits
+// (tests/test_reverse_kernels.py holds them to it).  The exception is mgdt_v4_nc_reduce_partial: it splits a pixel range over
+// 256 / min(C/4, 256) lanes where nc_reduce_partial_kernel uses 4, so the two sums agree to fp32 rounding, not bit for bit.
 #include "common.h"
 
 static bool v4_ok(const mgdt_view* v, int dtype) {
@@ -139,7 +141,8 @@ __global__ __launch_bounds__(256) void v4_bilinear_bwd_kernel(const mgdt_view gy
     DECODE_Q(i, gx, n, h, w, c)
     if (x2 && h >= 1 && h < gx.h - 1 && w >= 1 && w < gx.w - 1) {
       // src = o/2 - 0.25: outputs 2h-1, 2h, 2h+1, 2h+2 reach input h with weights 0.25, 0.75, 0.75, 0.25 (exactly what lerp_of yields there); same
-      // summation order as the generic scan below, so both paths give the same bits
+      // summation order and the same explicit fma as the generic scan below and bilinear_bwd_kernel, so all three give the same bits (left to the
+      // compiler, the unrolled stencil and the scan were contracted differently and differed in the last bit)
       const float wt[4] = {0.25f, 0.75f, 0.75f, 0.25f};
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(256) void v4_bilinear_bwd_kernel(const mgdt_view gy
           const f32x4 g = load4<T>(P4(const T, gy, n, 2 * h - 1 + dy, 2 * w - 1 + dx, c));
           const float ww = wt[dy] * wt[dx];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] += ww * g[j];
+          for (int j = 0; j < 4; ++j) acc[j] = fmaf(ww, g[j], acc[j]);
         }
       if (accumulate) acc += load4<T>(P4(const T, gx, n, h, w, c));
       store4<T>(P4(T, gx, n, h, w, c), acc);
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(256) void v4_bilinear_bwd_kernel(const mgdt_view gy
         const f32x4 g = load4<T>(P4(const T, gy, n, oy, ox, c));
         const float ww = wy * wx;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] += ww * g[j];
+        for (int j = 0; j < 4; ++j) acc[j] = fmaf(ww, g[j], acc[j]);
       }
     }
     if (accumulate) acc += load4<T>(P4(const T, gx, n, h, w, c));
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(256) void v4_grn_bwd_apply_kernel(const mgdt_view g
     const f32x4 sc = *(const f32x4*)(scale + n * t.c + c), cf = *(const f32x4*)(coef + n * t.c + c);
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = gv[j] * sc[j] + cf[j] * tv[j];
+    for (int j = 0; j < 4; ++j) o[j] = fmaf(gv[j], sc[j], cf[j] * tv[j]);      // the contraction spelled out: grn_bwd_apply_kernel uses the same
     store4<T>(P4(T, dt, n, h, w, c), o);
   }
 }

@@ -1035,6 +1035,7 @@ def conv_wgrad(x, dy, k, stride, dw, dbias=None, x2=None, accumulate=False):
     elif x.dtype != torch.float32 or dy.dtype not in (torch.float32, torch.bfloat16):
         # the generic kernel (any layout, any channel count) reads x as fp32 whatever dy is: any other dtype would be an out-of-range read
         raise RuntimeError(f'conv_wgrad: the generic (non-NHWC / channels % 4 != 0) path takes an fp32 input, got {x.dtype} (dy {dy.dtype})')
+    # the dtype code names dy's type: x is of that type too on the NHWC path (checked above) and always fp32 on the generic one
     ws = torch.empty(lib.mgdt_conv_wgrad_workspace_bytes(x.shape[1], dy.shape[1], k), dtype=torch.uint8, device=x.device)
     if _PROF is not None:
         b, ci, h, w = x.shape
@@ -1043,7 +1044,7 @@ def conv_wgrad(x, dy, k, stride, dw, dbias=None, x2=None, accumulate=False):
     if _WGRAD_DEFER[0] > 0 and accumulate:
         flush_wgrad()                                  # an accumulating gradient must see the value the pending jobs will write
     defer = (_WGRAD_DEFER[0] > 0 and dbias is None and not accumulate and is_nhwc(x) and x.shape[1] % 4 == 0 and dy.shape[1] % 4 == 0 and dw.is_contiguous())
-    _launch('conv_wgrad', 'mgdt_conv_wgrad', vp(x), vp(x2), vp(dy), k, stride, None if defer else ptr(dw), ptr(dbias), int(accumulate), ptr(ws), dtype_code(x.dtype), stream())
+    _launch('conv_wgrad', 'mgdt_conv_wgrad', vp(x), vp(x2), vp(dy), k, stride, None if defer else ptr(dw), ptr(dbias), int(accumulate), ptr(ws), dtype_code(dy.dtype), stream())
     if defer:
         _WGRAD_PENDING.append((ws, dw, dw.numel(), lib.mgdt_conv_wgrad_splits(x.shape[1], dy.shape[1], k)))
 
