@@ -142,6 +142,18 @@ int mgdt_detect_tail_supported(int c2, int c3, int nc, int reg_max, int dtype);
 int mgdt_detect_tail_fwd(const mgdt_view* tb, const mgdt_view* tc, const void* wb, const float* bb, const void* wc, const float* bc, int nc,
                          float stride, int a_off, int a_total, const mgdt_view* feat, float* y, unsigned long long* best_keys,
                          const void* wb3, const float* bb3, mgdt_stream s);
+/* The same launch with the test-time augmentation epilogue (nn/tasks.py:276-285 _descale_pred): the decoded xywh are divided by aug_scale,
+ * then x = aug_img_w - x when aug_flip (the pass ran on the left-right flipped image; aug_img_w = the ORIGINAL image width).  y / best_keys are
+ * the merged buffer of all passes: a_off is the level's offset in it, a_total its anchor count. */
+int mgdt_detect_tail_aug_fwd(const mgdt_view* tb, const mgdt_view* tc, const void* wb, const float* bb, const void* wc, const float* bc, int nc,
+                             float stride, int a_off, int a_total, const mgdt_view* feat, float* y, unsigned long long* best_keys,
+                             const void* wb3, const float* bb3, float aug_scale, int aug_flip, float aug_img_w, mgdt_stream s);
+
+/* ---- test-time augmentation input (yolo/utils/torch_utils.py:261-270 scale_img, after x.flip(3) when flip): x = N x 3 x H x W image (any
+ * strides; MGDT_F32 / MGDT_BF16 / MGDT_U8, u8 divided by 255), y = N x 3 x Hp x Wp (y_dtype MGDT_F32 / MGDT_BF16; 16-byte runs along W when
+ * W is contiguous).  Rows / columns below hs x ws are the bilinear resize of the (flipped) image to hs x ws (align_corners=False, PyTorch's
+ * CPU index and weight arithmetic), the rest is `pad`. */
+int mgdt_scale_img_fwd(const mgdt_view* x, int x_dtype, int flip, int hs, int ws, float pad, const mgdt_view* y, int y_dtype, mgdt_stream s);
 
 /* ---- a whole CSP block (MSPA_C2f / C2f) in one launch, bf16 inference (nn/modules/block.py:187-287, :514-526):
  *   mode 0 (MSPA_C2f): front = the three chained 1x1 convs of mgdt_pw_chain3_fwd (blob of mgdt_pw_chain_pack), bottleneck input
@@ -281,6 +293,10 @@ int mgdt_inject_fwd(const mgdt_view* local, const mgdt_view* ga, const mgdt_view
  * xywh = dist2bbox(softmax_R . arange(R), anchor(+0.5)) * stride, cls = sigmoid.  y is fp32.              */
 int mgdt_detect_decode_fwd(const mgdt_view* feat, int reg_max, int nc, float stride, int a_off, int a_total, float* y,
                            int dtype, mgdt_stream s);
+/* The same decode with the test-time augmentation epilogue of mgdt_detect_tail_aug_fwd (xywh /= aug_scale, x = aug_img_w - x when aug_flip);
+ * best_keys: NULL, or [N][a_total] - the NMS key of every anchor's best class, as mgdt_detect_tail_fwd writes it. */
+int mgdt_detect_decode_aug_fwd(const mgdt_view* feat, int reg_max, int nc, float stride, int a_off, int a_total, float* y,
+                               unsigned long long* best_keys, float aug_scale, int aug_flip, float aug_img_w, int dtype, mgdt_stream s);
 
 /* ---- batched NMS (yolo/utils/ops.py:136-266 incl. the torchvision.ops.nms call at :249) -----------------
  * pred fp32 [n][4+nc][a].  Outputs per image: out[n][max_det][6] fp32 rows (x1,y1,x2,y2,conf,cls),

@@ -79,6 +79,8 @@ PROTOTYPES = {
     'mgdt_stem2_fwd': (_i, [VP, _i, _vp, _vp, _vp, _vp, VP, _vp]),
     'mgdt_detect_tail_supported': (_i, [_i, _i, _i, _i, _i]),
     'mgdt_detect_tail_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _i, _f, _i, _i, VP, _vp, _vp, _vp, _vp, _vp]),
+    'mgdt_detect_tail_aug_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _i, _f, _i, _i, VP, _vp, _vp, _vp, _vp, _f, _i, _f, _vp]),
+    'mgdt_scale_img_fwd': (_i, [VP, _i, _i, _i, _i, _f, VP, _i, _vp]),
     'mgdt_csp_block_supported': (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     'mgdt_csp_block_tiles': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'mgdt_csp_block_fwd': (_i, [_i, VP, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, VP, _vp, _i, _vp]),
@@ -102,6 +104,7 @@ PROTOTYPES = {
     'mgdt_grn_stats_fwd': (_i, [VP, _vp, _vp, _vp, _i, _vp]),
     'mgdt_inject_fwd': (_i, [VP, VP, VP, VP, _i, _vp]),
     'mgdt_detect_decode_fwd': (_i, [VP, _i, _i, _f, _i, _i, _vp, _i, _vp]),
+    'mgdt_detect_decode_aug_fwd': (_i, [VP, _i, _i, _f, _i, _i, _vp, _vp, _f, _i, _f, _i, _vp]),
     'mgdt_detect_loss_workspace_bytes': (_sz, [_i, _i, _i]),
     'mgdt_detect_loss_fwd': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'mgdt_detect_loss_fwd_dev': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),

@@ -22,6 +22,8 @@ struct DtArgs {
   int N, H, W, HW, c2, c3, nc, kch, nbc, units_per_img, units, a_off, a_total;
   float stride;
   FastDiv fd_w;
+  int aug, aug_flip;                   // test-time augmentation epilogue (mgdt_detect_tail_aug_fwd): xywh /= aug_s, then x = aug_w - x when flipped
+  float aug_s, aug_w;
 };
 
 constexpr int DT_THREADS = 256;
@@ -138,7 +140,11 @@ __global__ __launch_bounds__(DT_THREADS) void detect_tail_kernel(const DtArgs a)
       const float dl = __shfl(dd, r, 64), dt = __shfl(dd, 16 + r, 64), dr = __shfl(dd, 32 + r, 64), db = __shfl(dd, 48 + r, 64);
       const float ax = (float)ox + 0.5f, ay = (float)oy + 0.5f;            // make_anchors offset 0.5 (tal.py:476-488)
       const float x1 = ax - dl, y1 = ay - dt, x2 = ax + dr, y2 = ay + db;       // dist2bbox (tal.py:491-500), then * stride (head.py:176)
-      const float comp = g == 0 ? (x1 + x2) / 2.f * a.stride : g == 1 ? (y1 + y2) / 2.f * a.stride : g == 2 ? (x2 - x1) * a.stride : (y2 - y1) * a.stride;
+      float comp = g == 0 ? (x1 + x2) / 2.f * a.stride : g == 1 ? (y1 + y2) / 2.f * a.stride : g == 2 ? (x2 - x1) * a.stride : (y2 - y1) * a.stride;
+      if (a.aug) {                                                           // _descale_pred (nn/tasks.py:276-285)
+        comp = comp / a.aug_s;
+        if (g == 0 && a.aug_flip) comp = a.aug_w - comp;
+      }
       {
         float* bt = yt + 32 * DT_P;
         bt[g * DT_P + r] = comp;
@@ -197,9 +203,9 @@ extern "C" int mgdt_detect_tail_supported(int c2, int c3, int nc, int reg_max, i
   return dtype == MGDT_BF16 && reg_max == 4 && c2 % 8 == 0 && c2 <= 32 && c3 % 8 == 0 && c3 <= 128 && nc >= 4 && nc <= 256 && nc % 4 == 0;   // nc % 4: 8-byte rows of the raw map
 }
 
-extern "C" int mgdt_detect_tail_fwd(const mgdt_view* tb, const mgdt_view* tc, const void* wb, const float* bb, const void* wc, const float* bc, int nc,
-                                    float stride, int a_off, int a_total, const mgdt_view* feat, float* y, unsigned long long* best_keys,
-                                    const void* wb3, const float* bb3, mgdt_stream s) {
+static int detect_tail_launch(const mgdt_view* tb, const mgdt_view* tc, const void* wb, const float* bb, const void* wc, const float* bc, int nc,
+                              float stride, int a_off, int a_total, const mgdt_view* feat, float* y, unsigned long long* best_keys,
+                              const void* wb3, const float* bb3, bool aug, float aug_scale, int aug_flip, float aug_img_w, mgdt_stream s) {
   if (!view_ok(tb) || !view_ok(tc) || !view_ok(feat) || !wb || !bb || !wc || !bc || !y) MGDT_FAIL(MGDT_BAD_ARG, "detect_tail: null/empty argument");
   if (!mgdt_detect_tail_supported(tb->c, tc->c, nc, 4, MGDT_BF16)) MGDT_FAIL(MGDT_BAD_SHAPE, "detect_tail: c2=%d c3=%d nc=%d not covered", tb->c, tc->c, nc);
   if (feat->c != 16 + nc || tb->n != tc->n || tb->h != tc->h || tb->w != tc->w || feat->n != tb->n || feat->h != tb->h || feat->w != tb->w ||
@@ -226,6 +232,7 @@ extern "C" int mgdt_detect_tail_fwd(const mgdt_view* tb, const mgdt_view* tc, co
   a.kch = cdiv(tc->c, 32); a.nbc = cdiv(nc, 16);
   a.units_per_img = cdiv(a.HW, 32); a.units = a.N * a.units_per_img;
   a.a_off = a_off; a.a_total = a_total; a.stride = stride; a.fd_w = make_fastdiv((uint32_t)tb->w);
+  a.aug = aug ? 1 : 0; a.aug_flip = aug_flip ? 1 : 0; a.aug_s = aug_scale; a.aug_w = aug_img_w;
   const size_t lds = 1024 + (size_t)a.kch * a.nbc * 1024 + (size_t)(16 + a.nbc * 16) * 4 + (size_t)4 * DT_WT * 4 + 5 * 1024 + 64;
   if (lds > 150 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "detect_tail: nc=%d needs %zu B of LDS", nc, lds);
   static size_t attr = 0;
@@ -238,4 +245,17 @@ extern "C" int mgdt_detect_tail_fwd(const mgdt_view* tb, const mgdt_view* tc, co
   detect_tail_kernel<<<grid, DT_THREADS, lds, (hipStream_t)s>>>(a);
   MGDT_CHECK_LAUNCH("detect_tail_fwd");
   return MGDT_OK;
+}
+
+extern "C" int mgdt_detect_tail_fwd(const mgdt_view* tb, const mgdt_view* tc, const void* wb, const float* bb, const void* wc, const float* bc, int nc,
+                                    float stride, int a_off, int a_total, const mgdt_view* feat, float* y, unsigned long long* best_keys,
+                                    const void* wb3, const float* bb3, mgdt_stream s) {
+  return detect_tail_launch(tb, tc, wb, bb, wc, bc, nc, stride, a_off, a_total, feat, y, best_keys, wb3, bb3, false, 1.f, 0, 0.f, s);
+}
+
+extern "C" int mgdt_detect_tail_aug_fwd(const mgdt_view* tb, const mgdt_view* tc, const void* wb, const float* bb, const void* wc, const float* bc, int nc,
+                                        float stride, int a_off, int a_total, const mgdt_view* feat, float* y, unsigned long long* best_keys,
+                                        const void* wb3, const float* bb3, float aug_scale, int aug_flip, float aug_img_w, mgdt_stream s) {
+  if (!(aug_scale > 0.f)) MGDT_FAIL(MGDT_BAD_ARG, "detect_tail_aug: scale %g", (double)aug_scale);
+  return detect_tail_launch(tb, tc, wb, bb, wc, bc, nc, stride, a_off, a_total, feat, y, best_keys, wb3, bb3, true, aug_scale, aug_flip, aug_img_w, s);
 }

@@ -1485,10 +1485,27 @@ extern "C" int mgdt_grn_stats_fwd(const mgdt_view* t, const float* gamma, float*
 }
 
 // ------------------------------------------------------------------------------------------------ Detect decode
+// Test-time augmentation epilogue (mgdt_detect_decode_aug_fwd, nn/tasks.py:276-285 _descale_pred): xywh /= s, then x = img_w - x for the
+// left-right flipped pass; `best` (optional) receives the NMS key of every anchor's best class, as mgdt_detect_tail_fwd writes it.
+struct DecAug {
+  int on, flip;
+  float s, img_w;
+  unsigned long long* best;
+  __device__ __forceinline__ void apply(float (&v)[4]) const {
+    if (!on) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = v[k] / s;
+    if (flip) v[0] = img_w - v[0];
+  }
+};
+__device__ __forceinline__ unsigned long long best_key(float score, int anchor, int nc, int cls) {
+  return ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(score)) << 32) | (unsigned long long)((unsigned)anchor * (unsigned)nc + (unsigned)cls);
+}
+
 // One thread per (image, anchor).  y[n][ch][a] is anchor-contiguous, so a wave's stores per channel are coalesced.
 template <typename T>
 __global__ void detect_decode_kernel(const T* __restrict__ f, long sn, long sh, long sw, int N, int H, int W, int R, int nc,
-                                     float stride, int a_off, int a_total, float* __restrict__ y) {
+                                     float stride, int a_off, int a_total, float* __restrict__ y, DecAug aug) {
   long total = (long)N * H * W;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     int a = (int)(i % ((long)H * W));
@@ -1511,11 +1528,18 @@ __global__ void detect_decode_kernel(const T* __restrict__ f, long sn, long sh, 
     float ax = (float)ox + 0.5f, ay = (float)oy + 0.5f;
     float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
     float* yo = y + (long)n * (4 + nc) * a_total + a_off + a;
-    yo[0] = (x1 + x2) / 2.f * stride;
-    yo[(long)a_total] = (y1 + y2) / 2.f * stride;
-    yo[2L * a_total] = (x2 - x1) * stride;
-    yo[3L * a_total] = (y2 - y1) * stride;
-    for (int c = 0; c < nc; ++c) yo[(long)(4 + c) * a_total] = 1.f / (1.f + expf(-(float)p[4 * R + c]));
+    float xywh[4] = {(x1 + x2) / 2.f * stride, (y1 + y2) / 2.f * stride, (x2 - x1) * stride, (y2 - y1) * stride};
+    aug.apply(xywh);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) yo[(long)k * a_total] = xywh[k];
+    float bs = -1.f;
+    int bc = 0;
+    for (int c = 0; c < nc; ++c) {
+      const float sg = 1.f / (1.f + expf(-(float)p[4 * R + c]));
+      yo[(long)(4 + c) * a_total] = sg;
+      if (sg > bs) { bs = sg; bc = c; }
+    }
+    if (aug.best) aug.best[(long)n * a_total + a_off + a] = best_key(bs, a_off + a, nc, bc);
   }
 }
 
@@ -1524,7 +1548,7 @@ __global__ void detect_decode_kernel(const T* __restrict__ f, long sn, long sh, 
 #define DEC_A 128
 template <typename T>
 __global__ __launch_bounds__(256) void detect_decode_tile_kernel(const T* __restrict__ f, long sn, long sh, long sw, int H, int W, int R,
-                                                                 int nc, float stride, int a_off, int a_total, float* __restrict__ y) {
+                                                                 int nc, float stride, int a_off, int a_total, float* __restrict__ y, DecAug aug) {
   extern __shared__ float tile[];
   const int no = 4 * R + nc, ld = no + 1, HW = H * W;
   const int n = blockIdx.y, a0 = blockIdx.x * DEC_A;
@@ -1557,19 +1581,29 @@ __global__ __launch_bounds__(256) void detect_decode_tile_kernel(const T* __rest
     int oy = a / W, ox = a - oy * W;
     float ax = (float)ox + 0.5f, ay = (float)oy + 0.5f;
     float x1 = ax - dd[0], y1 = ay - dd[1], x2 = ax + dd[2], y2 = ay + dd[3];
-    yo[al] = (x1 + x2) / 2.f * stride;
-    yo[(long)a_total + al] = (y1 + y2) / 2.f * stride;
-    yo[2L * a_total + al] = (x2 - x1) * stride;
-    yo[3L * a_total + al] = (y2 - y1) * stride;
+    float xywh[4] = {(x1 + x2) / 2.f * stride, (y1 + y2) / 2.f * stride, (x2 - x1) * stride, (y2 - y1) * stride};
+    aug.apply(xywh);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) yo[(long)k * a_total + al] = xywh[k];
   }
   for (int i = threadIdx.x; i < nc * DEC_A; i += 256) {   // cls: sigmoid, lanes = consecutive anchors of one channel plane
     int c = i / DEC_A, al = i - c * DEC_A;
     if (al < na) yo[(long)(4 + c) * a_total + al] = 1.f / (1.f + expf(-tile[al * ld + 4 * R + c]));
   }
+  if (aug.best && threadIdx.x < na) {     // NMS key of the anchor's best class: the same sigmoid as the stored score, first maximal class
+    const int al = threadIdx.x;
+    float bs = -1.f;
+    int bc = 0;
+    for (int c = 0; c < nc; ++c) {
+      const float sg = 1.f / (1.f + expf(-tile[al * ld + 4 * R + c]));
+      if (sg > bs) { bs = sg; bc = c; }
+    }
+    aug.best[(long)n * a_total + a_off + a0 + al] = best_key(bs, a_off + a0 + al, nc, bc);
+  }
 }
 
-extern "C" int mgdt_detect_decode_fwd(const mgdt_view* feat, int reg_max, int nc, float stride, int a_off, int a_total, float* y,
-                                      int dtype, mgdt_stream s) {
+static int detect_decode_launch(const mgdt_view* feat, int reg_max, int nc, float stride, int a_off, int a_total, float* y, int dtype, DecAug aug,
+                                mgdt_stream s) {
   if (!view_ok(feat) || !y) MGDT_FAIL(MGDT_BAD_ARG, "detect_decode: null/empty argument");
   if (feat->sc != 1 || feat->c != 4 * reg_max + nc || reg_max < 1 || a_off < 0 || a_off + feat->h * feat->w > a_total)
     MGDT_FAIL(MGDT_BAD_SHAPE, "detect_decode: c=%d reg_max=%d nc=%d a_off=%d a_total=%d", feat->c, reg_max, nc, a_off, a_total);
@@ -1588,13 +1622,24 @@ extern "C" int mgdt_detect_decode_fwd(const mgdt_view* feat, int reg_max, int nc
     }
     dim3 grid(cdiv((long)feat->h * feat->w, DEC_A), feat->n);
     MGDT_DISPATCH_DTYPE(dtype, (detect_decode_tile_kernel<T><<<grid, 256, lds, (hipStream_t)s>>>((const T*)feat->p, feat->sn, feat->sh, feat->sw, feat->h, feat->w,
-                                                                                                 reg_max, nc, stride, a_off, a_total, y)));
+                                                                                                 reg_max, nc, stride, a_off, a_total, y, aug)));
     MGDT_CHECK_LAUNCH("detect_decode_fwd");
     return MGDT_OK;
   }
   long total = (long)feat->n * feat->h * feat->w;
   MGDT_DISPATCH_DTYPE(dtype, (detect_decode_kernel<T><<<grid_for(total, 64), 64, 0, (hipStream_t)s>>>((const T*)feat->p, feat->sn, feat->sh, feat->sw, feat->n,
-                                                                                                feat->h, feat->w, reg_max, nc, stride, a_off, a_total, y)));
+                                                                                                feat->h, feat->w, reg_max, nc, stride, a_off, a_total, y, aug)));
   MGDT_CHECK_LAUNCH("detect_decode_fwd");
   return MGDT_OK;
+}
+
+extern "C" int mgdt_detect_decode_fwd(const mgdt_view* feat, int reg_max, int nc, float stride, int a_off, int a_total, float* y,
+                                      int dtype, mgdt_stream s) {
+  return detect_decode_launch(feat, reg_max, nc, stride, a_off, a_total, y, dtype, DecAug{0, 0, 1.f, 0.f, nullptr}, s);
+}
+
+extern "C" int mgdt_detect_decode_aug_fwd(const mgdt_view* feat, int reg_max, int nc, float stride, int a_off, int a_total, float* y,
+                                          unsigned long long* best_keys, float aug_scale, int aug_flip, float aug_img_w, int dtype, mgdt_stream s) {
+  if (!(aug_scale > 0.f)) MGDT_FAIL(MGDT_BAD_ARG, "detect_decode_aug: scale %g", (double)aug_scale);
+  return detect_decode_launch(feat, reg_max, nc, stride, a_off, a_total, y, dtype, DecAug{1, aug_flip ? 1 : 0, aug_scale, aug_img_w, best_keys}, s);
 }

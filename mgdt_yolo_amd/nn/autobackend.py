@@ -32,12 +32,13 @@ class AutoBackend(nn.Module):
         self.fp16, self.device, self.nhwc, self.triton = bool(fp16), device, False, False
 
     def forward(self, im, augment=False, visualize=False):
-        """(y, feats) of the detection model (autobackend.py:313-314).  uint8 images are accepted as they are (the stem divides by 255)."""
-        if augment or visualize:
-            raise RuntimeError('augment / visualize are host-side tooling outside the hot path')
+        """(y, feats) of the detection model (autobackend.py:313-314); `augment=True`: (y, None) of its test-time augmentation
+        (DetectionModel._predict_augment).  uint8 images are accepted as they are (the stem / the resampling kernel divide by 255)."""
+        if visualize:
+            raise RuntimeError('visualize is host-side tooling outside the hot path')
         if self.fp16 and im.dtype == torch.float32:
             im = im.to(torch.bfloat16)                          # `im.half()` of the reference (:304-305), in this path's half type
-        return self.model(im)
+        return self.model(im, augment=True) if augment else self.model(im)
 
     def warmup(self, imgsz=(1, 3, 640, 640)):
         """One forward on a dummy input: packs every weight panel and lets the allocator settle (autobackend.py:415-427)."""

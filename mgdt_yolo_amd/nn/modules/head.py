@@ -68,13 +68,22 @@ class Detect(HipModule):
         shape = x[0].shape
         r4 = 4 * self.reg_max
         y, a_off, strides = None, 0, None
-        if not self.training:
+        tta = None if self.training else self.__dict__.get('_tta')     # one pass of DetectionModel._predict_augment
+        aug = None if tta is None else tta['aug']
+        if tta is not None:
+            strides = self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])
+            y, best, a_off = tta['y'], tta['best'], tta['a_off']
+        elif not self.training:
             strides = self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])  # host copy, no sync per call
             a_total = sum(t.shape[2] * t.shape[3] for t in x)
             y = torch.empty(shape[0], 4 + self.nc, a_total, dtype=torch.float32, device=x[0].device)
             best = torch.empty(shape[0], a_total, dtype=torch.int64, device=x[0].device)      # NMS keys of the anchors' best classes (detect tail)
         decoded = [False] * self.nl
+        offs = [None] * self.nl
         for i in range(self.nl):
+            if tta is not None and i not in tta['levels']:
+                continue                                      # every anchor of this level is clipped away (_clip_augmented): not run
+            offs[i] = a_off
             xi = x[i]
             b, _, h, w = xi.shape
             feat = ops.new_act(b, self.no, h, w, self.cv2[i][0].out_dtype(xi), xi.device)
@@ -90,7 +99,7 @@ class Detect(HipModule):
                     pk3, pkb_pad = box3
                     pkc = self._cached((id(self.cv3[i][2]), feat.dtype), [self.cv3[i][2].weight, self.cv3[i][2].bias],
                                        lambda c=self.cv3[i][2]: ops.PackedConv(c.weight, c.bias, None, 1, feat.dtype))
-                    ops.detect_tail(t01[:, :c2], tc, pkb_pad, pkc, self.nc, strides[i], a_off, feat, y, best, pk3=pk3)
+                    ops.detect_tail(t01[:, :c2], tc, pkb_pad, pkc, self.nc, strides[i], a_off, feat, y, best, pk3=pk3, aug=aug)
                     decoded[i] = True
                     a_off += h * w
                     x[i] = feat
@@ -105,7 +114,7 @@ class Detect(HipModule):
                                    lambda c=self.cv2[i][2]: ops.PackedConv(c.weight, c.bias, None, 1, feat.dtype))
                 pkc = self._cached((id(self.cv3[i][2]), feat.dtype), [self.cv3[i][2].weight, self.cv3[i][2].bias],
                                    lambda c=self.cv3[i][2]: ops.PackedConv(c.weight, c.bias, None, 1, feat.dtype))
-                ops.detect_tail(tb, tc, pkb, pkc, self.nc, strides[i], a_off, feat, y, best)
+                ops.detect_tail(tb, tc, pkb, pkc, self.nc, strides[i], a_off, feat, y, best, aug=aug)
                 decoded[i] = True
             else:
                 _HeadConv.run(self, self.cv2[i][2], tb, feat[:, :r4])
@@ -117,6 +126,11 @@ class Detect(HipModule):
             x[i] = feat
         if self.training:
             return x
+        if tta is not None:
+            for i in tta['levels']:
+                if not decoded[i]:
+                    ops.detect_decode(x[i], self.reg_max, self.nc, strides[i], offs[i], y, aug=aug, best=best)
+            return y, x
         if self.dynamic or self.shape != shape:
             from ...yolo.utils.tal import make_anchors
             self.anchors, self.strides = (t.transpose(0, 1) for t in make_anchors(x, strides, 0.5))
@@ -405,7 +419,10 @@ class TOODHead(Detect):
     def forward(self, x):
         shape = x[0].shape
         r4 = 4 * self.reg_max
+        tta = None if self.training else self.__dict__.get('_tta')     # one pass of DetectionModel._predict_augment
         for i in range(self.nl):
+            if tta is not None and i not in tta['levels']:
+                continue                                                # every anchor of this level is clipped away: not run
             xi = x[i]
             b, _, h, w = xi.shape
             dt = self.share_conv[0].out_dtype(xi)
@@ -430,6 +447,12 @@ class TOODHead(Detect):
         if self.training:
             return x
         strides = self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])
+        if tta is not None:
+            a_off = tta['a_off']
+            for i in tta['levels']:
+                ops.detect_decode(x[i], self.reg_max, self.nc, strides[i], a_off, tta['y'], aug=tta['aug'], best=tta['best'])
+                a_off += x[i].shape[2] * x[i].shape[3]
+            return tta['y'], x
         if self.dynamic or self.shape != shape:
             from ...yolo.utils.tal import make_anchors
             self.anchors, self.strides = (t.transpose(0, 1) for t in make_anchors(x, strides, 0.5))

@@ -8,6 +8,7 @@ All per-layer compute runs in libmgdt_hip.so; there is no CPU or ATen fallback (
 """
 import ast
 import contextlib
+import math
 import re
 from copy import deepcopy
 from pathlib import Path
@@ -63,8 +64,12 @@ class BaseModel(nn.Module):
         return self.predict(x, *args, **kwargs)
 
     def predict(self, x, profile=False, visualize=False, augment=False):
-        if augment or profile or visualize:
-            raise RuntimeError('augment / profile / visualize are host-side tooling outside the hot path')
+        if profile or visualize:
+            raise RuntimeError('profile / visualize are host-side tooling outside the hot path')
+        if augment:                                         # test-time augmentation (tasks.py:57-58): inference only
+            if self.training or not hasattr(self, '_predict_augment'):
+                raise RuntimeError('augment=True is an inference call form: put the detection model in eval() (augmented training is not built)')
+            return self._predict_augment(x)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.model[0].parameters()):
             # training call form of the reference: the outputs carry a grad_fn, `loss.backward()` runs the HIP reverse pass
             if not hasattr(self, '_anchor'):
@@ -461,6 +466,107 @@ class DetectionModel(BaseModel):
     def init_criterion(self):
         from ..yolo.utils.loss import v8DetectionLoss
         return v8DetectionLoss(self)
+
+    # -- test-time augmentation (tasks.py:256-287) -------------------------------------------------------
+    def _predict_augment(self, x):
+        """(y (B, 4+nc, A_tta) fp32, None): the three passes of the reference (scales 1 / 0.83 / 0.67, the second one left-right flipped), each
+        de-scaled and clipped exactly as `_descale_pred` + `_clip_augmented` do, written straight into one merged `y`.  Per pass: one
+        mgdt_scale_img_fwd launch (none for the unscaled pass), the layer loop, and a head that runs only the levels the clip keeps, with the
+        de-scaling epilogue of its decode kernels writing at the pass's anchor offset (and the NMS best-class keys next to it).  A pass or a head
+        level whose anchors are all clipped is not run: for a one-level head (nl = 1) only the flipped 0.83 pass is left.  No host sync, so the
+        whole call captures into one graph."""
+        if not x.is_cuda:
+            raise RuntimeError('mgdt_yolo_amd runs on MI355X (HIP) only: move the model and the input to cuda (no CPU fallback)')
+        head = self.model[-1]
+        if not isinstance(head, Detect):
+            raise RuntimeError(f'augment=True: {type(head).__name__} heads are outside the detection path')
+        if self.__dict__.get('fp8_table'):
+            raise RuntimeError('augment=True is not built for the fp8-quantised model: its activation multipliers were calibrated at one input '
+                               'scale; dequantize_fp8() first')
+        strides = head._cached('stride_list', [head.stride], lambda: [float(v) for v in head.stride.tolist()])
+        h, w = int(x.shape[2]), int(x.shape[3])
+        geo = tta_geometry(h, w, strides)
+        b = x.shape[0]
+        y = torch.empty(b, 4 + head.nc, geo['anchors'], dtype=torch.float32, device=x.device)
+        best = torch.empty(b, geo['anchors'], dtype=torch.int64, device=x.device)
+        for p in geo['passes']:
+            if not p['levels_run']:
+                continue
+            if p['scale'] == 1 and not p['flip']:
+                xi = x                                                    # scale_img(ratio=1) returns the image unchanged
+            else:
+                xi = ops.scale_img(x, *p['resized'], *p['size'], p['flip'], self.compute_dtype)
+            head.__dict__['_tta'] = dict(y=y, best=best, a_off=p['a_off'], levels=p['levels_run'], aug=(p['scale'], p['flip'], float(w)))
+            try:
+                self._predict_once(xi)
+            finally:
+                head.__dict__.pop('_tta', None)
+        ops.attach_best_keys(y, best)        # every kept anchor's key was written by its level's tail / decode launch: NMS skips its scan
+        return y, None
+
+    @staticmethod
+    def _descale_pred(p, flips, scale, img_size, dim=1):
+        """De-scale predictions following augmented inference (tasks.py:276-285), on plain tensors."""
+        p[:, :4] /= scale
+        x, y, wh, cls = p.split((1, 1, 2, p.shape[dim] - 4), dim)
+        if flips == 2:
+            y = img_size[0] - y
+        elif flips == 3:
+            x = img_size[1] - x
+        return torch.cat((x, y, wh, cls), dim)
+
+    def _clip_augmented(self, y):
+        """Clip the augmented tails (tasks.py:287-296): the last level's anchors of the first pass, the first level's of the last."""
+        nl = self.model[-1].nl
+        g = sum(4 ** x for x in range(nl))
+        e = 1
+        i = (y[0].shape[-1] // g) * sum(4 ** x for x in range(e))
+        y[0] = y[0][..., :-i]
+        i = (y[-1].shape[-1] // g) * sum(4 ** (nl - 1 - x) for x in range(e))
+        y[-1] = y[-1][..., i:]
+        return y
+
+
+TTA_SCALES, TTA_FLIPS = (1, 0.83, 0.67), (None, 3, None)        # tasks.py:262-263 (flip 3 = left-right)
+
+
+def tta_geometry(h, w, strides):
+    """Host-side plan of `_predict_augment` for an h x w input and the head's level strides (no GPU).  gs = the model's own largest stride
+    (tasks.py:266, not AutoBackend's max(stride, 32)).  Per pass: scale, flip, resized (int(h*r), int(w*r)), size (padded up to multiples of gs;
+    the input's own for ratio 1), per-level anchor counts, the anchor range [lo, hi) `_clip_augmented` keeps, the head levels whose anchors
+    are all kept (`levels_run`; the others are all clipped and not run) and the pass's offset in the merged output.  Raises when a clip
+    boundary falls inside a level (only possible for inputs that are not multiples of gs)."""
+    strides = [int(s) for s in strides]
+    gs, nl = max(strides), len(strides)
+    passes = []
+    for si, fi in zip(TTA_SCALES, TTA_FLIPS):
+        if si == 1:
+            resized = size = (h, w)
+        else:
+            resized = (int(h * si), int(w * si))
+            size = tuple(math.ceil(v * si / gs) * gs for v in (h, w))
+        levels = [-(-size[0] // s) * -(-size[1] // s) for s in strides]
+        passes.append(dict(scale=si, flip=fi == 3, resized=resized, size=size, levels=levels, anchors=sum(levels)))
+    g = sum(4 ** x for x in range(nl))
+    a0, a2 = passes[0]['anchors'], passes[-1]['anchors']
+    i0 = a0 // g
+    passes[0]['keep'] = (0, max(a0 - i0, 0) if i0 else 0)                     # y[0][..., :-i] (an empty slice when i == 0)
+    passes[1]['keep'] = (0, passes[1]['anchors'])
+    passes[2]['keep'] = (min((a2 // g) * 4 ** (nl - 1), a2), a2)              # y[-1][..., i:]
+    off = 0
+    for k, p in enumerate(passes):
+        lo, hi = p['keep']
+        run, start = [], 0
+        for li, n in enumerate(p['levels']):
+            if lo <= start and start + n <= hi and n:
+                run.append(li)
+            elif start < hi and start + n > lo and n:
+                raise RuntimeError(f'augment=True: the clip of pass {k} ({lo}..{hi}) cuts head level {li} ({start}..{start + n}) at input {h}x{w}; '
+                                   f'use an input size that is a multiple of the largest stride {gs}')
+            start += n
+        p['levels_run'], p['a_off'] = run, off
+        off += max(hi - lo, 0)
+    return {'gs': gs, 'passes': passes, 'anchors': off}
 
 
 # ---------------------------------------------------------------------------------------------------------------

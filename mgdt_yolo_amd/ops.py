@@ -762,10 +762,16 @@ def inject(local, ga, gf, out=None):
     return out
 
 
-def detect_decode(feat, reg_max, nc, stride, a_off, y):
-    """feat (B,no,H,W) NHWC -> y[B, 4+nc, A_total] fp32 at anchor offset a_off."""
-    _launch('detect_decode_fwd', 'mgdt_detect_decode_fwd', vp(feat), reg_max, nc, float(stride), a_off, y.shape[2], ptr(y), dtype_code(feat.dtype),
-                                           stream())
+def detect_decode(feat, reg_max, nc, stride, a_off, y, aug=None, best=None):
+    """feat (B,no,H,W) NHWC -> y[B, 4+nc, A_total] fp32 at anchor offset a_off.  aug = (scale, flip, img_w): the test-time augmentation
+    epilogue (mgdt_detect_decode_aug_fwd: xywh / scale, x = img_w - x when flipped), with the best-class NMS keys into `best` (int64 [B][A_total])."""
+    if aug is None:
+        _launch('detect_decode_fwd', 'mgdt_detect_decode_fwd', vp(feat), reg_max, nc, float(stride), a_off, y.shape[2], ptr(y), dtype_code(feat.dtype),
+                stream())
+        return
+    s, flip, img_w = aug
+    _launch('detect_decode_aug_fwd', 'mgdt_detect_decode_aug_fwd', vp(feat), reg_max, nc, float(stride), a_off, y.shape[2], ptr(y), ptr(best), float(s),
+            int(bool(flip)), float(img_w), dtype_code(feat.dtype), stream())
 
 
 FUSED_DETECT_TAIL = True   # tests flip this to compare against conv + conv + decode
@@ -779,16 +785,38 @@ def detect_tail_supported(tb, tc, nc, reg_max, dtype):
 FUSED_DETECT_BOX3 = True   # tests flip this: the box branch's second 3x3 conv inside the Detect tail launch vs a launch of its own
 
 
-def detect_tail(tb, tc, pkb, pkc, nc, stride, a_off, feat, y, best=None, pk3=None):
+def detect_tail(tb, tc, pkb, pkc, nc, stride, a_off, feat, y, best=None, pk3=None, aug=None):
     """mgdt_detect_tail_fwd: final 1x1 convs of both branches + raw map `feat` + decode into y (+ per-anchor best-class NMS keys into `best`,
     int64 [B][A], when given).  pk3: PackedConv of the box branch's second 3x3 conv - `tb` is then that conv's 16-channel input and `pkb` the
-    final 1x1 packed over 32 zero-padded input channels."""
+    final 1x1 packed over 32 zero-padded input channels.  aug = (scale, flip, img_w): mgdt_detect_tail_aug_fwd, the test-time augmentation
+    epilogue (xywh / scale, x = img_w - x when flipped)."""
     if _PROF is not None:
         b, _, h, w = tb.shape
         _META['detect_tail_fwd'] = dict(shape=(b, tb.shape[1] + tc.shape[1], h, w, 16 + nc, 1, 1), flops=2.0 * b * h * w * (tb.shape[1] * 16 + tc.shape[1] * nc),
                                         bytes=float((tb.numel() + tc.numel() + feat.numel()) * 2 + b * (4 + nc) * h * w * 4))
-    _launch('detect_tail_fwd', 'mgdt_detect_tail_fwd', vp(tb), vp(tc), ptr(pkb.w), ptr(pkb.bias), ptr(pkc.w), ptr(pkc.bias), int(nc), float(stride), int(a_off),
-            y.shape[2], vp(feat), ptr(y), ptr(best), None if pk3 is None else ptr(pk3.w), None if pk3 is None else ptr(pk3.bias), stream())
+    args = (vp(tb), vp(tc), ptr(pkb.w), ptr(pkb.bias), ptr(pkc.w), ptr(pkc.bias), int(nc), float(stride), int(a_off), y.shape[2], vp(feat), ptr(y), ptr(best),
+            None if pk3 is None else ptr(pk3.w), None if pk3 is None else ptr(pk3.bias))
+    if aug is None:
+        _launch('detect_tail_fwd', 'mgdt_detect_tail_fwd', *args, stream())
+    else:
+        _launch('detect_tail_aug_fwd', 'mgdt_detect_tail_aug_fwd', *args, float(aug[0]), int(bool(aug[1])), float(aug[2]), stream())
+
+
+# ------------------------------------------------------------------ test-time augmentation input
+TTA_PAD = 0.447          # scale_img's padding value (yolo/utils/torch_utils.py:270, the ImageNet mean)
+
+
+def scale_img(x, hs, ws, hp, wp, flip, dtype):
+    """mgdt_scale_img_fwd: x (B, 3, H, W) image (uint8 / fp32 / bf16, any strides; uint8 / 255) -> (B, 3, hp, wp) contiguous `dtype` image: the
+    (left-right flipped when `flip`) image resized to hs x ws (bilinear, align_corners=False), padded with TTA_PAD to hp x wp."""
+    _need_gpu(x)
+    y = torch.empty(x.shape[0], 3, hp, wp, dtype=dtype, device=x.device)
+    if _PROF is not None:
+        _META['scale_img_fwd'] = dict(shape=(x.shape[0], 3, x.shape[2], x.shape[3], 3, hp, wp), flops=0.0,
+                                      bytes=float(x.numel() * x.element_size() + y.numel() * y.element_size()))
+    _launch('scale_img_fwd', 'mgdt_scale_img_fwd', vp(x), U8 if x.dtype == torch.uint8 else dtype_code(x.dtype), int(bool(flip)), int(hs), int(ws),
+            float(TTA_PAD), vp(y), dtype_code(dtype), stream())
+    return y
 
 
 # ------------------------------------------------------------------ NMS

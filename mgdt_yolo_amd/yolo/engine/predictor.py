@@ -13,7 +13,8 @@ from ..data.augment import LetterBox
 
 class BasePredictor:
     def __init__(self, overrides=None):
-        o = dict(conf=0.25, iou=0.7, imgsz=640, half=False, agnostic_nms=False, max_det=300, classes=None, device='cuda:0')   # yolo/cfg/default.yaml + model.py:241
+        o = dict(conf=0.25, iou=0.7, imgsz=640, half=False, agnostic_nms=False, max_det=300, classes=None, device='cuda:0',   # yolo/cfg/default.yaml + model.py:241
+                 augment=False)
         o.update(overrides or {})
         self.args = types.SimpleNamespace(**o)
         self.imgsz = self.args.imgsz if isinstance(self.args.imgsz, (tuple, list)) else (self.args.imgsz, self.args.imgsz)
@@ -45,8 +46,9 @@ class BasePredictor:
         return im.to(self.device)
 
     def inference(self, im):
+        """predictor.py:244: AutoBackend.forward(im, augment=self.args.augment)."""
         with torch.no_grad():
-            return self.model(im)
+            return self.model(im, augment=self.args.augment) if self.args.augment else self.model(im)
 
     def postprocess(self, preds, img, orig_imgs):
         return preds
