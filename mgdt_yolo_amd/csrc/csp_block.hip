@@ -12,9 +12,12 @@
 // which is recomputed per tile (the recomputed part is cheap: K <= 576, and it is MFMA work that replaces HBM round trips).
 //
 // Layout on the CU: two NHWC maps P (bottleneck input / output) and T (its hidden map) over the (TH+2h) x (TW+2h) region, pixel stride
-// wd*2 + 16 bytes (an odd number of 16-byte slots: 16 consecutive pixels hit 16 different LDS slots), and the concat buffer of the
-// tile's own pixels.  Every 3x3 conv walks its output rectangle as one linear pixel range (the wrap-around columns are computed and
-// never consumed), so a tap is a constant byte offset: B operand = one ds_read_b128 at (pixel + tap) * stride + piece * 16.
+// wd*2 bytes, and the concat buffer of the tile's own pixels without the last bottleneck's output (the back conv reads that one from P).
+// No padding: the 16-byte slots of a pixel row are XOR-swizzled by the pixel index (csp_psw, cat_at) so that every ds_read_b128 lane
+// group of the 3x3 convs and of the back conv hits 16 different slots of the 256-byte bank row.  Every 3x3 conv walks its output
+// rectangle as one linear pixel range (the wrap-around columns are computed and never consumed); the swizzle depends on the pixel
+// index mod 16 only, so a tap stays a per-lane constant byte offset: B operand = one ds_read_b128 at (pixel * stride + boff[tap]).
+// Pixel coordinates (image offset, tile index) are computed from the pixel index where they are needed, not stored in LDS tables.
 // GEMM orientation as conv_igemm: weights = A operand (rows = 16 output channels), pixels = B operand, so a lane ends with 4 consecutive
 // channels of one pixel = one 8-byte LDS / HBM store.  Each wave keeps the weight fragments of ONE cout block of the running conv in
 // registers (weights-stationary: 12..72 VGPRs) and streams pixel groups through them; the packed panels are the ordinary
@@ -34,11 +37,12 @@ struct CspArgs {
   int N, H, W, Cin, Cout, wd, nbtl, shortcut, act;
   int TH, TW, halo, RH, RW, tiles_x, tiles_y, total_tiles, per_xcd;
   int catC, nchb, nbo;                 // concat channels, K chunks / cout blocks of the back conv
-  int RPA, TPA, PS, CS;                // allocated region / tile pixels, pixel strides (bytes) of P/T and of the concat buffer
+  int RPA, TPA, CS;                    // allocated region / tile pixels, pixel stride (bytes) of the concat buffer (P/T: 2 * wd)
+  int catS, cmsk, csh;                 // concat channels held in the concat buffer (catC - wd), its slot swizzle (t >> csh) & cmsk
   int chain_words;                     // MSPA: 16-byte words of the chain blob's weight part
   unsigned long long* dbg;             // MGDT_CSP_DBG: 8 wall-clock stamps (10 ns units) per workgroup
   int pool_gst;                        // back phase: waves per cout block = pool slots per tile (1 when there are >= 8 cout blocks)
-  FastDiv fd_rw, fd_tw, fd_tx, fd_tpi; // table phase: division by region width / tile width / tiles per row / tiles per image without the ~40-instruction sequence
+  FastDiv fd_rw, fd_tw, fd_tx, fd_tpi; // pixel coordinates: division by region width / tile width / tiles per row / tiles per image without the ~40-instruction sequence
 };
 
 constexpr int CSP_THREADS = 512;
@@ -57,6 +61,10 @@ __device__ __forceinline__ void lds_store4(char* p, f32x4 v) {
   for (int i = 0; i < 4; ++i) o[i] = (bf16)v[i];
   *(bf16x4*)p = o;
 }
+// XOR applied to the 16-byte slot index of a P/T pixel (wd * 2 bytes): with it the 3x3 convs' ds_read_b128 lane groups are conflict-free
+// for wd = 32 / 64; for wd <= 16 the unswizzled rows are already within 10 % of conflict-free.  A function of pix mod 16 only.
+template <int WD> __device__ __forceinline__ int csp_psw(int pix) { return WD == 64 ? (pix & 7) : (WD == 32 ? ((pix >> 1) & 3) : 0); }
+
 __device__ __forceinline__ f32x4 lds_load4(const char* p) {
   const bf16x4 o = *(const bf16x4*)p;
   return f32x4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};
@@ -64,19 +72,17 @@ __device__ __forceinline__ f32x4 lds_load4(const char* p) {
 
 // MODE 0 = MSPA_C2f, 1 = C2f.  WD = bottleneck width (8, 16, 32, 64).
 template <int WD, int MODE>
-__global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1)) ? 4 : 2)) void csp_block_kernel(const CspArgs a) {   // 4: two workgroups per CU (<= 128 VGPRs) where LDS allows it
+__global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_kernel(const CspArgs a) {   // 4: two workgroups per CU (<= 128 VGPRs)
   constexpr int CP = WD / 8;                         // 16-byte pieces per tap
   constexpr int NCHB = WD == 8 ? 2 : (WD == 16 ? 3 : (WD == 32 ? 5 : 8));   // K chunks of the back conv at n = 2 (concat <= 256 channels)
   constexpr int NB = WD >= 16 ? WD / 16 : 1;         // cout blocks of a wd -> wd conv
   constexpr int NCH = (9 * CP + 3) / 4;              // K chunks of a 3x3 conv
   constexpr int NBK = NB, KC = (NBK + 1) / 2;        // pw chain geometry (mlp_chain.hip)
+  constexpr int PS = 2 * WD;                         // P/T pixel stride (bytes)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* goff = (int*)smem;                                        // [RPA] byte offset of the region pixel in the x view, MGDT_OOB outside the image
-  int* yoff = goff + a.RPA;                                      // [TPA] byte offset of the tile pixel in the y view
-  short* ctab = (short*)(yoff + a.TPA);                          // [RPA] index of the region pixel in the tile, -1 outside
-  char* Pb = (char*)(ctab + a.RPA);                              // RPA, TPA are multiples of 16: every array below starts 16-byte aligned
-  char* Tb = Pb + (size_t)a.RPA * a.PS;
-  char* catb = Tb + (size_t)a.RPA * a.PS;
+  char* Pb = smem;                                               // RPA, TPA are multiples of 16: every array below starts 16-byte aligned
+  char* Tb = Pb + (size_t)a.RPA * PS;
+  char* catb = Tb + (size_t)a.RPA * PS;                          // [TPA][catS] concat of the tile's pixels (the last bottleneck output stays in P)
   char* wl = catb + (size_t)a.TPA * a.CS;                        // MSPA: staged chain weights + bias
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -92,32 +98,36 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
   const int tyi = (int)fdiv((uint32_t)trem, a.fd_tx);
   const int ty0 = tyi * a.TH, tx0 = (trem - tyi * a.tiles_x) * a.TW;
   const int RP = a.RH * a.RW, TP = a.TH * a.TW;
+  const bool inner = ty0 >= a.halo && tx0 >= a.halo && ty0 + a.TH + a.halo <= a.H && tx0 + a.TW + a.halo <= a.W;   // region inside the image
   auto stamp = [&](int k) __attribute__((always_inline)) { if (a.dbg && tid == 0) a.dbg[(size_t)tlin * 8 + k] = __builtin_amdgcn_s_memrealtime(); };
+  // region pixel q -> byte offset in the x view (MGDT_OOB outside the image) and index in the tile (-1 outside it)
+  auto region_px = [&](int q, int& go, int& ct) __attribute__((always_inline)) {
+    const int ry = (int)fdiv((uint32_t)q, a.fd_rw), rx = q - ry * a.RW;
+    const int iy = ty0 - a.halo + ry, ix = tx0 - a.halo + rx;
+    go = (q < RP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) ? n * a.xsn + iy * a.xsh + ix * a.xsw : MGDT_OOB;
+    const int cy = ry - a.halo, cx = rx - a.halo;
+    ct = (q < RP && (unsigned)cy < (unsigned)a.TH && (unsigned)cx < (unsigned)a.TW) ? cy * a.TW + cx : -1;
+  };
+  // byte offsets of channel c (a multiple of 4) of P/T pixel q and of concat pixel t
+  auto pt_at = [&](int q, int c) __attribute__((always_inline)) { return q * PS + ((((c >> 3) ^ csp_psw<WD>(q)) << 4) | ((c & 7) << 1)); };
+  auto cat_at = [&](int t, int c) __attribute__((always_inline)) { return t * a.CS + ((((c >> 3) ^ ((t >> a.csh) & a.cmsk)) << 4) | ((c & 7) << 1)); };
   stamp(0);
 
   // weights-stationary: this wave's cout block of the running 3x3 conv lives in registers.  Every conv's fragments are requested one
-  // phase AHEAD (the first ones right here, before the tables and the front), so no phase starts by waiting on L2.
+  // phase AHEAD (the first ones right here, before the zero fill and the front), so no phase starts by waiting on L2.
   const int nbv = wave % NB, gvm = wave / NB, gstm = CSP_NW / NB;
   bf16x8 A[NCH];
+  f32x4 bias;
+  auto load_a0 = [&]() __attribute__((always_inline)) {
 #pragma unroll
-  for (int kc = 0; kc < NCH; ++kc) A[kc] = *(const bf16x8*)(a.mid[0] + ((size_t)(kc * NB + nbv) * 64 + lane) * 16);
-  f32x4 bias = *(const f32x4*)(a.mid_bias[0] + nbv * 16 + 4 * g);
+    for (int kc = 0; kc < NCH; ++kc) A[kc] = *(const bf16x8*)(a.mid[0] + ((size_t)(kc * NB + nbv) * 64 + lane) * 16);
+    bias = *(const f32x4*)(a.mid_bias[0] + nbv * 16 + 4 * g);
+  };
+  if (WD != 32 || MODE != 0) load_a0();
 
-  // ---- tables, zero fill, chain weights
-  for (int q = tid; q < a.RPA; q += CSP_THREADS) {
-    const int ry = (int)fdiv((uint32_t)q, a.fd_rw), rx = q - ry * a.RW;
-    const int iy = ty0 - a.halo + ry, ix = tx0 - a.halo + rx;
-    const bool in = q < RP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-    goff[q] = in ? n * a.xsn + iy * a.xsh + ix * a.xsw : MGDT_OOB;
-    const int cy = ry - a.halo, cx = rx - a.halo;
-    ctab[q] = (q < RP && (unsigned)cy < (unsigned)a.TH && (unsigned)cx < (unsigned)a.TW) ? (short)(cy * a.TW + cx) : (short)-1;
-  }
-  for (int t = tid; t < a.TPA; t += CSP_THREADS) {
-    const int cy = (int)fdiv((uint32_t)t, a.fd_tw), cx = t - cy * a.TW;
-    yoff[t] = t < TP ? n * a.ysn + (ty0 + cy) * a.ysh + (tx0 + cx) * a.ysw : MGDT_OOB;
-  }
+  // ---- zero fill, chain weights
   {
-    const int words = (int)(((size_t)2 * a.RPA * a.PS) >> 4);
+    const int words = (int)(((size_t)2 * a.RPA * PS) >> 4);
     uint4* z = (uint4*)Pb;
     for (int i = tid; i < words; i += CSP_THREADS) z[i] = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -149,8 +159,8 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
       for (int u = 0; u < U; ++u) {
         const bool gv_ = g0 + u < gend;
         const int q = (g0 + u) * 16 + r;
-        go[u] = gv_ ? goff[q] : MGDT_OOB;
-        ct[u] = gv_ ? (int)ctab[q] : -1;
+        region_px(q, go[u], ct[u]);
+        if (!gv_) go[u] = MGDT_OOB, ct[u] = -1;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -194,7 +204,7 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
             for (int j = 0; j < 4; ++j) acc[j] = (float)(bf16)csp_act(acc[j], a.act);
             prev[ob] = acc;
             const int c = ob * 16 + 4 * g;
-            if (c < WD && ct[u] >= 0) lds_store4(catb + ct[u] * a.CS + (i * WD + c) * 2, acc);
+            if (c < WD && ct[u] >= 0) lds_store4(catb + cat_at(ct[u], i * WD + c), acc);
           }
         }
         // bottleneck input = sp2 + x3 (the pending add of block.py:259), zero outside the image
@@ -203,7 +213,7 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
           const int c = ob * 16 + 4 * g;
           f32x4 p0 = prev[ob] + X[3][ob];
           if (go[u] == MGDT_OOB) p0 = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (c < WD) lds_store4(Pb + q * a.PS + c * 2, p0);
+          if (c < WD) lds_store4(Pb + pt_at(q, c), p0);
         }
       }
     }
@@ -221,8 +231,8 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
       for (int u = 0; u < U; ++u) {
         const bool gv_ = g0 + u < gend;
         const int q = (g0 + u) * 16 + r;
-        go[u] = gv_ ? goff[q] : MGDT_OOB;
-        ct[u] = gv_ ? (int)ctab[q] : -1;
+        region_px(q, go[u], ct[u]);
+        if (!gv_) go[u] = MGDT_OOB, ct[u] = -1;
 #pragma unroll
         for (int blk = 0; blk < NB2; ++blk)
           XR[u][blk] = __builtin_amdgcn_raw_buffer_load_b64(xrs, (uint32_t)go[u] + (uint32_t)((blk * 16 + 4 * g) * 2), 0, 0);   // zeros outside the image
@@ -234,12 +244,13 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
 #pragma unroll
         for (int blk = 0; blk < NB2; ++blk) {
           const int cc = blk * 16 + 4 * g;
-          if (ct[u] >= 0) *(csp_raw2*)(catb + ct[u] * a.CS + cc * 2) = XR[u][blk];
-          if (cc >= WD) *(csp_raw2*)(Pb + q * a.PS + (cc - WD) * 2) = XR[u][blk];      // second half = the bottleneck chain's input (block.py:201-203)
+          if (ct[u] >= 0) *(csp_raw2*)(catb + cat_at(ct[u], cc)) = XR[u][blk];
+          if (cc >= WD) *(csp_raw2*)(Pb + pt_at(q, cc - WD)) = XR[u][blk];      // second half = the bottleneck chain's input (block.py:201-203)
         }
       }
     }
   }
+  if (WD == 32 && MODE == 0) load_a0();
   stamp(2);
   __syncthreads();
   stamp(3);
@@ -251,14 +262,6 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
   const int bgst = a.pool_gst, bgv = wave / (CSP_NW / bgst), obst = CSP_NW / bgst, ob0 = wave % obst;
   {
     const int gv = gvm, gst = gstm;
-    int boff[NCH];                                               // this lane's byte offset of chunk kc's piece relative to its pixel
-#pragma unroll
-    for (int kc = 0; kc < NCH; ++kc) {
-      const int p = kc * 4 + g;
-      int tap = p / CP, cp = p - tap * CP;
-      if (tap >= 9) { tap = 4; cp = 0; }                         // padded piece: weights are zero, read something finite
-      boff[kc] = ((tap / 3 - 1) * a.RW + (tap % 3 - 1)) * a.PS + cp * 16;
-    }
     const int cch = nbv * 16 + 4 * g;                            // this lane's first output channel
     const int slot0 = (MODE == 0 ? 3 : 2) * WD;                  // concat offset of the first bottleneck output
     for (int j = 0; j < 2 * a.nbtl; ++j) {
@@ -285,26 +288,38 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
       const int lo = (j + 1) * a.RW + (j + 1), hi = (a.RH - j - 2) * a.RW + (a.RW - j - 1);
       const int ng = (hi - lo + 15) >> 4;
       const bool second = j & 1;
+      const bool tocat = second && (j >> 1) + 1 < a.nbtl;       // the last bottleneck's output is read from P by the back conv
+      // zero outside the image: only where a later conv reads it as padding, and only on tiles whose region crosses the image border
+      // (the last conv's outside pixels are wrap-around columns nobody reads)
+      const bool zchk = !inner && j + 1 < 2 * a.nbtl;
+      int boff[NCH];                                             // this lane's byte offset of chunk kc's piece relative to its pixel's row
+#pragma unroll
+      for (int kc = 0; kc < NCH; ++kc) {
+        const int p = kc * 4 + g;
+        int tap = p / CP, cp = p - tap * CP;
+        if (tap >= 9) { tap = 4; cp = 0; }                       // padded piece: weights are zero, read something finite
+        const int toff = (tap / 3 - 1) * a.RW + (tap % 3 - 1);
+        boff[kc] = toff * PS + ((cp ^ csp_psw<WD>(lo + r + toff)) << 4);   // pixel = lo + 16 k + r: its swizzle is known here
+      }
       auto finish = [&](int q, f32x4 acc) __attribute__((always_inline)) {
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) acc[jj] = csp_act(acc[jj], a.act);
         if (q < hi && cch < WD) {
-          char* po = out + q * a.PS + cch * 2;
+          char* po = out + pt_at(q, cch);
           if (second && a.shortcut) acc += lds_load4(po);       // x + cv2(cv1(x)): `out` still holds the bottleneck's input at this pixel
-          if (goff[q] == MGDT_OOB) acc = f32x4{0.f, 0.f, 0.f, 0.f};
+          int go = 0, ct = -1;
+          if (zchk || tocat) region_px(q, go, ct);
+          if (zchk && go == MGDT_OOB) acc = f32x4{0.f, 0.f, 0.f, 0.f};
           lds_store4(po, acc);
-          if (second) {
-            const int ct = ctab[q];
-            if (ct >= 0) lds_store4(catb + ct * a.CS + (slot0 + (j >> 1) * WD + cch) * 2, acc);
-          }
+          if (tocat && ct >= 0) lds_store4(catb + cat_at(ct, slot0 + (j >> 1) * WD + cch), acc);
         }
       };
       for (int grp = gv; grp < ng; grp += 2 * gst) {             // two pixel groups per step: two independent accumulator chains
         const int qa = lo + grp * 16 + r;
         const bool hasb = grp + gst < ng;                        // wave-uniform
         const int qb = hasb ? qa + gst * 16 : qa;
-        const char* pa = in + qa * a.PS;
-        const char* pb = in + qb * a.PS;
+        const char* pa = in + qa * PS;
+        const char* pb = in + qb * PS;
         f32x4 acca = bias, accb = bias;
 #pragma unroll
         for (int kc = 0; kc < NCH; ++kc) {
@@ -334,34 +349,59 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
   // ================================================================ back: 1x1 conv over the concat, store, per-tile channel sums
   {
     const int tg = (TP + 15) >> 4;
-    int coff[NCHB];
+    // K pieces [0, nsl) come from the concat buffer, [nsl, nsl + CP) (the last bottleneck's output) from P at the tile pixel's region
+    // index; a lane's pixel is t = 16 grp + r, so its concat swizzle (t >> csh) & cmsk = (r >> csh) & cmsk is fixed
+    const int nsl = a.catS >> 3, csw = (r >> a.csh) & a.cmsk;
+    int koff[NCHB];
+    bool kinp[NCHB];
 #pragma unroll
     for (int kc = 0; kc < NCHB; ++kc) {
       const int p = kc * 4 + g;
-      coff[kc] = p * 8 < a.catC ? p * 16 : 0;                   // padded piece: zero weights, finite data
+      kinp[kc] = p >= nsl && p < nsl + CP;
+      koff[kc] = kinp[kc] ? p - nsl : ((p < nsl ? p : 0) ^ csw) << 4;   // padded piece (p * 8 >= catC): zero weights, finite data
     }
     // few cout blocks (< 8): the waves that share a block split the tile's pixel groups; their partial sums go to separate pool slots
     const int gst = bgst, gv = bgv;
+    bf16x8 ABn[PREB ? 1 : NCHB];                                 // wide blocks: the next cout block's fragments land during this one's MFMAs
+    f32x4 biasBn = biasB;
+    if (!PREB && ob0 < a.nbo) {
+#pragma unroll
+      for (int kc = 0; kc < NCHB; ++kc)
+        if (kc < a.nchb) AB[kc] = *(const bf16x8*)(a.back + ((size_t)(kc * a.nbo + ob0) * 64 + lane) * 16);
+      biasB = *(const f32x4*)(a.back_bias + ob0 * 16 + 4 * g);
+    }
     for (int ob = ob0; ob < a.nbo; ob += obst) {
-      if (!PREB || ob != ob0) {
+      if (PREB && ob != ob0) {
 #pragma unroll
         for (int kc = 0; kc < NCHB; ++kc)
           if (kc < a.nchb) AB[kc] = *(const bf16x8*)(a.back + ((size_t)(kc * a.nbo + ob) * 64 + lane) * 16);
         biasB = *(const f32x4*)(a.back_bias + ob * 16 + 4 * g);
+      }
+      if (!PREB && ob + obst < a.nbo) {
+#pragma unroll
+        for (int kc = 0; kc < NCHB; ++kc)
+          if (kc < a.nchb) ABn[kc] = *(const bf16x8*)(a.back + ((size_t)(kc * a.nbo + ob + obst) * 64 + lane) * 16);
+        biasBn = *(const f32x4*)(a.back_bias + (ob + obst) * 16 + 4 * g);
       }
       const int co = ob * 16 + 4 * g;
       const int dead = co >= a.Cout ? MGDT_OOB : 0;
       f32x4 psum = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int grp = gv; grp < tg; grp += gst) {
         const int t = grp * 16 + r;
+        const int tc = min(t, TP - 1);                           // lanes past the tile: any in-tile pixel (their output is dropped)
+        const int cy = (int)fdiv((uint32_t)tc, a.fd_tw), cx = tc - cy * a.TW;
+        const int tq = (cy + a.halo) * a.RW + cx + a.halo;       // the pixel's index in the region (P)
+        const int yo = t < TP ? n * a.ysn + (ty0 + cy) * a.ysh + (tx0 + cx) * a.ysw : MGDT_OOB;
         const char* pc = catb + t * a.CS;
+        const char* pp = Pb + tq * PS;
+        const int psw = csp_psw<WD>(tq);
         f32x4 acc = biasB;
 #pragma unroll
         for (int kc = 0; kc < NCHB; ++kc)
-          if (kc < a.nchb) acc = mma(AB[kc], *(const bf16x8*)(pc + coff[kc]), acc);
+          if (kc < a.nchb) acc = mma(AB[kc], *(const bf16x8*)(kinp[kc] ? pp + ((koff[kc] ^ psw) << 4) : pc + koff[kc]), acc);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) acc[jj] = (float)(bf16)csp_act(acc[jj], a.act);
-        bstore4<bf16>(yrs, (uint32_t)(yoff[t] | dead) + (uint32_t)(co * 2), acc);
+        bstore4<bf16>(yrs, (uint32_t)(yo | dead) + (uint32_t)(co * 2), acc);
         if (t < TP) psum += acc;
       }
       if (a.pool) {
@@ -373,26 +413,40 @@ __global__ __launch_bounds__(CSP_THREADS, ((WD <= 16 || (WD == 32 && MODE == 1))
           *(f32x4*)(a.pool + (((size_t)n * tpi + trem) * gst + gv) * a.Cout + co) = psum;
         }
       }
+      if (!PREB && ob + obst < a.nbo) {
+#pragma unroll
+        for (int kc = 0; kc < NCHB; ++kc) AB[kc] = ABn[kc];
+        biasB = biasBn;
+      }
     }
   }
   stamp(6);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct CspGeom { int TH, TW, halo, RH, RW, RPA, TPA, PS, CS, tiles_x, tiles_y; size_t lds; };
+struct CspGeom { int TH, TW, halo, RH, RW, RPA, TPA, CS, tiles_x, tiles_y; size_t lds; };
+
+// concat buffer: catC - wd channels per pixel (the last bottleneck output is read from P), no padding; the 16-byte slot index is XORed
+// with (t >> csh) & cmsk, the form that leaves the back conv's ds_read_b128 lane groups conflict-free for the row's slot count
+static void csp_cat_swizzle(int slots, int* cmsk, int* csh) {
+  if (slots % 16 == 0) { *cmsk = 15; *csh = 0; }
+  else if (slots % 8 == 0) { *cmsk = 7; *csh = 0; }
+  else if (slots % 4 == 0) { *cmsk = 3; *csh = 1; }
+  else { *cmsk = 0; *csh = 0; }                                           // odd (or 2 mod 4) slot counts: within 25 % of conflict-free unswizzled
+}
 
 static bool csp_geometry(int mode, int H, int W, int wd, int nbtl, int catC, size_t extra, int th, int tw, CspGeom* g) {
   g->TH = th; g->TW = tw; g->halo = 2 * nbtl;
   g->RH = th + 2 * g->halo; g->RW = tw + 2 * g->halo;
   const int RP = g->RH * g->RW;
-  g->RPA = ((RP + 15) / 16) * 16 + ((g->RW + 1 + 15) / 16) * 16 + 16;      // whole groups + the reach of the last group's taps
+  // the last pixel group of a 3x3 conv ends < hi + 15 and its taps reach RW + 1 further; hi <= RP - RW - 1: reads stay below RP + 15
+  g->RPA = ((RP + 15 + 15) / 16) * 16;
   g->TPA = ((th * tw + 15) / 16) * 16;
-  g->PS = wd == 8 ? 16 : wd * 2 + 16;
-  g->CS = catC * 2 + 16;
+  g->CS = (catC - wd) * 2;
   g->tiles_x = W / tw; g->tiles_y = H / th;
-  g->lds = (size_t)g->RPA * 4 + (size_t)g->TPA * 4 + (size_t)g->RPA * 2 + 32 + 2 * (size_t)g->RPA * g->PS + (size_t)g->TPA * g->CS + extra;
+  g->lds = 2 * (size_t)g->RPA * (wd * 2) + (size_t)g->TPA * g->CS + extra;
   (void)mode;
-  return g->lds <= 156 * 1024 && RP < 32000;
+  return g->lds <= 156 * 1024;
 }
 
 static int csp_chain_nbk(int wd) { return wd >= 16 ? wd / 16 : 1; }
@@ -410,6 +464,12 @@ extern "C" int mgdt_csp_block_supported(int mode, int cin, int cout, int wd, int
   }
   return 1;
 }
+
+// residency: wd <= 32 builds fit two workgroups per CU in registers (<= 128 VGPRs); then a tile whose LDS keeps it at one workgroup per
+// CU pays CSP_1WG_COST (nothing overlaps its barriers and table / front latency; with batches in flight it also locks other kernels out
+// of the CU).  wd = 64 needs > 128 VGPRs: one workgroup per CU whatever its LDS.
+constexpr size_t CSP_LDS_2WG = 80 * 1024;
+constexpr double CSP_1WG_COST = 2.0;
 
 static bool csp_pick_tile(int mode, int H, int W, int N, int wd, int nbtl, int catC, size_t extra, CspGeom* best) {
   const char* e = getenv("MGDT_CSP_TILE");       // experiment knob "th,tw" (not part of the ABI)
@@ -430,7 +490,7 @@ static bool csp_pick_tile(int mode, int H, int W, int N, int wd, int nbtl, int c
       const double fill = (double)(th * tw) / g.TPA;              // lanes of the tile's last pixel group that do work
       double cost = ratio / fill;
       if (wgs < 256) cost *= 256.0 / wgs;                        // fewer workgroups than CUs: the chip is not filled (measured: 128 big tiles beat 512 small ones at 20x20)
-      if (g.lds > 76 * 1024) cost *= 1.3;                        // one workgroup per CU: nothing overlaps its barriers
+      if (wd <= 32 && g.lds > CSP_LDS_2WG) cost *= CSP_1WG_COST;
       if (cost < best_cost) { best_cost = cost; *best = g; found = true; }
     }
   }
@@ -491,7 +551,9 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
   CspGeom g;
   if (!csp_pick_tile(mode, a.H, a.W, a.N, wd, nbtl, a.catC, extra, &g)) MGDT_FAIL(MGDT_BAD_SHAPE, "csp_block: no tile fits %dx%d wd=%d n=%d", a.H, a.W, wd, nbtl);
   a.TH = g.TH; a.TW = g.TW; a.halo = g.halo; a.RH = g.RH; a.RW = g.RW; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
-  a.RPA = g.RPA; a.TPA = g.TPA; a.PS = g.PS; a.CS = g.CS;
+  a.RPA = g.RPA; a.TPA = g.TPA; a.CS = g.CS;
+  a.catS = a.catC - wd;
+  csp_cat_swizzle(a.catS / 8, &a.cmsk, &a.csh);
   a.total_tiles = a.N * g.tiles_x * g.tiles_y;
   a.fd_rw = make_fastdiv((uint32_t)g.RW); a.fd_tw = make_fastdiv((uint32_t)g.TW); a.fd_tx = make_fastdiv((uint32_t)g.tiles_x);
   a.fd_tpi = make_fastdiv((uint32_t)(g.tiles_x * g.tiles_y));
