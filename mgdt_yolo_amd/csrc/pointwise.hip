@@ -728,6 +728,10 @@ extern "C" int mgdt_scale_channels_fwd(const mgdt_view* x, const float* attn, co
 }
 
 // ------------------------------------------------------------------------------------------------ SPPF pools
+// The max of a pooling window is NaN when the window holds a NaN, as in ATen's max_pool2d and in maxpool5_bwd (train_vec.hip): fmaxf would
+// drop it.  IEEE-754 maximum (v_maximum3_f32 on gfx950) propagates it and stays exact and associative, so both forms below give the same bits.
+__device__ __forceinline__ float pool_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 // One workgroup = one image x 8 channels: the whole HxW plane (20x20 at 640^2) sits in LDS as fp32 with a 2-pixel -inf halo and MaxPool2d(5,1,2)
 // is applied three times as separable row / column 5-tap max passes, writing y1, y2, y3 after each.  The halo makes the taps unconditional: with
 // bounds tests around the LDS reads every read waited for the previous compare (32 us for a 3 MB map).
@@ -756,14 +760,14 @@ __global__ __launch_bounds__(256) void sppf_pool_kernel(const T* __restrict__ x,
       const int c = i % SPPF_CG, p = i / SPPF_CG, h = p / W, w = p - h * W;
       const int o = ((h + 2) * WP + w + 2) * SPPF_CG + c;
       const float a0 = A[o - 2 * SPPF_CG], a1 = A[o - SPPF_CG], a2 = A[o], a3 = A[o + SPPF_CG], a4 = A[o + 2 * SPPF_CG];
-      Bf[o] = fmaxf(fmaxf(fmaxf(a0, a1), fmaxf(a2, a3)), a4);
+      Bf[o] = pool_max(pool_max(pool_max(a0, a1), pool_max(a2, a3)), a4);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < HW * SPPF_CG; i += 256) {   // columns: Bf -> A
       const int c = i % SPPF_CG, p = i / SPPF_CG, h = p / W, w = p - h * W;
       const int o = ((h + 2) * WP + w + 2) * SPPF_CG + c, rs = WP * SPPF_CG;
       const float b0 = Bf[o - 2 * rs], b1 = Bf[o - rs], b2 = Bf[o], b3 = Bf[o + rs], b4 = Bf[o + 2 * rs];
-      A[o] = fmaxf(fmaxf(fmaxf(b0, b1), fmaxf(b2, b3)), b4);
+      A[o] = pool_max(pool_max(pool_max(b0, b1), pool_max(b2, b3)), b4);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < HW * QN; i += 256) {
@@ -812,9 +816,9 @@ __global__ __launch_bounds__(256) void sppf_pool3_kernel(const T* __restrict__ x
     float m5[V], m9[V], m13[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      m5[k] = fmaxf(fmaxf(fmaxf(t[4][k], t[5][k]), fmaxf(t[6][k], t[7][k])), t[8][k]);
-      m9[k] = fmaxf(fmaxf(m5[k], fmaxf(t[2][k], t[3][k])), fmaxf(t[9][k], t[10][k]));
-      m13[k] = fmaxf(fmaxf(m9[k], fmaxf(t[0][k], t[1][k])), fmaxf(t[11][k], t[12][k]));
+      m5[k] = pool_max(pool_max(pool_max(t[4][k], t[5][k]), pool_max(t[6][k], t[7][k])), t[8][k]);
+      m9[k] = pool_max(pool_max(m5[k], pool_max(t[2][k], t[3][k])), pool_max(t[9][k], t[10][k]));
+      m13[k] = pool_max(pool_max(m9[k], pool_max(t[0][k], t[1][k])), pool_max(t[11][k], t[12][k]));
     }
     stv<T, V>(R + ((size_t)(0 * HP + h + 6) * W + w) * V, m5);
     stv<T, V>(R + ((size_t)(1 * HP + h + 6) * W + w) * V, m9);
@@ -831,7 +835,7 @@ __global__ __launch_bounds__(256) void sppf_pool3_kernel(const T* __restrict__ x
     for (int j = 4; j <= 8; ++j) {
       ldv<T, V>(R + ((size_t)(0 * HP + h + j) * W + w) * V, t);
 #pragma unroll
-      for (int k = 0; k < V; ++k) o[k] = fmaxf(o[k], t[k]);
+      for (int k = 0; k < V; ++k) o[k] = pool_max(o[k], t[k]);
     }
     stv<T, V>(y1 + n * s1n + h * s1h + w * s1w + c0, o);
 #pragma unroll
@@ -840,7 +844,7 @@ __global__ __launch_bounds__(256) void sppf_pool3_kernel(const T* __restrict__ x
     for (int j = 2; j <= 10; ++j) {
       ldv<T, V>(R + ((size_t)(1 * HP + h + j) * W + w) * V, t);
 #pragma unroll
-      for (int k = 0; k < V; ++k) o[k] = fmaxf(o[k], t[k]);
+      for (int k = 0; k < V; ++k) o[k] = pool_max(o[k], t[k]);
     }
     stv<T, V>(y2 + n * s2n + h * s2h + w * s2w + c0, o);
 #pragma unroll
@@ -849,7 +853,7 @@ __global__ __launch_bounds__(256) void sppf_pool3_kernel(const T* __restrict__ x
     for (int j = 0; j <= 12; ++j) {
       ldv<T, V>(R + ((size_t)(2 * HP + h + j) * W + w) * V, t);
 #pragma unroll
-      for (int k = 0; k < V; ++k) o[k] = fmaxf(o[k], t[k]);
+      for (int k = 0; k < V; ++k) o[k] = pool_max(o[k], t[k]);
     }
     stv<T, V>(y3 + n * s3n + h * s3h + w * s3w + c0, o);
   }
