@@ -130,6 +130,10 @@ size_t mgdt_stem2_packed_bytes(void);
 int mgdt_stem2_pack(const float* w_folded, void* packed, mgdt_stream s);
 int mgdt_stem2_fwd(const mgdt_view* x, int x_dtype, const void* packed0, const float* bias0, const void* packed1, const float* bias1,
                    const mgdt_view* y, mgdt_stream s);
+/* Debug: the launch geometry of mgdt_stem2_fwd for an n x 3 x h x w image on a device with cu_count compute units (<= 0: the current device's).
+ * The kernel is persistent: out[0] = tiles (8 x 16 output pixels each), out[1] = workgroups launched (<= tiles, <= out[3] * out[4]; the experiment
+ * knob MGDT_STEM_WGS=<n> in the environment caps it), out[2] = LDS bytes per workgroup, out[3] = workgroups per compute unit, out[4] = compute units. */
+int mgdt_stem2_geometry(int n, int h, int w, int cu_count, int* out);
 
 /* ---- Detect head tail in one launch, bf16 (nn/modules/head.py:150-177): the two final 1x1 convs with bias (box c2 -> 16, cls c3 -> nc), the raw
  * (N, 16+nc, H, W) map and its decode (DFL expectation, dist2bbox, stride, sigmoid) into y[N][4+nc][a_total] at anchor offset a_off.

@@ -77,6 +77,7 @@ PROTOTYPES = {
     'mgdt_stem2_packed_bytes': (_sz, []),
     'mgdt_stem2_pack': (_i, [_vp, _vp, _vp]),
     'mgdt_stem2_fwd': (_i, [VP, _i, _vp, _vp, _vp, _vp, VP, _vp]),
+    'mgdt_stem2_geometry': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     'mgdt_detect_tail_supported': (_i, [_i, _i, _i, _i, _i]),
     'mgdt_detect_tail_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _i, _f, _i, _i, VP, _vp, _vp, _vp, _vp, _vp]),
     'mgdt_detect_tail_aug_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _i, _f, _i, _i, VP, _vp, _vp, _vp, _vp, _f, _i, _f, _vp]),
