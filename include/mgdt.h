@@ -313,6 +313,39 @@ int mgdt_nms_fwd(const float* pred, int n, int nc, int a, float conf_thres, floa
                  int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, float* out,
                  int32_t* kept_anchor, int32_t* counts, const unsigned long long* best_keys, void* ws, size_t ws_bytes, mgdt_stream s);
 
+/* The same selection on a prediction that carries nm mask-coefficient rows behind the class rows (yolo/utils/ops.py:136-266 with nm > 0):
+ * pred fp32 [n][4+nc+nm][a]; candidates, ordering and suppression read rows 0 .. 4+nc only (the code of mgdt_nms_fwd with another image stride);
+ * out[n][max_det][6+nm]: columns 6.. are the kept anchor's coefficients, copied.  nm = 0 is mgdt_nms_fwd. */
+int mgdt_nms_masks_fwd(const float* pred, int n, int nc, int nm, int a, float conf_thres, float iou_thres, const int32_t* classes,
+                       int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, float* out,
+                       int32_t* kept_anchor, int32_t* counts, const unsigned long long* best_keys, void* ws, size_t ws_bytes, mgdt_stream s);
+
+/* ---- instance segmentation inference (nn/modules/head.py:189-212 Segment, nn/modules/block.py:57-69 Proto, yolo/utils/ops.py:541-636) -----------
+ * deconv2x2: nn.ConvTranspose2d(cin, cout, 2, 2, 0) + bias (Proto.upsample; kernel == stride, so y[2i+dy][2j+dx] = W[:, :, dy, dx]^T x[i][j] + b):
+ *   packed4[2*dy + dx] = mgdt_conv_pack of the (cout, cin, 1, 1) matrix W[:, :, dy, dx]^T, bias = any of the four packs' bias_out (the conv bias);
+ *   four launches of the MFMA kernel of mgdt_conv2d_fwd, each writing one stride-2 phase of y (N x 2H x 2W x cout NHWC).  Other geometries are
+ *   not built.
+ * seg_concat: y fp32 [n][rows][a] (rows = 4 + nc, as Detect writes it) + the per-level cv4 maps mc[l] (n x h_l x w_l x nm NHWC, `dtype`) ->
+ *   out fp32 [n][rows+nm][a]: rows 0..rows copied, row rows+k of anchor a_off_l + pixel = mc[l][pixel][k] (head.py:208,212).
+ * seg_masks: crop_mask / process_mask / process_mask_upsample / process_mask_native for a whole batch in one launch.  protos: n x mh x mw x nm
+ *   NHWC (nm = 32), rows [n][max_det][6+nm] + counts[n] as mgdt_nms_masks_fwd writes them, offsets[n] = exclusive scan of counts (device);
+ *   out [sum(counts)][out_h][out_w] of 0 / 1, uint8 (out_u8) or fp32, every element written, nothing past it.
+ *     masks = sigmoid(rows[:, 6:] @ protos[top:top+win_h, left:left+win_w])          (MFMA; bf16: coefficients rounded to bf16, fp32 accumulation)
+ *     crop_before: zero where the proto pixel (x, y) fails x >= x1*box_sx, x < x2*box_sx, y >= y1*box_sy, y < y2*box_sy     (fp32, ops.py:541-557)
+ *     bilinear resample of the window to out_h x out_w (align_corners=False, PyTorch's CPU arithmetic; identity when the sizes agree)
+ *     crop_after: zero where the output pixel fails the same test on the unscaled box;  then > 0.5.
+ *   process_mask(upsample=False): window = whole map, out = mh x mw, crop_before with (mw/iw, mh/ih);  (upsample=True): the same with out = ih x iw;
+ *   process_mask_upsample: out = ih x iw, crop_after;  process_mask_native: window from the letter-box gain / pad (ops.py:628-632), crop_after.
+ *   no_skip: compute every (detection, tile) pair even when its crop box misses the tile (tests: the skip changes no byte).
+ *   mgdt_seg_mask_geometry: geom4 = {tile_h, tile_w, tiles_y, tiles_x} of that launch; 0 when the resampling ratio is not covered. */
+int mgdt_deconv2x2_fwd(const mgdt_view* x, const void* const* packed4, const float* bias, const mgdt_view* y, int dtype, mgdt_stream s);
+int mgdt_seg_concat_fwd(const float* y, int n, int rows, int a_total, const mgdt_view* const* mc, int n_levels, int nm, float* out, int dtype,
+                        mgdt_stream s);
+int mgdt_seg_mask_geometry(int win_h, int win_w, int out_h, int out_w, int* geom4);
+int mgdt_seg_masks_fwd(const mgdt_view* protos, const float* rows, const int32_t* counts, const int32_t* offsets, int max_det, int nm,
+                       int top, int left, int win_h, int win_w, int out_h, int out_w, int crop_before, float box_sx, float box_sy,
+                       int crop_after, int no_skip, void* out, int out_u8, int dtype, mgdt_stream s);
+
 /* ---- validator matching: DetectionValidator._process_batch, yolo/v8/detect/val.py:152-175, for a batch ----------
  * det [n][max_det][6] (x1,y1,x2,y2,conf,cls; the layout mgdt_nms_fwd writes) with ndet[n] valid rows, labels [n][max_lab][5]
  * (cls,x1,y1,x2,y2 in the same pixel frame) with nlab[n] valid rows, iouv[n_iou] ascending IoU levels (n_iou <= 16).

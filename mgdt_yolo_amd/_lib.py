@@ -149,6 +149,11 @@ PROTOTYPES = {
     'mgdt_ap_per_class': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'mgdt_nms_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mgdt_nms_fwd': (_i, [_vp, _i, _i, _i, _f, _f, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'mgdt_nms_masks_fwd': (_i, [_vp, _i, _i, _i, _i, _f, _f, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'mgdt_deconv2x2_fwd': (_i, [VP, _vp, _vp, VP, _i, _vp]),
+    'mgdt_seg_concat_fwd': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
+    'mgdt_seg_mask_geometry': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    'mgdt_seg_masks_fwd': (_i, [VP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _i, _vp]),
 }
 
 _lib = None

@@ -28,6 +28,7 @@ struct NmsArgs {
   int dbg;
   const float* pred;
   int n, nc, A;
+  int rows, nm;     // rows of one image's prediction (4 + nc + nm) and the mask coefficients carried to the output rows (mgdt_nms_masks_fwd; nm = 0: rows = 4 + nc)
   float conf, iou;
   const int32_t* classes;
   int n_classes, agnostic, multi_label, max_det, max_nms;
@@ -58,7 +59,7 @@ __device__ __forceinline__ bool class_ok(int c, const int32_t* classes, int n_cl
 __global__ __launch_bounds__(256) void nms_best_kernel(const NmsArgs a) {
   const int img = blockIdx.y, an = blockIdx.x * 256 + threadIdx.x;
   if (an >= a.A) return;
-  const float* P = a.pred + (long)img * (4 + a.nc) * a.A + (long)4 * a.A + an;
+  const float* P = a.pred + (long)img * a.rows * a.A + (long)4 * a.A + an;
   float best = P[0];
   int bc = 0;
   int c = 1;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void nms_best_kernel(const NmsArgs a) {
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int img = blockIdx.x, tid = threadIdx.x;
-  const float* P = a.pred + (long)img * (4 + a.nc) * a.A;
+  const float* P = a.pred + (long)img * a.rows * a.A;
   u64* gbuf = a.ws + (long)img * a.ws_per_image;
   u64* akeys = gbuf + a.cap_pow2;              // only used when !multi_label
   __shared__ unsigned hist[256];
@@ -530,16 +531,17 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs a) {
     seg *= 4;
   }
   __syncthreads();
-  // output rows (x1,y1,x2,y2,conf,cls) + anchor index of the kept boxes, one thread per row
+  // output rows (x1,y1,x2,y2,conf,cls [, the kept anchor's nm mask coefficients]) + anchor index of the kept boxes, one thread per row
   for (int t = tid; t < s_nkept; t += NMS_THREADS) {
     const u64 key = kkey[t];
     const unsigned cand = (unsigned)(key & 0xFFFFFFFFu);
     const int an = (int)(cand / (unsigned)a.nc), cls = (int)(cand % (unsigned)a.nc);
     const float cx = P[an], cy = P[(long)a.A + an], w = P[2L * a.A + an], h = P[3L * a.A + an];
-    float* o = a.out + ((long)img * md + t) * 6;
+    float* o = a.out + ((long)img * md + t) * (6 + a.nm);
     o[0] = cx - w / 2.f; o[1] = cy - h / 2.f; o[2] = cx + w / 2.f; o[3] = cy + h / 2.f;
     o[4] = __uint_as_float(0xFFFFFFFFu - (unsigned)(key >> 32));
     o[5] = (float)cls;
+    for (int k = 0; k < a.nm; ++k) o[6 + k] = P[(long)(4 + a.nc + k) * a.A + an];      // ops.py:219,227: the mask columns ride along
     a.kept_anchor[(long)img * md + t] = an;
   }
   if (tid == 0) a.counts[img] = s_nkept;
@@ -558,9 +560,9 @@ extern "C" size_t mgdt_nms_workspace_bytes(int n, int nc, int a, int multi_label
   return (size_t)n * (cap + (multi_label ? 0 : a)) * sizeof(u64);
 }
 
-extern "C" int mgdt_nms_fwd(const float* pred, int n, int nc, int a, float conf_thres, float iou_thres, const int32_t* classes,
-                            int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, float* out,
-                            int32_t* kept_anchor, int32_t* counts, const unsigned long long* best_keys, void* ws, size_t ws_bytes, mgdt_stream s) {
+static int nms_run(const float* pred, int n, int nc, int nm, int a, float conf_thres, float iou_thres, const int32_t* classes,
+                   int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, float* out,
+                   int32_t* kept_anchor, int32_t* counts, const unsigned long long* best_keys, void* ws, size_t ws_bytes, mgdt_stream s) {
   if (!pred || !out || !kept_anchor || !counts || !ws) MGDT_FAIL(MGDT_BAD_ARG, "nms: null pointer");
   if (!(conf_thres >= 0.f && conf_thres <= 1.f)) MGDT_FAIL(MGDT_BAD_ARG, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
   if (!(iou_thres >= 0.f && iou_thres <= 1.f)) MGDT_FAIL(MGDT_BAD_ARG, "Invalid IoU %g, valid values are between 0.0 and 1.0", iou_thres);
@@ -571,7 +573,7 @@ extern "C" int mgdt_nms_fwd(const float* pred, int n, int nc, int a, float conf_
   if (lds > 150 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "nms: max_det=%d too large for the LDS kept list", max_det);
   NmsArgs g;
   g.dbg = getenv("MGDT_NMS_DBG") != nullptr;
-  g.pred = pred; g.n = n; g.nc = nc; g.A = a; g.conf = conf_thres; g.iou = iou_thres; g.classes = n_classes > 0 ? classes : nullptr;
+  g.pred = pred; g.n = n; g.nc = nc; g.A = a; g.rows = 4 + nc + nm; g.nm = nm; g.conf = conf_thres; g.iou = iou_thres; g.classes = n_classes > 0 ? classes : nullptr;
   g.n_classes = n_classes; g.agnostic = agnostic; g.multi_label = multi_label; g.max_det = max_det; g.max_nms = max_nms;
   g.max_wh = max_wh; g.out = out; g.kept_anchor = kept_anchor; g.counts = counts; g.ws = (u64*)ws;
   g.best = multi_label ? nullptr : (const u64*)best_keys;
@@ -588,6 +590,21 @@ extern "C" int mgdt_nms_fwd(const float* pred, int n, int nc, int a, float conf_
   nms_kernel<<<n, NMS_THREADS, lds, (hipStream_t)s>>>(g);
   MGDT_CHECK_LAUNCH("nms_fwd");
   return MGDT_OK;
+}
+
+extern "C" int mgdt_nms_fwd(const float* pred, int n, int nc, int a, float conf_thres, float iou_thres, const int32_t* classes,
+                            int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, float* out,
+                            int32_t* kept_anchor, int32_t* counts, const unsigned long long* best_keys, void* ws, size_t ws_bytes, mgdt_stream s) {
+  return nms_run(pred, n, nc, 0, a, conf_thres, iou_thres, classes, n_classes, agnostic, multi_label, max_det, max_nms, max_wh, out, kept_anchor, counts,
+                 best_keys, ws, ws_bytes, s);
+}
+
+extern "C" int mgdt_nms_masks_fwd(const float* pred, int n, int nc, int nm, int a, float conf_thres, float iou_thres, const int32_t* classes,
+                                  int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, float* out,
+                                  int32_t* kept_anchor, int32_t* counts, const unsigned long long* best_keys, void* ws, size_t ws_bytes, mgdt_stream s) {
+  if (nm < 0 || nm > 256) MGDT_FAIL(MGDT_BAD_SHAPE, "nms_masks: nm=%d", nm);
+  return nms_run(pred, n, nc, nm, a, conf_thres, iou_thres, classes, n_classes, agnostic, multi_label, max_det, max_nms, max_wh, out, kept_anchor, counts,
+                 best_keys, ws, ws_bytes, s);
 }
 
 // ================================================================================================ validator matching

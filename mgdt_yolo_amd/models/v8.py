@@ -63,9 +63,27 @@ CONFIGS = {
 }
 
 
+def _seg(head):
+    """`head` with its Detect row replaced by Segment [nc, 32, 256] (models/v8/yolov8-seg.yaml:46)."""
+    def build():
+        rows = head()
+        rows[-1] = [rows[-1][0], 1, 'Segment', ['nc', 32, 256]]
+        return rows
+    return build
+
+
+# instance-segmentation graphs: `yolov8-seg` is the reference's models/v8/yolov8-seg.yaml; `mspa_c2f_gd_yolov8-seg` is this fork's MSPA-GD graph
+# with the same head swap (the reference ships no file for it).  Kept apart from CONFIGS, which lists the detection graphs only.
+SEG_CONFIGS = {
+    'yolov8-seg': lambda nc=80: _cfg('C2f', _seg(_pan_head), nc),
+    'mspa_c2f_gd_yolov8-seg': lambda nc=80: _cfg('MSPA_C2f', _seg(_gd_head), nc),
+}
+
+
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
-    d = CONFIGS[name]() if nc is None else CONFIGS[name](nc)      # nc=None: the YAML file's own class count
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    table = CONFIGS if name in CONFIGS else SEG_CONFIGS
+    d = table[name]() if nc is None else table[name](nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale
     d['yaml_file'] = f'{name}.yaml'
     return d

@@ -13,7 +13,7 @@ from .convnextv2 import ConvNeXtV2_Block
 from .spr_module import SPRModule
 
 __all__ = ('DFL', 'SPPF', 'C2f', 'MSPA_C2f', 'Bottleneck', 'SimFusion_4in', 'SimFusion_3in', 'IFM', 'h_sigmoid',
-           'InjectionMultiSum_Auto_pool', 'Upsample')
+           'InjectionMultiSum_Auto_pool', 'Upsample', 'Proto')
 
 
 def _plain_block(first, last, bottlenecks):
@@ -272,6 +272,33 @@ class SPPF(HipModule):
         g1 = ops.add(sl(gcat, 1), ops.maxpool5_bwd(sl(cat, 1), g2))
         g0 = ops.add(sl(gcat, 0), ops.maxpool5_bwd(sl(cat, 0), g1))
         return self.cv1.backward(g0)
+
+
+class Proto(HipModule):
+    """YOLOv8 mask Proto module (reference block.py:57-69): cv1 (3x3) -> 2x2 stride-2 transposed conv + bias -> cv2 (3x3) -> cv3 (1x1) = the nm
+    prototype maps at twice the input's resolution.  `upsample` is an nn.ConvTranspose2d parameter container (checkpoints interchange); its
+    compute is ops.deconv2x2."""
+
+    def __init__(self, c1, c_=256, c2=32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def run_upsample(self, x):
+        up = self.upsample
+        ops.check_deconv2x2(up.kernel_size, up.stride, up.padding, up.groups, up.output_padding, up.dilation)
+        if up.bias is None:
+            raise RuntimeError('Proto.upsample is built with its bias (block.py:63)')
+        dt = self.out_dtype(x)
+        pk = self._cached(('deconv', dt), [up.weight, up.bias], lambda: ops.PackedDeconv2x2(up.weight, up.bias, dt))
+        return ops.deconv2x2(x, pk)
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError('segmentation training is not built (the reference\'s v8SegmentationLoss cannot run in this fork): Proto runs in eval()')
+        return self.cv3(self.cv2(self.run_upsample(self.cv1(x))))
 
 
 class Upsample(nn.Module):

@@ -11,10 +11,10 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from .block import DFL
+from .block import DFL, Proto
 from .conv import Conv, HipModule
 
-__all__ = ('Detect', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
+__all__ = ('Detect', 'Segment', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
 
 
 class _HeadConv(HipModule):
@@ -198,6 +198,54 @@ class Detect(HipModule):
         for a, b, s in zip(self.cv2, self.cv3, self.stride):
             a[-1].bias.data[:] = 1.0
             b[-1].bias.data[:self.nc] = math.log(5 / self.nc / (640 / s) ** 2)
+
+
+SEG_TRAIN_MSG = ('segmentation training is not built: the reference\'s v8SegmentationLoss cannot run in this fork, so there is nothing to pin a '
+                 'training path to; Segment / SegmentationModel are inference modules (call .eval())')
+
+
+class Segment(Detect):
+    """YOLOv8 Segment head (reference head.py:189-212): Detect plus, per level, a mask-coefficient branch cv4 (3x3, 3x3, 1x1 + bias -> nm) and the
+    Proto module on the first level.  Eval returns (cat(y, mc) (B, 4+nc+nm, A) fp32, (feats, mc (B, nm, A) fp32, p (B, nm, mh, mw) NHWC));
+    export=True returns (cat, p).  Detect.forward runs unchanged; one launch (mgdt_seg_concat_fwd) then writes the wide prediction from its y and
+    the NHWC cv4 maps, and the best-class NMS keys are carried over to it.  All convolutions of this head stay bf16 under quantize_fp8."""
+
+    def __init__(self, nc=80, nm=32, npr=256, ch=()):
+        super().__init__(nc, ch)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+
+    def q8_site(self, key, x, x2=None):
+        return None                                           # fp8 for the Segment head is not built: its merged first convolutions stay bf16
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError(SEG_TRAIN_MSG)
+        p = self.proto(x[0])
+        mcs = []
+        for i in range(self.nl):
+            t = self.cv4[i][1](self.cv4[i][0](x[i]))
+            b, _, h, w = t.shape
+            m = ops.new_act(b, self.nm, h, w, t.dtype, t.device)
+            _HeadConv.run(self, self.cv4[i][2], t, m)
+            mcs.append(m)
+        export, self.export = self.export, False             # Detect.forward's own export form drops the feature maps
+        try:
+            y, feats = Detect.forward(self, x)
+        finally:
+            self.export = export
+        cat = ops.seg_concat(y, mcs)
+        best = ops._best_keys_of(y, y.shape[0], y.shape[2])
+        if best is not None:
+            ops.attach_best_keys(cat, best)
+        mc = cat[:, 4 + self.nc:]
+        return (cat, p) if self.export else (cat, (feats, mc, p))
+
+    def backward(self, grads):
+        raise NotImplementedError(SEG_TRAIN_MSG)
 
 
 # ====================================================================================================================

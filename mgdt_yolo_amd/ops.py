@@ -862,6 +862,197 @@ def nms(pred, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, ma
     return out, kept, counts
 
 
+def nms_masks(pred, nm, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, max_nms, max_wh):
+    """pred (B, 4+nc+nm, A) fp32 cuda contiguous -> (out [B,max_det,6+nm], kept_anchor [B,max_det] int32, counts [B] int32): mgdt_nms_masks_fwd,
+    the selection of `nms` on rows 0 .. 4+nc with the kept anchors' nm mask coefficients behind the six detection columns."""
+    _need_gpu(pred)
+    if pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise RuntimeError('nms: prediction must be a contiguous float32 tensor')
+    b, ch, a = pred.shape
+    nc = ch - 4 - nm
+    if nm < 1 or nc < 1:
+        raise RuntimeError(f'nms_masks: {ch} prediction rows cannot hold 4 box rows, classes and nm={nm} mask coefficients')
+    lib = L.lib()
+    ml = 1 if (multi_label and nc > 1) else 0
+    ws_bytes = lib.mgdt_nms_workspace_bytes(b, nc, a, ml, max_nms)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=pred.device)
+    out = torch.empty(b, max_det, 6 + nm, dtype=torch.float32, device=pred.device)
+    kept = torch.empty(b, max_det, dtype=torch.int32, device=pred.device)
+    counts = torch.empty(b, dtype=torch.int32, device=pred.device)
+    cls_t = None
+    if classes is not None:
+        cls_t = torch.as_tensor(list(classes), dtype=torch.int32).to(pred.device)
+    best = None if ml else _best_keys_of(pred, b, a)
+    if _PROF is not None:
+        _META['nms_masks_fwd'] = dict(shape=(b, nc, nm, a, max_det), flops=0.0, bytes=float(b * (4 + nc) * a * 4))
+    _launch('nms_masks_fwd', 'mgdt_nms_masks_fwd', ptr(pred), b, nc, nm, a, float(conf_thres), float(iou_thres), ptr(cls_t),
+            0 if cls_t is None else cls_t.numel(), int(bool(agnostic)), ml, max_det, max_nms, float(max_wh), ptr(out), ptr(kept), ptr(counts), ptr(best),
+            ptr(ws), ws_bytes, stream())
+    return out, kept, counts
+
+
+# ------------------------------------------------------------------ instance segmentation (Segment head, Proto, masks)
+class PackedDeconv2x2:
+    """The four 1x1 panels of one nn.ConvTranspose2d(cin, cout, 2, 2, 0) (weight (cin, cout, 2, 2)): panel 2*dy + dx = W[:, :, dy, dx]^T."""
+    __slots__ = ('panels', 'ptrs', 'bias', 'cin', 'cout', 'dtype', '__weakref__')
+
+    def __init__(self, weight, bias, dtype):
+        check_deconv2x2(weight.shape[2:], (2, 2), (0, 0), 1)
+        w = weight.detach().float()
+        self.cin, self.cout, self.dtype = w.shape[0], w.shape[1], dtype
+        self.panels = [PackedConv(w[:, :, dy, dx].t().reshape(self.cout, self.cin, 1, 1), bias, None, 1, dtype) for dy in (0, 1) for dx in (0, 1)]
+        self.ptrs = (C.c_void_p * 4)(*[p.w.data_ptr() for p in self.panels])
+        self.bias = self.panels[0].bias
+
+
+def check_deconv2x2(kernel_size, stride, padding, groups, output_padding=(0, 0), dilation=(1, 1)):
+    """Only the geometry of Proto.upsample is built (kernel 2, stride 2, padding 0, one group): anything else raises before a launch."""
+    if (tuple(kernel_size) != (2, 2) or tuple(stride) != (2, 2) or tuple(padding) != (0, 0) or groups != 1 or tuple(output_padding) != (0, 0)
+            or tuple(dilation) != (1, 1)):
+        raise RuntimeError(f'transposed convolution: only kernel 2, stride 2, padding 0, groups 1 is built (Proto.upsample), got kernel {tuple(kernel_size)} '
+                           f'stride {tuple(stride)} padding {tuple(padding)} groups {groups}')
+
+
+def deconv2x2(x, pk, out=None):
+    """mgdt_deconv2x2_fwd: x (B, cin, H, W) NHWC -> (B, cout, 2H, 2W) NHWC = conv_transpose2d(x, W, b, stride 2)."""
+    _need_gpu(x)
+    b, c, h, w = x.shape
+    if c != pk.cin or x.dtype != pk.dtype:
+        raise RuntimeError(f'deconv2x2: panels are packed for {pk.cin} channels of {pk.dtype}, the input has {c} of {x.dtype}')
+    if not conv_can_mfma(x, pk.cin, pk.cout, 1, 1, 1, pk.dtype):
+        raise RuntimeError(f'deconv2x2: needs an NHWC input with cin % {8 if pk.dtype == torch.bfloat16 else 4} == 0 and cout % 4 == 0 (cin {pk.cin}, cout {pk.cout})')
+    if out is None:
+        out = new_act(b, pk.cout, 2 * h, 2 * w, pk.dtype, x.device)
+    _same(x, out)
+    if _PROF is not None:
+        es = x.element_size()
+        _META['deconv2x2_fwd'] = dict(shape=(b, pk.cin, h, w, pk.cout, 2, 2), flops=2.0 * b * h * w * 4 * pk.cout * pk.cin,
+                                      bytes=float(b * h * w * (pk.cin + 4 * pk.cout) * es + 4 * pk.cin * pk.cout * es))
+    _launch('deconv2x2_fwd', 'mgdt_deconv2x2_fwd', vp(x), pk.ptrs, ptr(pk.bias), vp(out), dtype_code(pk.dtype), stream())
+    return out
+
+
+def seg_concat(y, mcs):
+    """mgdt_seg_concat_fwd: y (B, 4+nc, A) fp32 + per-level cv4 maps (B, nm, h, w) NHWC -> (B, 4+nc+nm, A) fp32 (torch.cat([y, mc], 1) of
+    head.py:212 with mc = cat of the levels' .view(bs, nm, -1))."""
+    _need_gpu(y)
+    b, rows, a = y.shape
+    nm = mcs[0].shape[1]
+    _same(*mcs)
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise RuntimeError('seg_concat: the prediction must be a contiguous float32 tensor')
+    out = torch.empty(b, rows + nm, a, dtype=torch.float32, device=y.device)
+    arr, keep = _view_array(mcs)
+    if _PROF is not None:
+        _META['seg_concat_fwd'] = dict(shape=(b, rows, nm, a), flops=0.0, bytes=float(b * a * (2 * rows * 4 + nm * (4 + mcs[0].element_size()))))
+    _launch('seg_concat_fwd', 'mgdt_seg_concat_fwd', ptr(y), b, rows, a, arr, len(mcs), nm, ptr(out), dtype_code(mcs[0].dtype), stream())
+    return out
+
+
+SEG_MASK_SKIP = True     # tests flip this: (detection, tile) pairs outside the detection's box store zeros without the GEMM vs computing every pair
+MASK_MODES = ('process_mask', 'process_mask_up', 'process_mask_upsample', 'process_mask_native')
+
+
+def seg_mask_plan(mode, mh, mw, shape):
+    """Host-side parameters of one mgdt_seg_masks_fwd launch for the reference routine `mode` (yolo/utils/ops.py:560-636) on mh x mw protos and
+    the image shape (h, w) the routine is given: (top, left, win_h, win_w, out_h, out_w, crop_before, box_sx, box_sy, crop_after)."""
+    import numpy as np
+    ih, iw = int(shape[0]), int(shape[1])
+    if mode not in MASK_MODES:
+        raise RuntimeError(f'mask mode {mode!r} is not one of {MASK_MODES}')
+    if ih < 1 or iw < 1:
+        raise RuntimeError(f'mask assembly: image shape {tuple(shape)}')
+    if mode in ('process_mask', 'process_mask_up'):
+        # `downsampled_bboxes[:, 0] *= mw / iw`: a Python double, rounded to the tensor's float32 for the multiplication
+        sx, sy = float(np.float32(mw / iw)), float(np.float32(mh / ih))
+        oh, ow = (mh, mw) if mode == 'process_mask' else (ih, iw)
+        return 0, 0, mh, mw, oh, ow, 1, sx, sy, 0
+    if mode == 'process_mask_upsample':
+        return 0, 0, mh, mw, ih, iw, 0, 1.0, 1.0, 1
+    gain = min(mh / ih, mw / iw)
+    pad = (mw - iw * gain) / 2, (mh - ih * gain) / 2
+    top, left = int(pad[1]), int(pad[0])
+    bottom, right = int(mh - pad[1]), int(mw - pad[0])
+    if bottom <= top or right <= left:
+        raise RuntimeError(f'process_mask_native: the letter-box window of {mh}x{mw} protos for shape {tuple(shape)} is empty')
+    return top, left, bottom - top, right - left, ih, iw, 0, 1.0, 1.0, 1
+
+
+def seg_skip_share(rows, counts, mh, mw, shape, mode):
+    """Host-side count of the (detection, tile) pairs mgdt_seg_masks_fwd skips for these NMS rows (a CPU tensor (B, max_det, 6+nm)) and counts:
+    (skipped, all pairs), by the kernel's own rule in float32 on the tile grid of mgdt_seg_mask_geometry.  Reporting / tests only."""
+    import numpy as np
+    f = np.float32
+    top, left, wh, ww, oh, ow, cb, bsx, bsy, ca = seg_mask_plan(mode, mh, mw, shape)
+    geom = (C.c_int * 4)()
+    if L.lib().mgdt_seg_mask_geometry(wh, ww, oh, ow, geom) != 1:
+        raise RuntimeError(f'mask assembly: {wh}x{ww} -> {oh}x{ow} is not covered')
+    th, tw, ny, nx = list(geom)
+
+    def tap(scale, o, n_in):
+        s = max(f(f(scale) * f(f(o) + f(0.5))) - f(0.5), f(0))
+        i0 = min(int(s), n_in - 1)
+        return i0, i0 + (1 if i0 < n_in - 1 else 0)
+    sy, sx = f(wh) / f(oh), f(ww) / f(ow)
+    r = rows.detach().float().cpu().numpy()
+    skipped = pairs = 0
+    for ty in range(ny):
+        oy0, oy1 = ty * th, min(ty * th + th, oh)
+        ry0, ry1 = tap(sy, oy0, wh)[0], tap(sy, oy1 - 1, wh)[1]
+        for tx in range(nx):
+            ox0, ox1 = tx * tw, min(tx * tw + tw, ow)
+            rx0, rx1 = tap(sx, ox0, ww)[0], tap(sx, ox1 - 1, ww)[1]
+            for b, n in enumerate(counts):
+                x1, y1, x2, y2 = (r[b, :n, k] for k in range(4))
+                dead = np.zeros(n, bool)
+                if ca:
+                    dead |= (f(ox1 - 1) < x1) | ~(f(ox0) < x2) | (f(oy1 - 1) < y1) | ~(f(oy0) < y2)
+                if cb:
+                    dead |= ((f(left + rx1) < x1 * f(bsx)) | ~(f(left + rx0) < x2 * f(bsx)) | (f(top + ry1) < y1 * f(bsy)) | ~(f(top + ry0) < y2 * f(bsy)))
+                skipped += int(dead.sum())
+                pairs += int(n)
+    return skipped, pairs
+
+
+def seg_masks(protos, rows, counts_dev, counts, shape, mode, out_dtype=torch.uint8, out=None):
+    """mgdt_seg_masks_fwd: the masks of a whole batch in one launch.  protos (B, nm, mh, mw) NHWC activation (fp32 / bf16), rows (B, max_det, 6+nm)
+    fp32 + counts_dev (B,) int32 as `nms_masks` returns them, counts = the host copy of counts_dev -> (sum(counts), H, W) 0 / 1 masks of
+    `out_dtype` (uint8 or float32), image after image.  `out`: a caller's buffer of at least that many elements (tests: guard bytes behind)."""
+    b, nm, mh, mw = protos.shape
+    if rows.dim() != 3 or rows.shape[0] != b or rows.shape[2] != 6 + nm or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise RuntimeError(f'mask assembly: rows must be a contiguous float32 (B={b}, max_det, 6+nm={6 + nm}) tensor for protos with nm={nm} channels, '
+                           f'got {tuple(rows.shape)} {rows.dtype}')
+    if nm != 32:
+        raise RuntimeError(f'mask assembly: the kernel is built for nm = 32 mask coefficients, got {nm}')
+    if out_dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f'mask assembly: masks are uint8 or float32, not {out_dtype}')
+    _need_gpu(protos)
+    _need_gpu(rows)
+    if not is_nhwc(protos):
+        raise RuntimeError('mask assembly: protos must be NHWC-backed (the Proto module output, or ops.copy into ops.new_act)')
+    counts = [int(c) for c in counts]
+    if len(counts) != b or any(c < 0 or c > rows.shape[1] for c in counts):
+        raise RuntimeError(f'mask assembly: counts {counts} do not fit (B={b}, max_det={rows.shape[1]})')
+    top, left, wh, ww, oh, ow, cb, sx, sy, ca = seg_mask_plan(mode, mh, mw, shape)
+    total = sum(counts)
+    if out is None:
+        out = torch.empty(total, oh, ow, dtype=out_dtype, device=protos.device)
+    elif out.dtype != out_dtype or out.numel() < total * oh * ow or not out.is_contiguous():
+        raise RuntimeError('mask assembly: `out` must be a contiguous buffer of out_dtype holding sum(counts) x H x W elements')
+    if total == 0:
+        return out
+    offs = [0] * b
+    for i in range(1, b):
+        offs[i] = offs[i - 1] + counts[i - 1]
+    offsets = torch.tensor(offs, dtype=torch.int32).to(protos.device, non_blocking=True)
+    if _PROF is not None:
+        _META['seg_masks_fwd'] = dict(shape=(b, total, mh, mw, oh, ow), flops=2.0 * total * wh * ww * nm,
+                                      bytes=float(total * oh * ow * out.element_size() + (total + 15) // 16 * wh * ww * nm * protos.element_size()))
+    _launch('seg_masks_fwd', 'mgdt_seg_masks_fwd', vp(protos), ptr(rows), ptr(counts_dev), ptr(offsets), rows.shape[1], nm, top, left, wh, ww, oh, ow,
+            cb, sx, sy, ca, 0 if SEG_MASK_SKIP else 1, ptr(out), 1 if out_dtype == torch.uint8 else 0, dtype_code(protos.dtype), stream())
+    return out
+
+
 def val_match(det, ndet, labels, nlab, iouv):
     """Validator matching for a batch (mgdt_val_match_fwd): det (B, max_det, 6) fp32 + ndet (B,) int32 as returned by `nms`, labels
     (B, max_lab, 5) fp32 [cls, x1, y1, x2, y2] + nlab (B,) int32, iouv (T,) fp32 -> correct (B, max_det, T) bool."""
