@@ -346,6 +346,29 @@ int mgdt_seg_masks_fwd(const mgdt_view* protos, const float* rows, const int32_t
                        int top, int left, int win_h, int win_w, int out_h, int out_w, int crop_before, float box_sx, float box_sy,
                        int crop_after, int no_skip, void* out, int out_u8, int dtype, mgdt_stream s);
 
+/* ---- instance-segmentation validation (reference yolo/v8/segment/val.py:131-166, yolo/utils/metrics.py:131-147 mask_iou) -------------
+ * mask_iou: iou [n][max_lab][max_det] fp32 of every (label, detection) pair of a batch in one call (a clear of the workspace, the i8 MFMA kernel,
+ *   a small final pass).  pred: uint8 0 / 1 masks [sum(counts)][hw] exactly as mgdt_seg_masks_fwd writes them, with its device counts[n] / offsets[n]
+ *   (counts are clamped to max_det).  Ground truth, gt_index_map != 0 (the reference's overlap_mask=True): gt uint8 [n][hw], pixel value j + 1 belongs to
+ *   label j of that image, 0 is background (lab_offsets may be NULL); gt_index_map == 0: instance masks uint8 [sum(nlab)][hw] with nlab[n] and
+ *   lab_offsets[n].  Intersections and areas are exact integers; iou = inter / ((area_gt + area_pred) - inter + eps) in fp32 with an IEEE division.
+ *   Entries with label >= nlab[i] or detection >= counts[i] are WRITTEN as 0.  ws: mgdt_mask_iou_workspace_bytes(n, max_det, max_lab) bytes.
+ *   Limits (MGDT_BAD_SHAPE before any launch): n <= 65535, max_det <= 1024, max_lab <= 256 (255 as an index map), hw <= 2^24,
+ *   n * max_lab * max_det < 2^31.
+ * gt_masks_resample: the ground truth of either form resampled to out_h x out_w as the reference does when the sizes differ (each binary mask:
+ *   bilinear, align_corners=False, > 0.5), written as instance masks uint8 [sum(nlab)][out_h][out_w] at lab_offsets.  Same limits; h*w, out_h*out_w <= 2^24.
+ * val_match_iou: the matching rule of mgdt_val_match_fwd on a given iou [n][max_lab][max_det]: det_cls / lab_cls point at the class of detection /
+ *   label 0 of image 0, consecutive rows det_stride / lab_stride floats apart (images max_det * det_stride / max_lab * lab_stride apart), so the
+ *   rows of mgdt_nms_masks_fwd (class at column 5) and [cls, box] labels (column 0) are read in place.  correct [n][max_det][n_iou] uint8. */
+size_t mgdt_mask_iou_workspace_bytes(int n, int max_det, int max_lab);
+int mgdt_mask_iou_fwd(const uint8_t* pred, const int32_t* counts, const int32_t* offsets, int n, int max_det, const uint8_t* gt, int gt_index_map,
+                      const int32_t* nlab, const int32_t* lab_offsets, int max_lab, int hw, float eps, float* iou, void* ws, size_t ws_bytes,
+                      mgdt_stream s);
+int mgdt_gt_masks_resample_fwd(const uint8_t* gt, int gt_index_map, const int32_t* nlab, const int32_t* lab_offsets, int n, int max_lab, int h, int w,
+                               int out_h, int out_w, uint8_t* out, mgdt_stream s);
+int mgdt_val_match_iou_fwd(const float* iou, int n, int max_lab, int max_det, const float* det_cls, int det_stride, const int32_t* ndet,
+                           const float* lab_cls, int lab_stride, const int32_t* nlab, const float* iouv, int n_iou, uint8_t* correct, mgdt_stream s);
+
 /* ---- validator matching: DetectionValidator._process_batch, yolo/v8/detect/val.py:152-175, for a batch ----------
  * det [n][max_det][6] (x1,y1,x2,y2,conf,cls; the layout mgdt_nms_fwd writes) with ndet[n] valid rows, labels [n][max_lab][5]
  * (cls,x1,y1,x2,y2 in the same pixel frame) with nlab[n] valid rows, iouv[n_iou] ascending IoU levels (n_iou <= 16).

@@ -1064,6 +1064,101 @@ def val_match(det, ndet, labels, nlab, iouv):
     return correct.view(torch.bool)
 
 
+# ------------------------------------------------------------------ instance-segmentation validation (mask IoU, matching from an IoU matrix)
+MASK_IOU_MAX_DET, MASK_IOU_MAX_LAB, MASK_IOU_MAX_HW = 1024, 256, 1 << 24
+
+
+def _i32(t, n, what):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise RuntimeError(f'{what} must be a contiguous int32 tensor of {n} elements, got {tuple(t.shape)} {t.dtype}')
+    _need_gpu(t)
+    return t
+
+
+def exclusive_offsets(counts_dev):
+    """(B,) int32 counts on the device -> their exclusive prefix sums (int32), without a host sync."""
+    c = torch.cumsum(counts_dev, 0, dtype=torch.int32)
+    return c - counts_dev
+
+
+def _gt_check(gt, index_map, b, what):
+    if gt.dtype != torch.uint8 or gt.dim() != 3 or not gt.is_contiguous():
+        raise RuntimeError(f'{what}: the ground truth is a contiguous uint8 tensor, (B, H, W) index maps or (sum(nlab), H, W) instance masks, got '
+                           f'{tuple(gt.shape)} {gt.dtype}')
+    if index_map and gt.shape[0] != b:
+        raise RuntimeError(f'{what}: {gt.shape[0]} index maps for a batch of {b}')
+    _need_gpu(gt)
+
+
+def mask_iou_batch(masks, counts_dev, offsets, max_det, gt, nlab, max_lab, index_map=True, lab_offsets=None, eps=1e-7, out=None):
+    """mgdt_mask_iou_fwd: masks (sum(counts), H, W) uint8 0 / 1 as `seg_masks` lays them out + counts_dev / offsets (B,) int32 on the device; gt the
+    (B, H, W) uint8 index maps (index_map=True: pixel value j + 1 = label j of that image) or (sum(nlab), H, W) uint8 instance masks with
+    lab_offsets; nlab (B,) int32 -> iou (B, max_lab, max_det) float32, zero past nlab[i] / counts[i].  `out`: a caller's buffer (tests: guards)."""
+    _need_gpu(masks)
+    b = counts_dev.numel()
+    if masks.dtype != torch.uint8 or masks.dim() != 3 or not masks.is_contiguous():
+        raise RuntimeError(f'mask_iou: predicted masks are a contiguous uint8 (sum(counts), H, W) tensor, got {tuple(masks.shape)} {masks.dtype}')
+    _gt_check(gt, index_map, b, 'mask_iou')
+    if tuple(gt.shape[1:]) != tuple(masks.shape[1:]):
+        raise RuntimeError(f'mask_iou: ground truth {tuple(gt.shape[1:])} and predictions {tuple(masks.shape[1:])} differ in size (ops.gt_masks_resample)')
+    _i32(counts_dev, b, 'mask_iou: counts')
+    _i32(offsets, b, 'mask_iou: offsets')
+    _i32(nlab, b, 'mask_iou: nlab')
+    if not index_map:
+        if lab_offsets is None:
+            raise RuntimeError('mask_iou: instance masks need lab_offsets')
+        _i32(lab_offsets, b, 'mask_iou: lab_offsets')
+    hw = masks.shape[1] * masks.shape[2]
+    lib = L.lib()
+    ws_bytes = lib.mgdt_mask_iou_workspace_bytes(b, max_det, max_lab)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=masks.device)
+    if out is None:
+        out = torch.empty(b, max_lab, max_det, dtype=torch.float32, device=masks.device)
+    elif out.dtype != torch.float32 or out.numel() < b * max_lab * max_det or not out.is_contiguous():
+        raise RuntimeError('mask_iou: `out` must be a contiguous float32 buffer of B x max_lab x max_det elements')
+    if _PROF is not None:
+        _META['mask_iou_fwd'] = dict(shape=(b, max_lab, max_det, hw), flops=2.0 * b * max_lab * max_det * hw, bytes=float(masks.numel() + gt.numel()))
+    _launch('mask_iou_fwd', 'mgdt_mask_iou_fwd', ptr(masks), ptr(counts_dev), ptr(offsets), b, max_det, ptr(gt), 1 if index_map else 0, ptr(nlab),
+            ptr(lab_offsets), max_lab, hw, float(eps), ptr(out), ptr(ws), ws_bytes, stream())
+    return out
+
+
+def gt_masks_resample(gt, nlab, lab_offsets, total, max_lab, shape, index_map=True):
+    """mgdt_gt_masks_resample_fwd: ground truth of either form -> (total = sum(nlab), *shape) uint8 instance masks, each binary mask resampled
+    bilinearly (align_corners=False) and thresholded > 0.5 as val.py:146-148 does when the sizes differ."""
+    b = nlab.numel()
+    _gt_check(gt, index_map, b, 'gt_masks_resample')
+    _i32(nlab, b, 'gt_masks_resample: nlab')
+    _i32(lab_offsets, b, 'gt_masks_resample: lab_offsets')
+    oh, ow = int(shape[0]), int(shape[1])
+    out = torch.empty(int(total), oh, ow, dtype=torch.uint8, device=gt.device)
+    if int(total) == 0:
+        return out
+    _launch('gt_masks_resample_fwd', 'mgdt_gt_masks_resample_fwd', ptr(gt), 1 if index_map else 0, ptr(nlab), ptr(lab_offsets), b, max_lab,
+            gt.shape[1], gt.shape[2], oh, ow, ptr(out), stream())
+    return out
+
+
+def val_match_iou(iou, det_rows, ndet, labels, nlab, iouv):
+    """mgdt_val_match_iou_fwd: iou (B, max_lab, max_det) fp32, det_rows (B, max_det, >= 6) fp32 (class at column 5: the rows of `nms` / `nms_masks`
+    read in place), labels (B, max_lab, >= 1) fp32 (class at column 0) -> correct (B, max_det, T) bool by the rule of `val_match`."""
+    _need_gpu(iou)
+    b, ml, md = iou.shape
+    if (det_rows.dim() != 3 or det_rows.shape[0] != b or det_rows.shape[1] != md or det_rows.shape[2] < 6 or det_rows.dtype != torch.float32
+            or not det_rows.is_contiguous()):
+        raise RuntimeError(f'val_match_iou: det_rows must be contiguous float32 (B={b}, max_det={md}, >= 6), got {tuple(det_rows.shape)} {det_rows.dtype}')
+    if labels.dim() != 3 or labels.shape[0] != b or labels.shape[1] != ml or labels.dtype != torch.float32 or not labels.is_contiguous():
+        raise RuntimeError(f'val_match_iou: labels must be contiguous float32 (B={b}, max_lab={ml}, >= 1), got {tuple(labels.shape)} {labels.dtype}')
+    if iou.dtype != torch.float32 or not iou.is_contiguous() or iouv.dtype != torch.float32:
+        raise RuntimeError('val_match_iou: iou and iouv are contiguous float32 tensors')
+    _i32(ndet, b, 'val_match_iou: ndet')
+    _i32(nlab, b, 'val_match_iou: nlab')
+    correct = torch.empty(b, md, iouv.numel(), dtype=torch.uint8, device=iou.device)
+    _launch('val_match_iou_fwd', 'mgdt_val_match_iou_fwd', ptr(iou), b, ml, md, C.c_void_p(det_rows.data_ptr() + 20), det_rows.shape[2], ptr(ndet),
+            ptr(labels), labels.shape[2], ptr(nlab), ptr(iouv), iouv.numel(), ptr(correct), stream())
+    return correct.view(torch.bool)
+
+
 # ------------------------------------------------------------------ detection loss (assigner + BCE/CIoU/DFL)
 def _view_array(ts):
     views = [view(t) for t in ts]

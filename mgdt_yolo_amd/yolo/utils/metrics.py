@@ -1,6 +1,6 @@
-"""Box overlap functions and the validator's AP reduction with the reference's names (reference: yolo/utils/metrics.py).
+"""Box and mask overlap functions and the validator's AP reduction with the reference's names (reference: yolo/utils/metrics.py).
 
-`box_iou`, `bbox_iou` (IoU / GIoU / DIoU / CIoU, forward values) run as HIP kernels (mgdt_box_iou / mgdt_bbox_iou).  `ap_per_class` keeps
+`box_iou`, `bbox_iou` (IoU / GIoU / DIoU / CIoU, forward values) and `mask_iou` run as HIP kernels (mgdt_box_iou / mgdt_bbox_iou / mgdt_mask_iou_fwd).  `ap_per_class` keeps
 the reference's signature and return tuple: the O(detections) part - per-class cumulative TP / FP, recall / precision curves, compute_ap's
 envelope, 101-point interpolation and integration, the 1000-point P / R-vs-confidence curves - runs on the device in fp64 with numpy's own
 arithmetic order (mgdt_ap_per_class: the AP matrix equals the reference's bit for bit); grouping the detections by (class, confidence) is a
@@ -34,6 +34,36 @@ def bbox_iou(box1, box2, xywh=True, GIoU=False, DIoU=False, CIoU=False, eps=1e-7
     L.check(L.lib().mgdt_bbox_iou(hip.ptr(b1), 4 if b1.shape[0] == n and n > 1 or b1.shape[0] == n == 1 else 0, hip.ptr(b2),
                                   4 if b2.shape[0] == n and n > 1 or b2.shape[0] == n == 1 else 0, n, int(bool(xywh)), mode, float(eps), hip.ptr(out),
                                   hip.stream()), 'bbox_iou')
+    return out
+
+
+def mask_iou(mask1, mask2, eps=1e-7):
+    """IoU of 0 / 1 masks: mask1 (N, n) ground truth, mask2 (M, n) predictions, float32 or uint8 holding 0 / 1 ONLY
+    (the reference accepts any float; other values are refused by a device-side assertion) -> (N, M) float32 (metrics.py:131-147), on the
+    mask bytes with the int8 matrix cores (mgdt_mask_iou_fwd).  Intersections and areas are exact integers, so the result equals the reference's
+    float32 matmul bit for bit for n <= 2^24.  More rows than the kernel's limits (256 / 1024) are processed in blocks."""
+    hip._need_gpu(mask1)
+    if mask1.dim() != 2 or mask2.dim() != 2 or mask1.shape[1] != mask2.shape[1]:
+        raise RuntimeError(f'mask_iou: (N, n) and (M, n) masks expected, got {tuple(mask1.shape)} and {tuple(mask2.shape)}')
+    def u8(m):
+        if m.dtype != torch.uint8:
+            if hasattr(torch, '_assert_async'):       # no host sync; the conversion below truncates, so anything but 0 / 1 would change the answer
+                torch._assert_async(((m == 0) | (m == 1)).all(), 'mask_iou: masks must hold 0 / 1 only')
+            m = m.to(torch.uint8)
+        return m.contiguous()
+    m1, m2 = u8(mask1), u8(mask2)
+    N, M, n = m1.shape[0], m2.shape[0], m1.shape[1]
+    out = torch.zeros(N, M, dtype=torch.float32, device=m1.device)
+    if N == 0 or M == 0 or n == 0:
+        return out
+    cnt = lambda k: torch.full((1,), k, dtype=torch.int32, device=m1.device)
+    zero = torch.zeros(1, dtype=torch.int32, device=m1.device)
+    for i in range(0, N, hip.MASK_IOU_MAX_LAB):
+        a = m1[i:i + hip.MASK_IOU_MAX_LAB]
+        for j in range(0, M, hip.MASK_IOU_MAX_DET):
+            b = m2[j:j + hip.MASK_IOU_MAX_DET]
+            out[i:i + a.shape[0], j:j + b.shape[0]] = hip.mask_iou_batch(b.view(-1, 1, n), cnt(b.shape[0]), zero, b.shape[0], a.view(-1, 1, n),
+                                                                         cnt(a.shape[0]), a.shape[0], index_map=False, lab_offsets=zero, eps=eps)[0]
     return out
 
 
