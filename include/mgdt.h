@@ -346,6 +346,21 @@ int mgdt_seg_masks_fwd(const mgdt_view* protos, const float* rows, const int32_t
                        int top, int left, int win_h, int win_w, int out_h, int out_w, int crop_before, float box_sx, float box_sy,
                        int crop_after, int no_skip, void* out, int out_u8, int dtype, mgdt_stream s);
 
+/* ---- pose-estimation inference (nn/modules/head.py:215-253 Pose, yolo/v8/pose/predict.py:16-41, yolo/utils/ops.py:636-666) -----------------------
+ * pose_concat: y fp32 [n][rows][a] (rows = 4 + nc, as Detect writes it) + the per-level cv4 maps kpt[l] (n x h_l x w_l NHWC of `dtype`, at least nk
+ *   channels per pixel - the pixel stride may exceed nk: the zero-padded MFMA route leaves 52 channels for nk = 51) and the levels' strides[l] (host) ->
+ *   out fp32 [n][rows+nk][a]: rows 0..rows copied, row rows+k of anchor a_off_l + pixel (x, y) decoded from v = kpt[l][pixel][k] as kpts_decode's
+ *   non-export branch does in fp32: k % ndim == 0: (v*2 + ((x + 0.5) - 0.5)) * stride, == 1: the same with y, == 2 (ndim 3): sigmoid(v);
+ *   kpt_raw fp32 [n][nk][a] = the v themselves (the `kpt` the head returns next to the feature maps).  nk <= 240, ndim in {2, 3}, <= 4 levels.
+ * pose_scale: PosePredictor.postprocess after the NMS, in place on rows [n][max_det][lead+nk] for the first min(counts[i], max_det) rows of image i;
+ *   lead = 6: the layout mgdt_nms_masks_fwd writes, lead = 0: bare keypoint coordinates (scale_coords / clip_coords alone).  meta fp32 [n][8] =
+ *   {gain, kpt_pad_x, kpt_pad_y, h0, w0, box_pad_x, box_pad_y, normalize} (device), gain / pads from the host exactly as scale_coords (fractional pads)
+ *   and scale_boxes (rounded pads) compute them.  Columns 0..4 (lead = 6): clip((v - box_pad) / gain, 0, w0 | h0), then round half-to-even (torch.round);
+ *   columns lead + k with k % ndim == 0 / 1: clip((v - kpt_pad) / gain, 0, w0 | h0), divided by w0 | h0 when normalize != 0; every other column untouched. */
+int mgdt_pose_concat_fwd(const float* y, int n, int rows, int a_total, const mgdt_view* const* kpt, const float* strides, int n_levels, int nk,
+                         int ndim, float* out, float* kpt_raw, int dtype, mgdt_stream s);
+int mgdt_pose_scale_fwd(float* rows, const int32_t* counts, const float* meta, int n, int max_det, int lead, int nk, int ndim, mgdt_stream s);
+
 /* ---- instance-segmentation validation (reference yolo/v8/segment/val.py:131-166, yolo/utils/metrics.py:131-147 mask_iou) -------------
  * mask_iou: iou [n][max_lab][max_det] fp32 of every (label, detection) pair of a batch in one call (a clear of the workspace, the i8 MFMA kernel,
  *   a small final pass).  pred: uint8 0 / 1 masks [sum(counts)][hw] exactly as mgdt_seg_masks_fwd writes them, with its device counts[n] / offsets[n]

@@ -154,6 +154,8 @@ PROTOTYPES = {
     'mgdt_seg_concat_fwd': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     'mgdt_seg_mask_geometry': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     'mgdt_seg_masks_fwd': (_i, [VP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _i, _vp]),
+    'mgdt_pose_concat_fwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'mgdt_pose_scale_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'mgdt_mask_iou_workspace_bytes': (_sz, [_i, _i, _i]),
     'mgdt_mask_iou_fwd': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _sz, _vp]),
     'mgdt_gt_masks_resample_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

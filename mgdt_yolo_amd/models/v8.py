@@ -80,9 +80,32 @@ SEG_CONFIGS = {
 }
 
 
+def _pose(head):
+    """`head` with its Detect row replaced by Pose [nc, kpt_shape] (models/v8/yolov8-pose.yaml:46)."""
+    def build():
+        rows = head()
+        rows[-1] = [rows[-1][0], 1, 'Pose', ['nc', 'kpt_shape']]
+        return rows
+    return build
+
+
+def _pose_cfg(block, head, nc, kpt_shape):
+    d = _cfg(block, _pose(head), nc)
+    d['kpt_shape'] = list(kpt_shape)
+    return d
+
+
+# pose-estimation graphs: `yolov8-pose` is the reference's models/v8/yolov8-pose.yaml (nc 1, 17 keypoints of (x, y, visibility)); `mspa_c2f_gd_yolov8-pose`
+# is this fork's MSPA-GD graph with the same head swap (a one-level head; the reference ships no file for it).
+POSE_CONFIGS = {
+    'yolov8-pose': lambda nc=1, kpt_shape=(17, 3): _pose_cfg('C2f', _pan_head, nc, kpt_shape),
+    'mspa_c2f_gd_yolov8-pose': lambda nc=1, kpt_shape=(17, 3): _pose_cfg('MSPA_C2f', _gd_head, nc, kpt_shape),
+}
+
+
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS / SEG_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
-    table = CONFIGS if name in CONFIGS else SEG_CONFIGS
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    table = CONFIGS if name in CONFIGS else SEG_CONFIGS if name in SEG_CONFIGS else POSE_CONFIGS
     d = table[name]() if nc is None else table[name](nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale
     d['yaml_file'] = f'{name}.yaml'

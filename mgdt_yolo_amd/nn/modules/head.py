@@ -14,7 +14,7 @@ from ... import ops
 from .block import DFL, Proto
 from .conv import Conv, HipModule
 
-__all__ = ('Detect', 'Segment', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
+__all__ = ('Detect', 'Segment', 'Pose', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
 
 
 class _HeadConv(HipModule):
@@ -246,6 +246,89 @@ class Segment(Detect):
 
     def backward(self, grads):
         raise NotImplementedError(SEG_TRAIN_MSG)
+
+
+POSE_TRAIN_MSG = ('pose training is not built: the reference\'s v8PoseLoss calls the assigner with the old signature and cannot run in this fork, so '
+                  'there is nothing to pin a training path to; Pose / PoseModel are inference modules (call .eval())')
+
+
+def padded_conv_params(m, cin_p, cout_p):
+    """(weight (cout_p, cin_p, k, k), conv bias or None, BatchNorm tuple or None) of `m` (a Conv before or after fuse(), or a plain nn.Conv2d) with its
+    channels zero-padded: padded input channels meet zero weights; padded output channels have zero weights, zero bias and the identity BatchNorm
+    (gamma 1, beta 0, mean 0, var 1: folded scale * 0 = 0, folded shift 0), so they carry act(0) = 0 for SiLU and no real channel changes by a bit.
+    Works on whatever device the parameters live on."""
+    conv = m.conv if isinstance(m, Conv) else m
+    w = conv.weight.detach().float()
+    cout, cin = w.shape[:2]
+    if cout_p < cout or cin_p < cin:
+        raise RuntimeError(f'padded_conv_params: cannot pad {cout}x{cin} channels down to {cout_p}x{cin_p}')
+    wp = w.new_zeros(cout_p, cin_p, *w.shape[2:])
+    wp[:cout, :cin] = w
+    pad = lambda t, fill: None if t is None else torch.cat([t.detach().float(), torch.full((cout_p - cout,), fill, dtype=torch.float32, device=t.device)])
+    bn = None
+    if isinstance(m, Conv) and hasattr(m, 'bn'):
+        bn = (pad(m.bn.weight, 1.0), pad(m.bn.bias, 0.0), pad(m.bn.running_mean, 0.0), pad(m.bn.running_var, 1.0), m.bn.eps)
+    return wp, pad(conv.bias, 0.0), bn
+
+
+class Pose(Detect):
+    """YOLOv8 Pose head (reference head.py:215-253): Detect plus, per level, a keypoint branch cv4 (3x3, 3x3, 1x1 + bias -> nk = kpt_shape[0] *
+    kpt_shape[1]).  Eval returns (cat(y, pred_kpt) (B, 4+nc+nk, A) fp32, (feats, kpt (B, nk, A) fp32 raw)); export=True returns the concatenated
+    tensor alone.  Detect.forward runs unchanged; one launch (mgdt_pose_concat_fwd) then decodes the keypoints and writes the wide prediction from
+    its y and the NHWC cv4 maps, and the best-class NMS keys are carried over to it.  c4 = max(ch[0] // 4, nk) is 51 for kpt_shape (17, 3) at the
+    n, s and m scales, which the MFMA convolution does not take (cin % 8, cout % 4): the branch then runs on it over zero-padded panels (56 hidden,
+    52 output channels, `padded_conv_params`), see ops.POSE_PAD_MFMA.  All convolutions of this head stay bf16 under quantize_fp8."""
+
+    def __init__(self, nc=80, kpt_shape=(17, 3), ch=()):
+        super().__init__(nc, ch)
+        self.kpt_shape = kpt_shape
+        self.nk = kpt_shape[0] * kpt_shape[1]
+        c4 = max(ch[0] // 4, self.nk)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+
+    def q8_site(self, key, x, x2=None):
+        return None                                           # fp8 for the Pose head is not built: its merged first convolutions stay bf16
+
+    def _kpt_branch(self, i, xi):
+        """cv4[i](xi) as an NHWC map whose first nk channels are the raw keypoints (52 channels on the padded route for nk = 51)."""
+        c0, c1, c2 = self.cv4[i]
+        dt = c0.out_dtype(xi)
+        b, _, h, w = xi.shape
+        c4, nk = c2.in_channels, self.nk
+        c4p, nkp = -(-c4 // 8) * 8, -(-nk // 4) * 4
+        plain = lambda m: (isinstance(m, Conv) and m.plain_affine() and isinstance(m.act, nn.SiLU) and m.conv.kernel_size == (3, 3) and m.conv.stride == (1, 1)
+                           and m.conv.groups == 1 and m.conv.dilation == (1, 1) and m.conv.padding == (1, 1) and not m._forward_hooks)
+        if (ops.POSE_PAD_MFMA and (c4p != c4 or nkp != nk) and plain(c0) and plain(c1) and c2.kernel_size == (1, 1) and c2.groups == 1
+                and ops.conv_can_mfma(xi, c0.conv.in_channels, c4p, 3, 1, 1, dt)):
+            # panels packed from padded copies are derived copies (never refreshed in place): rebuilt whenever a live tensor they depend on changes
+            pk0 = self._cached(('kpt', i, 0, dt), c0.affine_tensors(), lambda: ops.PackedConv(*padded_conv_params(c0, c0.conv.in_channels, c4p), 3, dt))
+            pk1 = self._cached(('kpt', i, 1, dt), c1.affine_tensors(), lambda: ops.PackedConv(*padded_conv_params(c1, c4p, c4p), 3, dt))
+            pk2 = self._cached(('kpt', i, 2, dt), [c2.weight, c2.bias], lambda: ops.PackedConv(*padded_conv_params(c2, c4p, nkp), 1, dt))
+            t = ops.conv2d(ops.conv2d(xi, pk0, 1, ops.ACT_SILU), pk1, 1, ops.ACT_SILU)
+            return ops.conv2d(t, pk2, 1, ops.ACT_NONE)
+        t = c1(c0(xi))
+        m = ops.new_act(b, nk, h, w, t.dtype, t.device)
+        _HeadConv.run(self, c2, t, m)
+        return m
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError(POSE_TRAIN_MSG)
+        kps = [self._kpt_branch(i, x[i]) for i in range(self.nl)]
+        export, self.export = self.export, False             # Detect.forward's own export form drops the feature maps
+        try:
+            y, feats = Detect.forward(self, x)
+        finally:
+            self.export = export
+        strides = self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])
+        cat, kpt = ops.pose_concat(y, kps, strides, self.nk, self.kpt_shape[1])
+        best = ops._best_keys_of(y, y.shape[0], y.shape[2])
+        if best is not None:
+            ops.attach_best_keys(cat, best)
+        return cat if self.export else (cat, (feats, kpt))
+
+    def backward(self, grads):
+        raise NotImplementedError(POSE_TRAIN_MSG)
 
 
 # ====================================================================================================================

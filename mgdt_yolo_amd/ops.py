@@ -949,6 +949,60 @@ def seg_concat(y, mcs):
     return out
 
 
+# ------------------------------------------------------------------ pose estimation (Pose head, keypoint decode, post-NMS scaling)
+POSE_PAD_MFMA = True     # tests / tools/pose_bench.py flip this: Pose.cv4 convolutions whose channel counts the MFMA kernel does not take (51) run on it over
+#                          zero-padded panels (56 / 52 channels) vs through mgdt_conv2d_direct_fwd
+
+
+def pose_concat(y, kps, strides, nk, ndim):
+    """mgdt_pose_concat_fwd: y (B, 4+nc, A) fp32 + per-level cv4 maps (B, >= nk, h, w) NHWC + the levels' strides (host floats) ->
+    (cat(y, kpts_decode(kpt)) (B, 4+nc+nk, A) fp32, kpt (B, nk, A) fp32 raw) (head.py:236-253, non-export decode)."""
+    _need_gpu(y)
+    b, rows, a = y.shape
+    _same(*kps)
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise RuntimeError('pose_concat: the prediction must be a contiguous float32 tensor')
+    if len(strides) != len(kps) or any(t.shape[1] < nk or not is_nhwc(t) for t in kps):
+        raise RuntimeError(f'pose_concat: one NHWC map with at least nk={nk} channels and one stride per level expected')
+    out = torch.empty(b, rows + nk, a, dtype=torch.float32, device=y.device)
+    raw = torch.empty(b, nk, a, dtype=torch.float32, device=y.device)
+    arr, keep = _view_array(kps)
+    st = (C.c_float * len(kps))(*[float(s) for s in strides])
+    if _PROF is not None:
+        _META['pose_concat_fwd'] = dict(shape=(b, rows, nk, a), flops=0.0, bytes=float(b * a * (2 * rows * 4 + nk * (8 + kps[0].element_size()))))
+    _launch('pose_concat_fwd', 'mgdt_pose_concat_fwd', ptr(y), b, rows, a, arr, st, len(kps), int(nk), int(ndim), ptr(out), ptr(raw), dtype_code(kps[0].dtype),
+            stream())
+    return out, raw
+
+
+def pose_scale_meta(img1_shape, img0_shape, normalize=False):
+    """Host side of mgdt_pose_scale_fwd for one image: [gain, kpt_pad_x, kpt_pad_y, h0, w0, box_pad_x, box_pad_y, normalize] with the gain and the
+    fractional padding of scale_coords (ops.py:653-655) and the rounded padding of scale_boxes (ops.py:104-105), in Python floats like the reference."""
+    gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+    pad = (img1_shape[1] - img0_shape[1] * gain) / 2, (img1_shape[0] - img0_shape[0] * gain) / 2
+    return [gain, pad[0], pad[1], float(img0_shape[0]), float(img0_shape[1]), float(round(pad[0] - 0.1)), float(round(pad[1] - 0.1)), float(bool(normalize))]
+
+
+def pose_scale(rows, counts_dev, meta, nk, ndim, lead=6):
+    """mgdt_pose_scale_fwd, in place: rows (B, max_det, lead+nk) fp32 contiguous, counts (B,) int32 on the device, meta (B, 8) fp32 on the device (one
+    `pose_scale_meta` row per image).  lead = 6: boxes scaled, clipped and rounded, keypoints scaled and clipped; lead = 0: keypoints only."""
+    _need_gpu(rows)
+    if rows.dtype != torch.float32 or rows.dim() != 3 or not rows.is_contiguous() or rows.shape[2] != lead + nk:
+        raise RuntimeError(f'pose_scale: rows must be a contiguous float32 (B, max_det, {lead} + nk={nk}) tensor, got {tuple(rows.shape)} {rows.dtype}')
+    b, md, _ = rows.shape
+    if (counts_dev.dtype != torch.int32 or counts_dev.numel() != b or not counts_dev.is_contiguous() or meta.dtype != torch.float32 or tuple(meta.shape) != (b, 8)
+            or not meta.is_contiguous()):
+        raise RuntimeError('pose_scale: counts (B,) int32 and meta (B, 8) float32 expected')
+    _need_gpu(counts_dev)
+    _need_gpu(meta)
+    if md == 0:
+        return rows
+    if _PROF is not None:
+        _META['pose_scale_fwd'] = dict(shape=(b, md, lead, nk), flops=0.0, bytes=float(2 * rows.numel() * 4))
+    _launch('pose_scale_fwd', 'mgdt_pose_scale_fwd', ptr(rows), ptr(counts_dev), ptr(meta), b, md, int(lead), int(nk), int(ndim), stream())
+    return rows
+
+
 SEG_MASK_SKIP = True     # tests flip this: (detection, tile) pairs outside the detection's box store zeros without the GEMM vs computing every pair
 MASK_MODES = ('process_mask', 'process_mask_up', 'process_mask_upsample', 'process_mask_native')
 

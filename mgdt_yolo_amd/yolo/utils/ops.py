@@ -1,4 +1,4 @@
-"""Detection and segmentation post-processing with the reference's names (reference: yolo/utils/ops.py)."""
+"""Detection, segmentation and pose post-processing with the reference's names (reference: yolo/utils/ops.py)."""
 import torch
 
 from ... import _lib as L
@@ -55,13 +55,45 @@ def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None):
     return boxes
 
 
+def _coords_inplace(coords, meta):
+    """One mgdt_pose_scale_fwd launch (lead = 0) on coords (..., 2 | 3) fp32 cuda, in place like the reference's helpers."""
+    hip._need_gpu(coords)
+    if coords.dtype != torch.float32 or coords.dim() < 1 or coords.shape[-1] not in (2, 3):
+        raise RuntimeError(f'keypoint helpers take float32 (..., 2) or (..., 3) coordinates, got {tuple(coords.shape)} {coords.dtype}')
+    n = coords.numel() // coords.shape[-1]
+    if n == 0:
+        return coords
+    flat = coords if coords.is_contiguous() else coords.contiguous()
+    dev = coords.device
+    hip.pose_scale(flat.view(1, n, coords.shape[-1]), torch.tensor([n], dtype=torch.int32).to(dev), torch.tensor([meta], dtype=torch.float32).to(dev),
+                   coords.shape[-1], coords.shape[-1], lead=0)
+    if flat is not coords:
+        coords.copy_(flat)
+    return coords
+
+
+def clip_coords(coords, shape):
+    """In-place clip of (..., 2 | 3) keypoint coordinates to the image (h, w): x to [0, w], y to [0, h] (ops.py:288-300)."""
+    return _coords_inplace(coords, [1.0, 0.0, 0.0, float(shape[0]), float(shape[1]), 0.0, 0.0, 0.0])
+
+
+def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None, normalize=False):
+    """Rescale keypoint coordinates (in place, like the reference) from the letter-boxed shape img1_shape (h, w) to the original img0_shape and
+    clip them (ops.py:636-666): the padding is NOT rounded here, unlike scale_boxes.  coords: float32 (..., 2) or (..., 3) [x, y(, visibility)]."""
+    meta = hip.pose_scale_meta(img1_shape, img0_shape, normalize)
+    if ratio_pad is not None:
+        meta[0], meta[1], meta[2] = ratio_pad[0][0], ratio_pad[1][0], ratio_pad[1][1]
+    return _coords_inplace(coords, meta)
+
+
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, labels=(),
                         max_det=300, nc=0, max_time_img=0.05, max_nms=30000, max_wh=7680):
     """Batched NMS, same signature and return type as the reference (ops.py:136-266): list of (n_i, 6) tensors
     [x1, y1, x2, y2, conf, cls] on prediction.device.  One fused HIP launch for the whole batch + one D2H of the counts.
 
     With mask channels (nm = prediction rows - 4 - nc > 0, a Segment head's output) the rows are (n_i, 6 + nm): the kept anchors' mask
-    coefficients behind the six detection columns (mgdt_nms_masks_fwd; the nm == 0 call is unchanged).
+    coefficients behind the six detection columns (mgdt_nms_masks_fwd; the nm == 0 call is unchanged).  A Pose prediction is the same call with
+    nm = nk decoded keypoint values.
 
     Differences, all documented in DESIGN.md: `max_time_img` is accepted and ignored (no wall-clock truncation);
     score ties are ordered by candidate index; `labels` (autolabelling a-priori boxes) are not on the hot path and raise.
