@@ -222,7 +222,8 @@ int mgdt_tood_layer_attn_fwd(const float* sums, int n, int c, int hw, const floa
                              int stacked, float* scale, mgdt_stream s);
 /* DCNv2 3x3, stride 1, pad 1, one deform group (block.py:401-432, mmcv modulated_deform_conv): offset_mask = N x H x W x (>=27):
  * 18 offsets (dy, dx per kernel point) then 9 mask logits (sigmoid applied inside, head.py:525).  w_gemm [9*cin][cout] fp32
- * (mgdt_conv_pack_direct layout), bias fp32[cout] or NULL. */
+ * (mgdt_conv_pack_direct layout), bias fp32[cout] or NULL.  The weight tile of 16 output channels (9 * cin * 64 B) is held in LDS: cin <= 284,
+ * MGDT_BAD_SHAPE beyond that before any launch. */
 int mgdt_dcnv2_fwd(const mgdt_view* x, const mgdt_view* offset_mask, const float* w_gemm, const float* bias, const mgdt_view* y, int dtype,
                    mgdt_stream s);
 /* The same on the MFMA path (bf16, cin % 8 == 0, cout in {16,32,48,64}, no bias): packed_w = mgdt_conv_pack(w, no BN, cin, cout, k = 3, bf16). */

@@ -8,7 +8,8 @@
 //   DCNv2 training                 : sampled-and-modulated columns materialised once (mgdt_dcn_im2col) so that the weight / column gradients are
 //                                    ordinary 1x1 conv wgrad / dgrad; the column gradient is scattered back to the input and reduced to the
 //                                    offset / mask-logit gradients by mgdt_dcn_col2im_bwd (mmcv modulated_deformable_col2im(_coord)).
-// Parity: unpinned like the forward (mmcv is absent); tests compare with torch.autograd of oracle/tood.py.
+// Parity: mmcv is absent, so the yardstick is oracle/tood.py; every kernel here is pinned to it (and to fp64 autograd of it) route by route, in
+// fp32 and bf16, by tests/test_tood_kernels.py.
 #include "common.h"
 
 #define TT_AT(T, v, n, h, w, c) ((T*)(v).p + ((long)(n) * (v).sn + (long)(h) * (v).sh + (long)(w) * (v).sw + (c)))
@@ -276,9 +277,9 @@ extern "C" int mgdt_tood_layer_attn_bwd(const float* sums, const float* dscale, 
                                                                                                   (float*)ws);
   const float* w_ = (const float*)ws;
   tt_sum_rows_kernel<<<cdiv(hid * c, 256), 256, 0, st>>>(w_, n, P, hid * c, dw1, accumulate);
-  tt_sum_rows_kernel<<<1, 256, 0, st>>>(w_ + (long)hid * c, n, P, hid, db1, accumulate);
+  tt_sum_rows_kernel<<<cdiv(hid, 256), 256, 0, st>>>(w_ + (long)hid * c, n, P, hid, db1, accumulate);
   tt_sum_rows_kernel<<<cdiv(stacked * hid, 256), 256, 0, st>>>(w_ + (long)hid * c + hid, n, P, stacked * hid, dw2, accumulate);
-  tt_sum_rows_kernel<<<1, 256, 0, st>>>(w_ + (long)hid * c + hid + (long)stacked * hid, n, P, stacked, db2, accumulate);
+  tt_sum_rows_kernel<<<cdiv(stacked, 256), 256, 0, st>>>(w_ + (long)hid * c + hid + (long)stacked * hid, n, P, stacked, db2, accumulate);
   MGDT_CHECK_LAUNCH("tood_layer_attn_bwd");
   return MGDT_OK;
 }

@@ -654,10 +654,11 @@ def dcnv2(x, offset_mask, w_gemm, bias, cout):
     return out
 
 
-def dcnv2_mfma(x, offset_mask, pk):
+def dcnv2_mfma(x, offset_mask, pk, out=None):
     """DCNv2 on the MFMA path (bf16): pk = PackedConv(weight, None, None, 3, bfloat16)."""
     b, _, h, w = x.shape
-    out = new_act(b, pk.cout, h, w, x.dtype, x.device)
+    out = new_act(b, pk.cout, h, w, x.dtype, x.device) if out is None else out
+    _same(x, offset_mask, out)
     _launch('dcnv2_mfma_fwd', 'mgdt_dcnv2_mfma_fwd', vp(x), vp(offset_mask), ptr(pk.w), vp(out), dtype_code(x.dtype), stream())
     return out
 
@@ -680,9 +681,9 @@ def gn_affine(y, gamma, beta, groups, eps):
     return A, B, mean, rstd
 
 
-def nc_affine_act_bwd(g, y, A, B, act):
-    gu = like(y)
-    _same(g, y)
+def nc_affine_act_bwd(g, y, A, B, act, out=None):
+    gu = like(y) if out is None else out
+    _same(g, y, gu)
     _launch('nc_affine_act_bwd', 'mgdt_nc_affine_act_bwd', vp(g), vp(y), ptr(A), ptr(B), act, vp(gu), dtype_code(y.dtype), stream())
     return gu
 
@@ -739,12 +740,12 @@ def dcn_im2col(x, om):
     return col
 
 
-def dcn_col2im_bwd(gcol, x, om):
-    """-> (gx in x's dtype, gom like om)."""
+def dcn_col2im_bwd(gcol, x, om, gom=None):
+    """-> (gx in x's dtype, gom like om: every channel written, the padding channels past the 27th with zeros)."""
     b, c, h, w = x.shape
     gx32 = torch.zeros(b, h, w, c, dtype=torch.float32, device=x.device)
-    gom = like(om)
-    _same(gcol, x, om)
+    gom = like(om) if gom is None else gom
+    _same(gcol, x, om, gom)
     _launch('dcn_col2im_bwd', 'mgdt_dcn_col2im_bwd', vp(gcol), vp(x), vp(om), ptr(gx32), vp(gom), dtype_code(x.dtype), stream())
     gx = gx32.permute(0, 3, 1, 2)                          # (B,C,H,W) view of the NHWC buffer = channels_last
     return (gx if x.dtype == torch.float32 else copy(gx, like(x))), gom
