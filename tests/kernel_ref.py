@@ -1,5 +1,6 @@
-"""Shared helpers of the per-route kernel tests (test_reverse_kernels.py, test_forward_kernels.py, test_tood_kernels.py): seeded inputs already representable in a kernel's
-dtype, NHWC device buffers and channel-slice views, the stated comparison bounds, and the float64 deformable-conv reference pieces.  A plain module, not a conftest."""
+"""Shared helpers of the per-route kernel tests (test_reverse_kernels.py, test_forward_kernels.py, test_tood_kernels.py, test_block_kernels.py): seeded inputs
+already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds, the float64 deformable-conv reference
+pieces and the restatements of the fused forward block kernels.  A plain module, not a conftest."""
 import zlib
 
 import torch
@@ -68,6 +69,23 @@ def _close(got, ref, dt, what=''):
         bound = 2.0 ** -8 * ref.abs() + 1e-3 * m
         worst = (err - bound).max().item()
         assert worst <= 0, (what, 'worst excess over the bf16 bound', worst, 'max err', err.max().item(), 'max ref', m)
+
+
+def _bound_use(got, ref, dt):
+    """Largest fraction of _close's bound that the error uses (1.0 = at the bound): a figure to print, never a check."""
+    got = got.detach().double().cpu().reshape(ref.shape)
+    ref = ref.detach().double().cpu()
+    err = (got - ref).abs()
+    m = max(ref.abs().max().item(), 1e-300)
+    if dt == F32:
+        return max(err.max().item() / (1e-4 * m), err.norm().item() / max(ref.norm().item(), 1e-300) / 2e-5)
+    return (err / (2.0 ** -8 * ref.abs() + 1e-3 * m)).max().item()
+
+
+def _check(got, ref, dt, what=''):
+    """_close, after printing how much of the bound the case uses."""
+    print(f'{what}: uses {_bound_use(got, ref, dt):.3f} of the {"fp32" if dt == F32 else "bf16"} bound')
+    _close(got, ref, dt, what)
 
 
 def _exact(got, ref, what=''):
@@ -149,3 +167,190 @@ def _dcn_columns(x, offset, mask):
         idx = (hh.clamp(0, h - 1) * w + ww.clamp(0, w - 1)).reshape(b, 1, 9, h * w).expand(b, c, 9, h * w)
         val = val + torch.gather(xf, 3, idx).reshape(b, c, 9, h, w) * (cf * (ok & inside)).unsqueeze(1)
     return (val * mask.unsqueeze(1)).reshape(b, c * 9, h, w)
+
+
+# ------------------------------------------------------------------------------------------------ fused forward blocks (test_block_kernels.py)
+# Restatements of the five fused bf16 kernels in plain torch on the CPU.  Every function takes the evaluation dtype `dt`: float64 is the reference,
+# float32 is what the host-only soundness tests compare with it (same rounding points, another accumulation precision).
+def _rb(t):
+    """Round to bf16 and come back: a point where the kernel stores bf16 by design."""
+    return t.to(BF16).to(t.dtype)
+
+
+def _fold(w, cb, bn):
+    """BN fold of pack_kernel / fold_kernel (conv_igemm.hip) and pw_chain_pack (mlp_chain.hip), restated in fp32 as they compute it:
+    s = gamma / sqrtf(eps + var), packed weight = bf16(w * s), bias = beta - gamma * mean / sqrtf(var + eps) (+ s * conv_bias), the bias kept in
+    fp32.  Without BN: packed weight = bf16(w), bias = conv_bias (or 0).  Returns (weights, bias) as fp64."""
+    w = w.float()
+    if bn is None:
+        return w.to(BF16).double(), (torch.zeros(w.shape[0]) if cb is None else cb.float()).double()
+    g, b, mu, var, eps = bn
+    e = torch.tensor(eps, dtype=F32)
+    s = g / torch.sqrt(e + var)
+    bo = b - g * mu / torch.sqrt(var + e)
+    if cb is not None:
+        bo = bo + s * cb
+    return (w * s.view(-1, 1, 1, 1)).to(BF16).double(), bo.double()
+
+
+class ConvP:
+    """One convolution of a case: bf16-representable weights (cout, cin, k, k), fp32 bias or None, BN tuple or None; wq / bq = _fold of them."""
+
+    def __init__(self, gen, cout, cin, k, bn=False, bias=True, gain=1.0):
+        self.k, self.cin, self.cout = k, cin, cout
+        self.w = (torch.randn(cout, cin, k, k, generator=gen) * (gain / (cin * k * k) ** 0.5)).to(BF16).float()
+        self.cb = (torch.randn(cout, generator=gen) * 0.2).float() if bias else None
+        self.bn = None
+        if bn:
+            u = lambda: torch.rand(cout, generator=gen) + 0.5
+            self.bn = (u(), torch.randn(cout, generator=gen) * 0.2, torch.randn(cout, generator=gen) * 0.2, u(), 1e-3)
+        self.wq, self.bq = _fold(self.w, self.cb, self.bn)
+
+    def dev_args(self, perm=None):
+        """(weight, conv_bias, bn) on the device, the input channels permuted by `perm` when given."""
+        w = self.w if perm is None else self.w[:, perm]
+        d = lambda t: None if t is None else t.to(DEV)
+        bn = None if self.bn is None else tuple(d(t) for t in self.bn[:4]) + (self.bn[4],)
+        return d(w.contiguous()), d(self.cb), bn
+
+    def pack(self, perm=None):
+        from mgdt_yolo_amd import ops
+        w, cb, bn = self.dev_args(perm)
+        return ops.PackedConv(w, cb, bn, self.k, BF16)
+
+    def __call__(self, x, dt):
+        import torch.nn.functional as F
+        return F.conv2d(x, self.wq.to(dt), self.bq.to(dt), 1, self.k // 2)
+
+
+def _silu(t):
+    return t * torch.sigmoid(t)
+
+
+def ref_pw_chain3(x, convs, dt=torch.float64):
+    """mgdt_pw_chain3_fwd.  x (B, 3 wd, H, W): sp0 = silu(cv0(x0)), sp_i = silu(cv_i(bf16(bf16(sp_{i-1}) + x_i))).  Rounding points read off the
+    kernel: each sp_i is rounded to bf16 when stored and the NEXT conv reads that rounded value (`prev` holds (float)(T)acc); the sum
+    sp_{i-1} + x_i is formed in fp32 and rounded to bf16 as the MFMA operand.  Returns the three sp_i BEFORE their final rounding."""
+    wd = convs[0].cout
+    xs = x.to(dt).split(wd, 1)
+    out, prev = [], None
+    for i in range(3):
+        a = xs[i] if prev is None else _rb(prev + xs[i])
+        sp = _silu(convs[i](a, dt))
+        out.append(sp)
+        prev = _rb(sp)
+    return torch.cat(out, 1)
+
+
+def ref_csp_block(mode, x, front, mids, shortcut, back, dt=torch.float64):
+    """mgdt_csp_block_fwd (mode 0 = MSPA_C2f, 1 = C2f), every conv = Conv + folded BN + SiLU with zero padding.
+      MSPA front: the pw chain above on x0..x2 -> concat slots sp0, sp1, sp2 (bf16); bottleneck input P = bf16(sp2 + x3).
+      C2f front : x = [y0 | y1] is copied to the concat, P = y1.
+      bottleneck: T = bf16(silu(cv1(P))), P' = bf16(silu(cv2(T)) (+ P with shortcut)); each P' is a concat slot.
+      back      : y = silu(cv(concat)), stored as bf16.
+    Rounding points (read off the kernel): the concat slots, P and T live in LDS as bf16 (lds_store4); the shortcut adds the bf16 P to the fp32
+    SiLU output before the one rounding of P'.  Returns y BEFORE its final rounding."""
+    x = x.to(dt)
+    wd = mids[0].cout
+    if mode == 0:
+        sp = _rb(ref_pw_chain3(x[:, :3 * wd], front, dt))
+        cat, p = [sp], _rb(sp[:, 2 * wd:] + x[:, 3 * wd:])
+    else:
+        cat, p = [x], x[:, wd:]
+    for j in range(0, len(mids), 2):
+        t = _rb(_silu(mids[j](p, dt)))
+        q = _silu(mids[j + 1](t, dt))
+        p = _rb(q + p if shortcut else q)
+        cat.append(p)
+    return _silu(back(torch.cat(cat, 1), dt))
+
+
+def inj_lerp(osz, isz):
+    """inj_lerp of inject_fused.hip for every output index, in fp32 without contraction as the kernel states it: src = max(0, (in/out) * (o + 0.5) -
+    0.5), i0 = min(int(src), in - 1), i1 = i0 + (i0 < in - 1), l1 = src - i0.  Returns (i0, i1, l1) as numpy arrays."""
+    import numpy as np
+    f = np.float32
+    o = np.arange(osz, dtype=f)
+    src = np.maximum(f(f(isz) / f(osz)) * (o + f(0.5)) - f(0.5), f(0))
+    i0 = np.minimum(src.astype(np.int64), isz - 1)
+    return i0, i0 + (i0 < isz - 1), (src - i0.astype(f)).astype(f)
+
+
+def inj_bilinear(g, H, W):
+    """F.interpolate(g, (H, W), bilinear, align_corners=False) in the association the kernel header states:
+    (v00 * lx0 + v01 * lx1) * ly0 + (v10 * lx0 + v11 * lx1) * ly1 with lx0 = 1 - lx1 formed in fp32; indices and weights from inj_lerp."""
+    import numpy as np
+    dt = g.dtype
+    y0, y1, wy = inj_lerp(H, g.shape[2])
+    x0, x1, wx = inj_lerp(W, g.shape[3])
+    y0, y1, x0, x1 = (torch.from_numpy(a) for a in (y0, y1, x0, x1))
+    t = lambda a: torch.from_numpy(a).to(dt)
+    lx1, lx0 = t(wx), t(np.float32(1) - wx)
+    ly1, ly0 = t(wy).view(-1, 1), t(np.float32(1) - wy).view(-1, 1)
+    r0, r1 = g[:, :, y0], g[:, :, y1]
+    return (r0[..., x0] * lx0 + r0[..., x1] * lx1) * ly0 + (r1[..., x0] * lx0 + r1[..., x1] * lx1) * ly1
+
+
+def inj_matrix_bf16(H, W, Hg, Wg):
+    """The GCONV form's interpolation operand: row = output pixel, column = source pixel, entry = bf16 of the fp32 sum of the tap weights
+    w00 = (1 - ly1)(1 - lx1), w01 = (1 - ly1) lx1, w10 = ly1 (1 - lx1), w11 = ly1 lx1 that fall on that source pixel (coinciding taps add up, in
+    this order).  (H W, Hg Wg) fp64 of bf16 values."""
+    import numpy as np
+    f = np.float32
+    y0, y1, wy = inj_lerp(H, Hg)
+    x0, x1, wx = inj_lerp(W, Wg)
+    M = np.zeros((H * W, Hg * Wg), dtype=f)
+    rows = np.arange(H * W)
+    for ys, xs, wyy, wxx in ((y0, x0, f(1) - wy, f(1) - wx), (y0, x1, f(1) - wy, wx), (y1, x0, wy, f(1) - wx), (y1, x1, wy, wx)):
+        s = (ys[:, None] * Wg + xs[None, :]).reshape(-1)
+        M[rows, s] = M[rows, s] + (wyy[:, None] * wxx[None, :]).astype(f).reshape(-1)
+    return torch.from_numpy(M).to(BF16).double()
+
+
+def _hsig(t):
+    return (t / 6 + 0.5).clamp(0, 1)
+
+
+def ref_inject(x, pk, ga, gf, dt=torch.float64, pkg=None, gsrc=None):
+    """mgdt_conv1x1_inject_fwd and the injection half of mgdt_conv1x1_inject_conv_fwd: loc * bilinear(h_sigmoid(ga)) + bilinear(gf) with
+    loc = bf16(conv1x1(x)) (the kernel keeps the rounding the unfused pair had) and h_sigmoid = clamp(v / 6 + 0.5, 0, 1) applied BEFORE the
+    interpolation.  With (pkg, gsrc), the GCONV form: ga | gf = bf16(conv1x1(gsrc)) over the merged panel, the gate bf16(h_sigmoid(ga)) rounded
+    once more, and the interpolation a matrix product with the bf16 tap weights of inj_matrix_bf16.  Returns the injected map unrounded."""
+    B, _, H, W = x.shape
+    loc = _rb(pk(x.to(dt), dt))
+    if pkg is None:
+        return loc * inj_bilinear(_hsig(ga.to(dt)), H, W) + inj_bilinear(gf.to(dt), H, W)
+    c = pk.cout
+    gaf = _rb(pkg(gsrc.to(dt), dt))
+    hg, gff = _rb(_hsig(gaf[:, :c])), gaf[:, c:]
+    M = inj_matrix_bf16(H, W, gsrc.shape[2], gsrc.shape[3]).to(dt)
+    ip = lambda m: torch.einsum('ps,bcs->bcp', M, m.reshape(B, c, -1)).reshape(B, c, H, W)
+    return loc * ip(hg) + ip(gff)
+
+
+def ref_inject_conv(x, pk, ga, gf, pk2, dt=torch.float64, pkg=None, gsrc=None):
+    """mgdt_conv1x1_inject_conv_fwd: silu(conv1x1_2(bf16(injected map))): the injected map is rounded to bf16 where the stored map would be
+    (it is the second MFMA's operand).  Returns the output unrounded."""
+    return _silu(pk2(_rb(ref_inject(x, pk, ga, gf, dt, pkg, gsrc)), dt))
+
+
+def ref_detect_map(tb, tc, pkb, pkc, pk3=None, dt=torch.float64):
+    """The raw head map of mgdt_detect_tail_fwd: [conv1x1(tb) | conv1x1(tc)] with bias, no activation; with pk3 the box input goes through
+    bf16(silu(conv3x3(tb))) first (Conv + BN + SiLU, zero padding; rounded like the stored map it replaces).  Unrounded."""
+    t = tb.to(dt)
+    if pk3 is not None:
+        t = _rb(_silu(pk3(t, dt)))
+    return torch.cat([pkb(t, dt), pkc(tc.to(dt), dt)], 1)
+
+
+def ref_detect_decode(feat, nc, stride, aug=None):
+    """y (B, 4 + nc, H W) in fp64 from a raw map: the DFL softmax expectation, dist2bbox and anchors of oracle.layers, x stride, sigmoid scores;
+    aug = (s, flip, img_w): xywh / s, then x = img_w - x when flipped."""
+    from oracle import layers as OL
+    y = OL.detect_decode([feat.double()], [float(stride)], 4, nc)
+    if aug is not None:
+        y = y.clone()
+        y[:, :4] = y[:, :4] / aug[0]
+        if aug[1]:
+            y[:, 0] = aug[2] - y[:, 0]
+    return y
