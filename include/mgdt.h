@@ -88,6 +88,24 @@ int mgdt_conv_pack_fp8(const float* w_oihw, const float* conv_bias, const float*
 int mgdt_conv2d_fp8_fwd(const mgdt_view* x, const mgdt_view* x2, const float* in_scale, const float* in_shift, const void* packed_w,
                         const float* bias, const float* oscale, float x_qscale, int k, int stride, int act, const mgdt_view* r1,
                         const mgdt_view* r2, const mgdt_view* y, mgdt_stream s);
+/* Host-only route query: the plan mgdt_conv2d_fwd (or, with MGDT_ROUTE_FP8, mgdt_conv2d_fp8_fwd) would launch for these views and fused extras.  It
+ * launches nothing, needs no device and never looks at a pointer (p may be NULL); sizes, strides, k, stride, dtype and act are checked as the launch
+ * checks them.  The launch and this query call the same planning functions, experiment knobs (environment) included.
+ *   flags: which optional operands are present.
+ *   family MGDT_ROUTE_IGEMM (conv_igemm_kernel<T, NT, MT, D, extra, nseg > 1>): NT cout blocks of 16 per workgroup, MT pixel groups of 16 per wave,
+ *     D = register sets of the K pipeline, nseg x seg_chunks = the staged weight panel, grid gx x gy workgroups of `waves` waves walking numTiles pixel
+ *     tiles (persistent when numTiles > gx), ragged = the last cout block is partly padding (cout % 16 != 0).
+ *   family MGDT_ROUTE_LDS3X3 (conv3x3_lds_kernel): NBW cout blocks per workgroup, tiles of tile_rows x 16 output pixels, ncg cout groups, nwg
+ *     workgroups of `waves` waves over ntiles tiles.
+ *   nchunks (K chunks of 4 pieces), waves and lds_bytes (dynamic LDS of the launch) are filled for both; the other family's fields are 0. */
+enum { MGDT_ROUTE_X2 = 1, MGDT_ROUTE_IN_SCALE = 2, MGDT_ROUTE_IN_SHIFT = 4, MGDT_ROUTE_R1 = 8, MGDT_ROUTE_R2 = 16, MGDT_ROUTE_FP8 = 32 };
+enum { MGDT_ROUTE_IGEMM = 0, MGDT_ROUTE_LDS3X3 = 1 };
+typedef struct {
+  int32_t family, nchunks, waves, lds_bytes;
+  int32_t NT, MT, D, extra, nseg, seg_chunks, gx, gy, numTiles, ragged; /* igemm */
+  int32_t NBW, tile_rows, ncg, nwg, ntiles;                             /* lds3x3 */
+} mgdt_conv_route;
+int mgdt_conv2d_route(const mgdt_view* x, const mgdt_view* y, int k, int stride, int dtype, int flags, int act, mgdt_conv_route* out);
 /* One phase (py, px) = phase >> 1, phase & 1 of the data gradient of a stride-2 3x3 convolution: dx[:, 2i+py, 2j+px] as a stride-1 convolution of dy
  * whose K holds only the taps that phase uses (packed by mgdt_conv_pack_dgrad(phase)); replaces the four 9-tap convolutions over mostly-zero weights.
  * Reference: the autograd of the stride-2 nn.Conv2d layers (backbone rows 0, 1, 3, 5, 7 of models/v8/*.yaml). */

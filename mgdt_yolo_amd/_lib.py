@@ -33,6 +33,14 @@ class WgradFinalDesc(C.Structure):            # == mgdt_wgrad_final_desc
     _fields_ = [('partial', C.c_void_p), ('dw', C.c_void_p), ('n', C.c_long), ('nsplit', C.c_int32), ('accumulate', C.c_int32)]
 
 
+class ConvRoute(C.Structure):                 # == mgdt_conv_route
+    _fields_ = [(n, C.c_int32) for n in ('family', 'nchunks', 'waves', 'lds_bytes', 'NT', 'MT', 'D', 'extra', 'nseg', 'seg_chunks', 'gx', 'gy', 'numTiles',
+                                         'ragged', 'NBW', 'tile_rows', 'ncg', 'nwg', 'ntiles')]
+
+
+ROUTE_X2, ROUTE_IN_SCALE, ROUTE_IN_SHIFT, ROUTE_R1, ROUTE_R2, ROUTE_FP8 = 1, 2, 4, 8, 16, 32
+ROUTE_IGEMM, ROUTE_LDS3X3 = 0, 1
+
 PROTOTYPES = {
     'mgdt_last_error': (C.c_char_p, []),
     'mgdt_version': (C.c_char_p, []),
@@ -42,6 +50,7 @@ PROTOTYPES = {
     'mgdt_conv_packed_bytes_fp8': (_sz, [_i, _i, _i]),
     'mgdt_conv_pack_fp8': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'mgdt_conv2d_fp8_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, VP, VP, VP, _vp]),
+    'mgdt_conv2d_route': (_i, [VP, VP, _i, _i, _i, _i, _i, C.POINTER(ConvRoute)]),
     'mgdt_conv_pack_batch': (_i, [_vp, _i, _vp]),
     'mgdt_conv2d_phase_fwd': (_i, [VP, _vp, _vp, _i, VP, VP, VP, _i, _vp]),
     'mgdt_conv_wgrad_splits': (_i, [_i, _i, _i]),

@@ -33,6 +33,9 @@ static inline bool view_nhwc(const mgdt_view* v) { return v->sc == 1; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t dtype_size(int dt) { return dt == MGDT_BF16 ? 2 : 4; }
 
+// What the host decided about one launch of the LDS-staged 3x3 kernel (mgdt_conv3x3_lds_plan in conv3x3_lds.hip; reported by mgdt_conv2d_route)
+struct C3Plan { int NBW, MT, waves, ncg, nwg, tiles_x, tiles_per_img, ntiles, XP; size_t lds; long extx, exty; };
+
 // ---- scalar load/store with conversion ----
 template <typename T> __device__ __forceinline__ float ldf(const T* p);
 template <> __device__ __forceinline__ float ldf<float>(const float* p) { return *p; }

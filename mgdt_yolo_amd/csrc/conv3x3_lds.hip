@@ -224,10 +224,9 @@ __global__ __launch_bounds__(256 * WS, 1) void conv3x3_lds_kernel(const C3Args a
   if (a.dbg && tid == 0) { unsigned long long* d = a.dbg + (size_t)blockIdx.x * 6; d[0] = T0; d[1] = tl; d[2] = Tc; d[3] = Tm; d[4] = Te; d[5] = ntl; }
 }
 
-// true when the layer is launched here (the caller returns), false: conv_igemm takes it
-bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
-                             const float* q8_oscale, float q8_xq, int stride) {
-  const bool q8 = q8_oscale != nullptr;                    // e4m3 panel from mgdt_conv_pack_fp8
+// The predicate half: true when the LDS-staged kernel takes the layer, with the plan of its launch in *p; false: conv_igemm takes it.  Looks at shapes and
+// strides only (mgdt_conv2d_route calls it without pointers).
+bool mgdt_conv3x3_lds_plan(const mgdt_view* x, const mgdt_view* y, int act, int CP, int nchunks, int NTtot, bool q8, int stride, C3Plan* p) {
   static const int mode = getenv("MGDT_CONV3_LDS") ? atoi(getenv("MGDT_CONV3_LDS")) : 1;      // experiment knob: 0 = never
   if (!mode) return false;
   static const bool ws2 = !(getenv("MGDT_C3_WAVES8") && atoi(getenv("MGDT_C3_WAVES8")) == 0);   // experiment knob: 0 = the four-wave form everywhere
@@ -236,46 +235,66 @@ bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void*
   // stride 2 - instantiated: bf16, 4 cout blocks per workgroup, Cin = 32 / 64.  Measured (B = 32, bench step): 32 -> 64 at 160 -> 80 35.9 us (igemm 38-40): default;
   // 64 -> 128 at 80 -> 40 35.4 us (igemm 34.9): only with MGDT_CONV3_LDS=3.  The 8x16-output tiles carry 72 / 144 MFMAs per wave, so a tile costs mostly its
   // staging latency and two barriers with one workgroup per CU - the LDS route wins much less here than the byte counts suggest.
-  if (stride == 2 && (q8_oscale || Cin > 64 || NTtot % 4 || (nchunks != 9 && !(nchunks == 18 && wide)))) return false;
+  if (stride == 2 && (q8 || Cin > 64 || NTtot % 4 || (nchunks != 9 && !(nchunks == 18 && wide)))) return false;
   if (Cin % 8 || Cin < 32 || Cin > 80 || Cout % 4 || Cout < 32 || (act != MGDT_ACT_SILU && act != MGDT_ACT_NONE && act != MGDT_ACT_RELU)) return false;
   const long M = (long)x->n * x->h * x->w;
   if (M < 16 * 1024 || x->h < 16 || x->w < 16) return false;                                    // small maps: the igemm kernel's finer tiles fill the chip better
-  const long extx = ((long)(x->n - 1) * x->sn + (long)(x->h - 1) * x->sh + (long)(x->w - 1) * x->sw + x->c) * 2;
-  const long exty = ((long)(y->n - 1) * y->sn + (long)(y->h - 1) * y->sh + (long)(y->w - 1) * y->sw + y->c) * 2;
-  if (extx >= 0x7fffffffL || exty >= 0x7fffffffL) return false;
-  C3Args a;
-  memset(&a, 0, sizeof(a));
-  a.x = (const char*)x->p; a.xsn = (int)(x->sn * 2); a.xsh = (int)(x->sh * 2); a.xsw = (int)(x->sw * 2); a.x_bytes = (uint32_t)extx;
-  a.y = (char*)y->p; a.ysn = (int)(y->sn * 2); a.ysh = (int)(y->sh * 2); a.ysw = (int)(y->sw * 2); a.y_bytes = (uint32_t)exty;
-  a.wpk = (const char*)packed_w; a.bias = bias;
-  a.N = x->n; a.H = x->h; a.W = x->w; a.Ho = y->h; a.Wo = y->w; a.Cin = Cin; a.Cout = Cout; a.CP = CP; a.nchunks = nchunks; a.NTtot = NTtot; a.act = act;
-  a.XP = q8 ? Cin + 16 : Cin * 2 + 16;
-  a.oscale = q8_oscale; a.xq = q8_xq;
+  p->extx = ((long)(x->n - 1) * x->sn + (long)(x->h - 1) * x->sh + (long)(x->w - 1) * x->sw + x->c) * 2;
+  p->exty = ((long)(y->n - 1) * y->sn + (long)(y->h - 1) * y->sh + (long)(y->w - 1) * y->sw + y->c) * 2;
+  if (p->extx >= 0x7fffffffL || p->exty >= 0x7fffffffL) return false;
+  p->XP = q8 ? Cin + 16 : Cin * 2 + 16;
   // every cout block in ONE workgroup (the input region is then staged once per tile); layers whose whole weight panel does not fit next to the
   // region stay on the igemm kernel: splitting the couts over workgroups re-reads the input per group and measured no faster
   const int NBW = stride == 2 ? 4 : NTtot;
   if (NBW != 2 && NBW != 3 && NBW != 4 && NBW != 5 && NBW != 6) return false;
   // (80 couts in bf16: the 8x16-tile form measured slower than the igemm kernel - 66.9 vs 55 us at 80 -> 80, 80x80, B = 32; the 12x16 form (MGDT_CONV3_LDS=3) 58.9 us; MGDT_CONV3_LDS=2 forces 8x16)
-  a.ncg = NTtot / NBW;
+  p->NBW = NBW;
+  p->ncg = NTtot / NBW;
   const size_t fixed = (((size_t)nchunks * 16 + 15) & ~(size_t)15) + (size_t)nchunks * NBW * (q8 ? 512 : 1024);
-  auto region = [&](int mt) { return stride == 2 ? (size_t)(8 * mt + 1) * 33 * a.XP : (size_t)(4 * mt + 2) * C3_RW * a.XP; };
+  auto region = [&](int mt) { return stride == 2 ? (size_t)(8 * mt + 1) * 33 * p->XP : (size_t)(4 * mt + 2) * C3_RW * p->XP; };
   int MT = stride == 2 ? 2 : 4;                            // stride 1: 16x16 tiles when the region fits next to the panel, else 12x16 (5 cout blocks), else 8x16; stride 2: 8x16
   if (stride == 1 && fixed + region(MT) > 160 * 1024) MT = NBW == 5 && !q8 && wide && fixed + region(3) <= 160 * 1024 ? 3 : 2;   // 12x16 tiles at 80 -> 80: 58.9 us vs 55 us igemm
-  const size_t lds = fixed + region(MT);
-  if (lds > 160 * 1024) return false;
+  p->lds = fixed + region(MT);
+  if (p->lds > 160 * 1024) return false;
   if (NBW == 5 && !q8 && MT == 2 && mode < 2) return false;
   if (stride == 1 && (q8 ? MT != 4 : ((NBW == 5 && MT == 4) || (NBW != 5 && MT != 4)))) return false;   // instantiated: bf16 5 blocks with 12x16 / 8x16 tiles, everything else 16x16
+  p->MT = MT;
   const int TH = 4 * MT;
-  a.tiles_x = cdiv(y->w, C3_TW);
-  a.tiles_per_img = a.tiles_x * cdiv(y->h, TH);
-  a.ntiles = x->n * a.tiles_per_img;
+  p->tiles_x = cdiv(y->w, C3_TW);
+  p->tiles_per_img = p->tiles_x * cdiv(y->h, TH);
+  p->ntiles = x->n * p->tiles_per_img;
   if ((stride == 2 ? (2 * TH + 1) * 33 * CP > 256 * 18 : (TH + 2) * C3_RW * CP > 256 * C3_MAXI)) return false;
-  a.fd_tpi = make_fastdiv((uint32_t)a.tiles_per_img); a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_cp = make_fastdiv((uint32_t)CP);
-  int nwg = 256 / a.ncg * a.ncg;                                                                // one workgroup per CU, a multiple of the cout groups (the e4m3 form's LDS
+  int nwg = 256 / p->ncg * p->ncg;                                                              // one workgroup per CU, a multiple of the cout groups (the e4m3 form's LDS
                                                                                                 // footprint would let two share a CU at 64 -> 96, its ~370 registers do not)
-  nwg = (int)std::min<long>(nwg, (long)a.ntiles * a.ncg);
-  nwg = nwg / a.ncg * a.ncg;
-  if (nwg < a.ncg) return false;
+  nwg = (int)std::min<long>(nwg, (long)p->ntiles * p->ncg);
+  nwg = nwg / p->ncg * p->ncg;
+  if (nwg < p->ncg) return false;
+  p->nwg = nwg;
+  // eight waves (two per SIMD, each wave half the cout blocks): every stride-2 form, and 4 / 6 cout blocks or 5 on 12x16 tiles at stride 1; the e4m3 forms have four
+  p->waves = q8 ? 4 : (ws2 && (stride == 2 || NBW == 6 || NBW == 4 || (NBW == 5 && MT == 3))) ? 8 : 4;
+  return true;
+}
+
+// true when the layer is launched here (the caller returns), false: conv_igemm takes it
+bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
+                             const float* q8_oscale, float q8_xq, int stride) {
+  const bool q8 = q8_oscale != nullptr;                    // e4m3 panel from mgdt_conv_pack_fp8
+  C3Plan pl;
+  if (!mgdt_conv3x3_lds_plan(x, y, act, CP, nchunks, NTtot, q8, stride, &pl)) return false;
+  const int Cin = x->c, Cout = y->c, NBW = pl.NBW, MT = pl.MT, nwg = pl.nwg;
+  const size_t lds = pl.lds;
+  const bool ws2 = pl.waves == 8;
+  C3Args a;
+  memset(&a, 0, sizeof(a));
+  a.x = (const char*)x->p; a.xsn = (int)(x->sn * 2); a.xsh = (int)(x->sh * 2); a.xsw = (int)(x->sw * 2); a.x_bytes = (uint32_t)pl.extx;
+  a.y = (char*)y->p; a.ysn = (int)(y->sn * 2); a.ysh = (int)(y->sh * 2); a.ysw = (int)(y->sw * 2); a.y_bytes = (uint32_t)pl.exty;
+  a.wpk = (const char*)packed_w; a.bias = bias;
+  a.N = x->n; a.H = x->h; a.W = x->w; a.Ho = y->h; a.Wo = y->w; a.Cin = Cin; a.Cout = Cout; a.CP = CP; a.nchunks = nchunks; a.NTtot = NTtot; a.act = act;
+  a.XP = pl.XP;
+  a.oscale = q8_oscale; a.xq = q8_xq;
+  a.ncg = pl.ncg;
+  a.tiles_x = pl.tiles_x; a.tiles_per_img = pl.tiles_per_img; a.ntiles = pl.ntiles;
+  a.fd_tpi = make_fastdiv((uint32_t)a.tiles_per_img); a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_cp = make_fastdiv((uint32_t)CP);
  #define C3_LAUNCH_Q8(NB, ACTV)                                                                                      \
   {                                                                                                                  \
     static std::atomic<bool> qattr{false}, qattr18{false}, qattr23{false};                                            \

@@ -337,27 +337,98 @@ extern "C" int mgdt_conv_pack_batch(const mgdt_pack_desc* d, int n, mgdt_stream 
   return MGDT_OK;
 }
 
+bool mgdt_conv3x3_lds_plan(const mgdt_view* x, const mgdt_view* y, int act, int CP, int nchunks, int NTtot, bool q8, int stride, C3Plan* p);   // conv3x3_lds.hip
 bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
                              const float* q8_oscale, float q8_xq, int stride);
 
 template <typename T, int NT, int MT, bool Q8>
-int launch_igemm(const ConvArgs& a, int gx, int gy, int threads, size_t lds, hipStream_t st);   // defined in conv_igemm_inst_*.hip
+int launch_igemm(const ConvArgs& a, const IgemmPlan& p, hipStream_t st);   // defined in conv_igemm_inst_*.hip
 
 template <typename T>
-static int dispatch_igemm(const ConvArgs& a, int NT, int MT, int gx, int gy, int threads, size_t lds, hipStream_t st) {
+static int dispatch_igemm(const ConvArgs& a, const IgemmPlan& p, hipStream_t st) {
+  const int NT = p.NT, MT = p.MT;
 #define CASE(nt, mt) \
-  if (NT == nt && MT == mt) return launch_igemm<T, nt, mt, false>(a, gx, gy, threads, lds, st);
+  if (NT == nt && MT == mt) return launch_igemm<T, nt, mt, false>(a, p, st);
   CASE(1, 2) CASE(1, 4) CASE(2, 2) CASE(3, 2) CASE(4, 2) CASE(5, 2) CASE(6, 2) CASE(8, 2)
 #undef CASE
   MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: no kernel for NT=%d MT=%d", NT, MT);
 }
 
-static int dispatch_igemm_q8(const ConvArgs& a, int NT, int gx, int gy, int threads, size_t lds, hipStream_t st) {
+static int dispatch_igemm_q8(const ConvArgs& a, const IgemmPlan& p, hipStream_t st) {
+  const int NT = p.NT;
 #define CASE(nt) \
-  if (NT == nt) return launch_igemm<bf16, nt, 2, true>(a, gx, gy, threads, lds, st);
+  if (NT == nt) return launch_igemm<bf16, nt, 2, true>(a, p, st);
   CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(8)
 #undef CASE
   MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d_fp8: no kernel for NT=%d", NT);
+}
+
+// ---- planning: everything the host decides about a launch from shapes, strides and flags alone.  conv2d_fwd_impl launches what these functions
+// return and mgdt_conv2d_route reports it, so the two cannot drift apart.
+// The geometric half of the argument checks (no pointers): dtype, k / stride, y's size, channel multiples, NHWC strides in whole pieces.
+static int conv_check_shapes(const mgdt_view* x, const mgdt_view* y, int k, int stride, int dtype, int* Ho_, int* Wo_) {
+  if (dtype != MGDT_F32 && dtype != MGDT_BF16) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d: dtype %d", dtype);
+  if ((k != 1 && k != 3) || (stride != 1 && stride != 2)) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: k=%d stride=%d unsupported", k, stride);
+  const int pe = piece_elems(dtype);
+  const int pad = k / 2;
+  const int Ho = (x->h + 2 * pad - k) / stride + 1, Wo = (x->w + 2 * pad - k) / stride + 1;
+  if (y->n != x->n || y->h != Ho || y->w != Wo) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: y is %dx%dx%d, expected %dx%dx%d", y->n, y->h, y->w, x->n, Ho, Wo);
+  if (x->c % pe || y->c % 4) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: cin=%d must be a multiple of %d and cout=%d of 4", x->c, pe, y->c);
+  *Ho_ = Ho; *Wo_ = Wo;
+  return MGDT_OK;
+}
+static inline bool conv_view_aligned(const mgdt_view* v, int q, int dtype) {
+  return v->sc == 1 && v->sw % q == 0 && v->sh % q == 0 && v->sn % q == 0 && ((uintptr_t)v->p % (q * dtype_size(dtype))) == 0;
+}
+// plain 3x3 bf16 layers: the only ones the LDS-staged kernel (conv3x3_lds.hip) is asked about
+static inline bool conv_lds_candidate(int tapmode, int dtype, int k, bool x2, bool in_scale, bool in_shift, bool r1, bool r2) {
+  return tapmode == 0 && dtype == MGDT_BF16 && k == 3 && !x2 && !in_scale && !in_shift && !r1 && !r2;
+}
+static int igemm_plan(int nchunks, int NTtot, long M, bool q8, bool extra, IgemmPlan* p) {
+  const int WB = q8 ? 512 : 1024;
+  // tile choice: NT = cout blocks per workgroup - as many as divide NTtot and keep the whole weight panel in LDS
+  // (activations are then read NTtot/NT times; once when NT == NTtot), fewer when the grid would starve the 256 CUs
+  int LDS_PANEL_KIB = 144;   // measured (round 2, tools/knob_sweep.sh, B = 32 bf16): 96 -> 1.377, 128 -> 1.326, 144 / 150 -> 1.312 ms per step (NT 2 -> 4 on the 128 -> 256 stride-2 conv)
+  { const char* e = getenv("MGDT_CONV_PANEL_KIB"); if (e) LDS_PANEL_KIB = atoi(e); }   // experiment knob (not part of the ABI)
+  int NT = 1;
+  for (int c : {8, 6, 5, 4, 3, 2, 1})
+    if (NTtot % c == 0 && (long)nchunks * c * WB <= LDS_PANEL_KIB * 1024L) { NT = c; break; }
+  int MT = 2;   // MT=2 with depth-4 prefetch measured faster than MT=4 on every wide layer of the target nets
+  if (!q8 && NT == 1 && NTtot == 1) { const char* e = getenv("MGDT_CONV_MT1"); MT = e && atoi(e) == 4 ? 4 : 2; }   // (MT = 8 spilled registers: removed)
+  int waves = 8;
+  auto wgs = [&](int nt, int wv) { return (long)cdiv(M, 16 * wv * MT) * (NTtot / nt); };
+  // (4-wave workgroups for small maps were tried: 8 waves measured faster on the whole net - fewer, fuller workgroups stage the weight panel less often)
+  {
+    const char* e = getenv("MGDT_CONV_MINWG");            // experiment knob (not part of the ABI)
+    const int minwg = e ? atoi(e) : 128;               // measured: 64 -> 1.800, 128 -> 1.791, 256 -> 1.811, 512 -> 1.876 ms per step
+    while (wgs(NT, waves) < minwg && NT > 1 && NT % 2 == 0) NT /= 2;    // ... and split the couts over workgroups
+  }
+  {   // a grid a few workgroups larger than what is resident at once (~3 eight-wave workgroups per CU) runs a second, almost empty round at the first one's
+      // full cost: 32 -> 512 at 40x40 (B = 32) is 800 workgroups on 768 slots.  Halving NT gives twice as many half-size workgroups: two full rounds of half the work.
+    // Measured (r02f): that layer 30.6 -> 28.1 us, but the whole step 1.294 -> 1.322 ms (the next kernels start behind a longer tail of small workgroups): off by default.
+    static const bool tail_split = getenv("MGDT_CONV_TAIL_SPLIT") != nullptr;     // experiment knob (not part of the ABI)
+    const long w0 = wgs(NT, waves);
+    if (tail_split && w0 > 768 && w0 <= 960 && NT % 2 == 0) NT /= 2;
+  }
+  {   // experiment knob (not part of the ABI)
+    const char* e;
+    if ((e = getenv("MGDT_CONV_WAVES"))) waves = std::min(8, std::max(1, atoi(e)));   // __launch_bounds__(512): at most 8 waves per workgroup
+  }
+  p->numTiles = cdiv(M, 16 * waves * MT);
+  p->T8 = cdiv(p->numTiles, 8);
+  p->tab_bytes = (nchunks + 3) / 4 * 4 * 4 * 16;   // uint4 per piece, padded to a multiple of 4 chunks (>= nchp in the kernel)
+  size_t panel = (size_t)nchunks * NT * WB;
+  if (panel <= (size_t)LDS_PANEL_KIB * 1024) { p->seg_chunks = nchunks; p->nseg = 1; }
+  else { p->seg_chunks = 64; p->nseg = cdiv(nchunks, p->seg_chunks); }   // NT == 1 here: 64 KiB segments
+  p->lds = p->tab_bytes + (size_t)(q8 ? 2 : 1) * NT * 16 * sizeof(float) + (size_t)p->seg_chunks * NT * WB;
+  int gcap = waves == 8 ? 256 : 1024;   // measured with the 144 KiB panels: 256 -> 1.293, 384 -> 1.306, 512 -> 1.312 ms per step (one persistent workgroup per CU and cout group)
+  { const char* e = getenv("MGDT_CONV_GCAP"); if (e) gcap = atoi(e); }
+  if (p->lds > 160 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: %zu bytes of LDS for NT=%d, %d chunks", p->lds, NT, p->seg_chunks);   // cannot happen with panels <= 150 KiB (table <= 9.4 KiB)
+  p->gx = std::min(8 * p->T8, gcap); p->gy = NTtot / NT;   // persistent: ~2 (8-wave) / 4 (4-wave) workgroups per CU
+  p->NT = NT; p->MT = MT; p->waves = waves;
+  p->D = nchunks >= 3 ? 4 : 2;        // pipeline depth: look-ahead D-1 <= nchunks
+  p->extra = extra;                   // second input / input affine: the EXTRA instantiations
+  return MGDT_OK;
 }
 
 static int conv2d_fwd_impl(const mgdt_view* x, const mgdt_view* x2, const float* in_scale, const float* in_shift,
@@ -389,18 +460,12 @@ static int conv2d_fwd_impl(const mgdt_view* x, const mgdt_view* x2, const float*
                            const mgdt_view* r2, const mgdt_view* y, int dtype, int tapmode, mgdt_stream s,
                            const float* q8_oscale, float q8_xq) {
   const bool q8 = q8_oscale != nullptr;
-  const int WB = q8 ? 512 : 1024;
   if (!view_ok(x) || !view_ok(y) || !packed_w || !bias) MGDT_FAIL(MGDT_BAD_ARG, "conv2d: null/empty view or weights");
-  if (dtype != MGDT_F32 && dtype != MGDT_BF16) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d: dtype %d", dtype);
-  if ((k != 1 && k != 3) || (stride != 1 && stride != 2)) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: k=%d stride=%d unsupported", k, stride);
+  int Ho, Wo;
+  if (int rc = conv_check_shapes(x, y, k, stride, dtype, &Ho, &Wo)) return rc;
   const int pe = piece_elems(dtype);
   const int pad = k / 2;
-  const int Ho = (x->h + 2 * pad - k) / stride + 1, Wo = (x->w + 2 * pad - k) / stride + 1;
-  if (y->n != x->n || y->h != Ho || y->w != Wo) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: y is %dx%dx%d, expected %dx%dx%d", y->n, y->h, y->w, x->n, Ho, Wo);
-  if (x->c % pe || y->c % 4) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: cin=%d must be a multiple of %d and cout=%d of 4", x->c, pe, y->c);
-  auto aligned = [&](const mgdt_view* v, int q) {
-    return v->sc == 1 && v->sw % q == 0 && v->sh % q == 0 && v->sn % q == 0 && ((uintptr_t)v->p % (q * dtype_size(dtype))) == 0;
-  };
+  auto aligned = [&](const mgdt_view* v, int q) { return conv_view_aligned(v, q, dtype); };
   if (!aligned(x, pe) || !aligned(y, 4)) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: x/y must be NHWC views (sc==1) with 16-byte aligned pieces");
   if (x2 && x2->p && (x2->n != x->n || x2->h != x->h || x2->w != x->w || x2->c != x->c || !aligned(x2, pe)))
     MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: x2 must match x");
@@ -440,53 +505,51 @@ static int conv2d_fwd_impl(const mgdt_view* x, const mgdt_view* x2, const float*
   a.M = (int)M; a.HoWo = Ho * Wo;
   a.fd_howo = make_fastdiv((uint32_t)a.HoWo); a.fd_wo = make_fastdiv((uint32_t)Wo);
   // plain 3x3 stride-1 bf16 layers with 32-80 input channels on large maps: the LDS-staged kernel (conv3x3_lds.hip)
-  if (tapmode == 0 && dtype == MGDT_BF16 && k == 3 && !(x2 && x2->p) && !in_scale && !in_shift && !(r1 && r1->p) && !(r2 && r2->p) &&
+  if (conv_lds_candidate(tapmode, dtype, k, x2 && x2->p, in_scale, in_shift, r1 && r1->p, r2 && r2->p) &&
       mgdt_conv3x3_lds_launch(x, y, packed_w, bias, act, a.CP, a.nchunks, a.NTtot, (hipStream_t)s, q8_oscale, q8_xq, stride)) {
     MGDT_CHECK_LAUNCH("conv2d(3x3 lds)");
     return MGDT_OK;
   }
 
-  // tile choice: NT = cout blocks per workgroup - as many as divide NTtot and keep the whole weight panel in LDS
-  // (activations are then read NTtot/NT times; once when NT == NTtot), fewer when the grid would starve the 256 CUs
-  int LDS_PANEL_KIB = 144;   // measured (round 2, tools/knob_sweep.sh, B = 32 bf16): 96 -> 1.377, 128 -> 1.326, 144 / 150 -> 1.312 ms per step (NT 2 -> 4 on the 128 -> 256 stride-2 conv)
-  { const char* e = getenv("MGDT_CONV_PANEL_KIB"); if (e) LDS_PANEL_KIB = atoi(e); }   // experiment knob (not part of the ABI)
-  int NT = 1;
-  for (int c : {8, 6, 5, 4, 3, 2, 1})
-    if (a.NTtot % c == 0 && (long)a.nchunks * c * WB <= LDS_PANEL_KIB * 1024L) { NT = c; break; }
-  int MT = 2;   // MT=2 with depth-4 prefetch measured faster than MT=4 on every wide layer of the target nets
-  if (!q8 && NT == 1 && a.NTtot == 1) { const char* e = getenv("MGDT_CONV_MT1"); MT = e && atoi(e) == 4 ? 4 : 2; }   // (MT = 8 spilled registers: removed)
-  int waves = 8;
-  auto wgs = [&](int nt, int wv) { return (long)cdiv(M, 16 * wv * MT) * (a.NTtot / nt); };
-  // (4-wave workgroups for small maps were tried: 8 waves measured faster on the whole net - fewer, fuller workgroups stage the weight panel less often)
-  {
-    const char* e = getenv("MGDT_CONV_MINWG");            // experiment knob (not part of the ABI)
-    const int minwg = e ? atoi(e) : 128;               // measured: 64 -> 1.800, 128 -> 1.791, 256 -> 1.811, 512 -> 1.876 ms per step
-    while (wgs(NT, waves) < minwg && NT > 1 && NT % 2 == 0) NT /= 2;    // ... and split the couts over workgroups
-  }
-  {   // a grid a few workgroups larger than what is resident at once (~3 eight-wave workgroups per CU) runs a second, almost empty round at the first one's
-      // full cost: 32 -> 512 at 40x40 (B = 32) is 800 workgroups on 768 slots.  Halving NT gives twice as many half-size workgroups: two full rounds of half the work.
-    // Measured (r02f): that layer 30.6 -> 28.1 us, but the whole step 1.294 -> 1.322 ms (the next kernels start behind a longer tail of small workgroups): off by default.
-    static const bool tail_split = getenv("MGDT_CONV_TAIL_SPLIT") != nullptr;     // experiment knob (not part of the ABI)
-    const long w0 = wgs(NT, waves);
-    if (tail_split && w0 > 768 && w0 <= 960 && NT % 2 == 0) NT /= 2;
-  }
-  {   // experiment knob (not part of the ABI)
-    const char* e;
-    if ((e = getenv("MGDT_CONV_WAVES"))) waves = std::min(8, std::max(1, atoi(e)));   // __launch_bounds__(512): at most 8 waves per workgroup
-  }
-  a.numTiles = cdiv(M, 16 * waves * MT);
-  a.T8 = cdiv(a.numTiles, 8);
-  a.tab_bytes = (a.nchunks + 3) / 4 * 4 * 4 * 16;   // uint4 per piece, padded to a multiple of 4 chunks (>= nchp in the kernel)
-  size_t panel = (size_t)a.nchunks * NT * WB;
-  if (panel <= (size_t)LDS_PANEL_KIB * 1024) { a.seg_chunks = a.nchunks; a.nseg = 1; }
-  else { a.seg_chunks = 64; a.nseg = cdiv(a.nchunks, a.seg_chunks); }   // NT == 1 here: 64 KiB segments
-  size_t lds = a.tab_bytes + (size_t)(q8 ? 2 : 1) * NT * 16 * sizeof(float) + (size_t)a.seg_chunks * NT * WB;
-  int gcap = waves == 8 ? 256 : 1024;   // measured with the 144 KiB panels: 256 -> 1.293, 384 -> 1.306, 512 -> 1.312 ms per step (one persistent workgroup per CU and cout group)
-  { const char* e = getenv("MGDT_CONV_GCAP"); if (e) gcap = atoi(e); }
-  if (lds > 160 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: %zu bytes of LDS for NT=%d, %d chunks", lds, NT, a.seg_chunks);   // cannot happen with panels <= 150 KiB (table <= 9.4 KiB)
-  int gx = std::min(8 * a.T8, gcap), gy = a.NTtot / NT;   // persistent: ~2 (8-wave) / 4 (4-wave) workgroups per CU
+  IgemmPlan pl;
+  if (int rc = igemm_plan(a.nchunks, a.NTtot, M, q8, a.x2 || a.in_scale || a.in_shift, &pl)) return rc;
+  a.numTiles = pl.numTiles; a.T8 = pl.T8; a.tab_bytes = pl.tab_bytes; a.seg_chunks = pl.seg_chunks; a.nseg = pl.nseg;
   hipStream_t st = (hipStream_t)s;
-  if (q8) return dispatch_igemm_q8(a, NT, gx, gy, waves * 64, lds, st);
-  if (dtype == MGDT_F32) return dispatch_igemm<float>(a, NT, MT, gx, gy, waves * 64, lds, st);
-  return dispatch_igemm<bf16>(a, NT, MT, gx, gy, waves * 64, lds, st);
+  if (q8) return dispatch_igemm_q8(a, pl, st);
+  if (dtype == MGDT_F32) return dispatch_igemm<float>(a, pl, st);
+  return dispatch_igemm<bf16>(a, pl, st);
+}
+
+// Host-only: the plan conv2d_fwd_impl would launch for these views and flags (see include/mgdt.h).  Pointers are not looked at.
+extern "C" int mgdt_conv2d_route(const mgdt_view* x, const mgdt_view* y, int k, int stride, int dtype, int flags, int act, mgdt_conv_route* out) {
+  if (!x || !y || !out || x->n <= 0 || x->h <= 0 || x->w <= 0 || x->c <= 0 || y->c <= 0) MGDT_FAIL(MGDT_BAD_ARG, "conv2d_route: null/empty view");
+  const bool q8 = flags & MGDT_ROUTE_FP8;
+  if (q8 && dtype != MGDT_BF16) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d_route: the fp8 kernels take bf16 views");
+  int Ho, Wo;
+  if (int rc = conv_check_shapes(x, y, k, stride, dtype, &Ho, &Wo)) return rc;
+  mgdt_view xv = *x, yv = *y;
+  xv.p = yv.p = nullptr;
+  if (!conv_view_aligned(&xv, piece_elems(dtype), dtype) || !conv_view_aligned(&yv, 4, dtype))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: x/y must be NHWC views (sc==1) with 16-byte aligned pieces");
+  int CP, nchunks, NTtot;
+  conv_geometry(x->c, y->c, k, dtype, &CP, &nchunks, &NTtot);
+  const long M = (long)x->n * Ho * Wo;
+  if (M > 0x7fffffffL - (1 << 20)) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: problem too large");
+  memset(out, 0, sizeof(*out));
+  out->nchunks = nchunks;
+  C3Plan c3;
+  if (conv_lds_candidate(0, dtype, k, flags & MGDT_ROUTE_X2, flags & MGDT_ROUTE_IN_SCALE, flags & MGDT_ROUTE_IN_SHIFT, flags & MGDT_ROUTE_R1, flags & MGDT_ROUTE_R2) &&
+      mgdt_conv3x3_lds_plan(&xv, &yv, act, CP, nchunks, NTtot, q8, stride, &c3)) {
+    out->family = MGDT_ROUTE_LDS3X3;
+    out->NBW = c3.NBW; out->tile_rows = 4 * c3.MT; out->ncg = c3.ncg; out->nwg = c3.nwg; out->ntiles = c3.ntiles; out->waves = c3.waves;
+    out->lds_bytes = (int)c3.lds;
+    return MGDT_OK;
+  }
+  IgemmPlan pl;
+  if (int rc = igemm_plan(nchunks, NTtot, M, q8, flags & (MGDT_ROUTE_X2 | MGDT_ROUTE_IN_SCALE | MGDT_ROUTE_IN_SHIFT), &pl)) return rc;
+  out->family = MGDT_ROUTE_IGEMM;
+  out->NT = pl.NT; out->MT = pl.MT; out->D = pl.D; out->extra = pl.extra; out->nseg = pl.nseg; out->seg_chunks = pl.seg_chunks; out->waves = pl.waves;
+  out->gx = pl.gx; out->gy = pl.gy; out->numTiles = pl.numTiles; out->lds_bytes = (int)pl.lds;
+  out->ragged = NTtot * 16 > y->c;
+  return MGDT_OK;
 }

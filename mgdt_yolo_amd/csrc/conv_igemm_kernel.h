@@ -415,8 +415,11 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(const ConvArgs a) {
   }
 }
 
+// What the host decided about one launch (igemm_plan in conv_igemm.hip): the kernel instantiation and its grid.  mgdt_conv2d_route reports the same struct.
+struct IgemmPlan { int NT, MT, D, extra, waves, gx, gy, numTiles, T8, tab_bytes, seg_chunks, nseg; size_t lds; };
+
 template <typename T, int NT, int MT, bool Q8 = false>
-int launch_igemm(const ConvArgs& a, int gx, int gy, int threads, size_t lds, hipStream_t st) {
+int launch_igemm(const ConvArgs& a, const IgemmPlan& p, hipStream_t st) {
   static std::atomic<bool> attr_set{false};  // idempotent; racing setters write the same value
   constexpr bool M1 = NT == 1;   // the segmented-panel variant exists for NT == 1 only (host never asks for it otherwise)
   const void* ks[8] = {(const void*)conv_igemm_kernel<T, NT, MT, 2, false, false, Q8>, (const void*)conv_igemm_kernel<T, NT, MT, 4, false, false, Q8>,
@@ -430,15 +433,13 @@ int launch_igemm(const ConvArgs& a, int gx, int gy, int threads, size_t lds, hip
     }
     attr_set = true;
   }
-  const int D = a.nchunks >= 3 ? 4 : 2;        // look-ahead D-1 <= nchunks
-  const bool extra = a.x2 || a.in_scale || a.in_shift;
   void* kargs[] = {(void*)&a};
-  hipError_t le = hipLaunchKernel(ks[(a.nseg > 1 ? 4 : 0) + (extra ? 2 : 0) + (D == 4 ? 1 : 0)], dim3(gx, gy), dim3(threads), kargs, lds, st);
+  hipError_t le = hipLaunchKernel(ks[(p.nseg > 1 ? 4 : 0) + (p.extra ? 2 : 0) + (p.D == 4 ? 1 : 0)], dim3(p.gx, p.gy), dim3(p.waves * 64), kargs, p.lds, st);
   if (le != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "conv2d: launch: %s", hipGetErrorString(le));
   MGDT_CHECK_LAUNCH("conv2d_fwd");
   return MGDT_OK;
 }
 
 
-#define MGDT_IGEMM_INSTANTIATE(T, nt) template int launch_igemm<T, nt, 2>(const ConvArgs&, int, int, int, size_t, hipStream_t);
-#define MGDT_IGEMM_INSTANTIATE_Q8(nt) template int launch_igemm<bf16, nt, 2, true>(const ConvArgs&, int, int, int, size_t, hipStream_t);
+#define MGDT_IGEMM_INSTANTIATE(T, nt) template int launch_igemm<T, nt, 2>(const ConvArgs&, const IgemmPlan&, hipStream_t);
+#define MGDT_IGEMM_INSTANTIATE_Q8(nt) template int launch_igemm<bf16, nt, 2, true>(const ConvArgs&, const IgemmPlan&, hipStream_t);

@@ -306,6 +306,26 @@ def conv2d(x, pk, stride, act, out=None, x2=None, r1=None, r2=None, in_scale=Non
     return out
 
 
+def conv2d_route(x, y, k, stride, dtype=None, act=ACT_SILU, x2=False, in_scale=False, in_shift=False, r1=False, r2=False, fp8=False):
+    """mgdt_conv2d_route: the plan conv2d / conv2d_fp8 would launch for the views x -> y with these fused extras, as a dict.  Launches nothing and needs
+    no device: x and y may live anywhere (CPU or meta tensors included), only their sizes and strides count.  'family' is 'igemm' (keys NT, MT, D, extra,
+    nseg, seg_chunks, waves, gx, gy, numTiles, ragged, nchunks, lds_bytes) or 'lds3x3' (NBW, tile_rows, ncg, nwg, ntiles, waves, nchunks, lds_bytes)."""
+    def shape_view(t):
+        b, c, h, w = t.shape
+        sn, sc, sh, sw = t.stride()
+        return View(None, b, h, w, c, sn, sh, sw, sc)
+    flags = sum(f for on, f in ((x2, L.ROUTE_X2), (in_scale, L.ROUTE_IN_SCALE), (in_shift, L.ROUTE_IN_SHIFT), (r1, L.ROUTE_R1), (r2, L.ROUTE_R2),
+                                (fp8, L.ROUTE_FP8)) if on)
+    r = L.ConvRoute()
+    L.check(L.lib().mgdt_conv2d_route(C.byref(shape_view(x)), C.byref(shape_view(y)), k, stride, dtype_code(dtype or x.dtype), flags, act, C.byref(r)),
+            'conv2d_route')
+    keys = (('NT', 'MT', 'D', 'extra', 'nseg', 'seg_chunks', 'gx', 'gy', 'numTiles', 'ragged') if r.family == L.ROUTE_IGEMM
+            else ('NBW', 'tile_rows', 'ncg', 'nwg', 'ntiles'))
+    out = {'family': 'igemm' if r.family == L.ROUTE_IGEMM else 'lds3x3'}
+    out.update((n, getattr(r, n)) for n in keys + ('waves', 'nchunks', 'lds_bytes'))
+    return out
+
+
 # ------------------------------------------------------------------ MSPA attention
 def spr_attention(x, fc1_w, fc1_b, fc2_w, fc2_b, groups, softmax=True):
     """softmax_over_groups(SPR(x_group)) -> attn fp32 [B, C] (softmax=False: the bare sigmoid weights)."""

@@ -1,6 +1,7 @@
-"""Shared helpers of the per-route kernel tests (test_reverse_kernels.py, test_forward_kernels.py, test_tood_kernels.py, test_block_kernels.py): seeded inputs
-already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds, the float64 deformable-conv reference
-pieces and the restatements of the fused forward block kernels.  A plain module, not a conftest."""
+"""Shared helpers of the per-route kernel tests (test_reverse_kernels.py, test_forward_kernels.py, test_tood_kernels.py, test_block_kernels.py,
+test_conv_kernels.py): seeded inputs already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds,
+the float64 deformable-conv reference pieces, the restatements of the fused forward block kernels and of the fused convolution.  A plain module, not a
+conftest."""
 import zlib
 
 import torch
@@ -177,34 +178,35 @@ def _rb(t):
     return t.to(BF16).to(t.dtype)
 
 
-def _fold(w, cb, bn):
+def _fold(w, cb, bn, dt=BF16):
     """BN fold of pack_kernel / fold_kernel (conv_igemm.hip) and pw_chain_pack (mlp_chain.hip), restated in fp32 as they compute it:
     s = gamma / sqrtf(eps + var), packed weight = bf16(w * s), bias = beta - gamma * mean / sqrtf(var + eps) (+ s * conv_bias), the bias kept in
-    fp32.  Without BN: packed weight = bf16(w), bias = conv_bias (or 0).  Returns (weights, bias) as fp64."""
+    fp32.  Without BN: packed weight = bf16(w), bias = conv_bias (or 0).  dt = F32: the fp32 panel keeps the fp32 product.  Returns (weights, bias) as fp64."""
     w = w.float()
     if bn is None:
-        return w.to(BF16).double(), (torch.zeros(w.shape[0]) if cb is None else cb.float()).double()
+        return w.to(dt).double(), (torch.zeros(w.shape[0]) if cb is None else cb.float()).double()
     g, b, mu, var, eps = bn
     e = torch.tensor(eps, dtype=F32)
     s = g / torch.sqrt(e + var)
     bo = b - g * mu / torch.sqrt(var + e)
     if cb is not None:
         bo = bo + s * cb
-    return (w * s.view(-1, 1, 1, 1)).to(BF16).double(), bo.double()
+    return (w * s.view(-1, 1, 1, 1)).to(dt).double(), bo.double()
 
 
 class ConvP:
-    """One convolution of a case: bf16-representable weights (cout, cin, k, k), fp32 bias or None, BN tuple or None; wq / bq = _fold of them."""
+    """One convolution of a case: weights (cout, cin, k, k) representable in `wrep` (bf16 by default), fp32 bias or None, BN tuple or None;
+    wq / bq = _fold of them for panels of dtype dt."""
 
-    def __init__(self, gen, cout, cin, k, bn=False, bias=True, gain=1.0):
-        self.k, self.cin, self.cout = k, cin, cout
-        self.w = (torch.randn(cout, cin, k, k, generator=gen) * (gain / (cin * k * k) ** 0.5)).to(BF16).float()
+    def __init__(self, gen, cout, cin, k, bn=False, bias=True, gain=1.0, dt=BF16, wrep=BF16):
+        self.k, self.cin, self.cout, self.dt = k, cin, cout, dt
+        self.w = (torch.randn(cout, cin, k, k, generator=gen) * (gain / (cin * k * k) ** 0.5)).to(wrep).float()
         self.cb = (torch.randn(cout, generator=gen) * 0.2).float() if bias else None
         self.bn = None
         if bn:
             u = lambda: torch.rand(cout, generator=gen) + 0.5
             self.bn = (u(), torch.randn(cout, generator=gen) * 0.2, torch.randn(cout, generator=gen) * 0.2, u(), 1e-3)
-        self.wq, self.bq = _fold(self.w, self.cb, self.bn)
+        self.wq, self.bq = _fold(self.w, self.cb, self.bn, dt)
 
     def dev_args(self, perm=None):
         """(weight, conv_bias, bn) on the device, the input channels permuted by `perm` when given."""
@@ -216,11 +218,16 @@ class ConvP:
     def pack(self, perm=None):
         from mgdt_yolo_amd import ops
         w, cb, bn = self.dev_args(perm)
-        return ops.PackedConv(w, cb, bn, self.k, BF16)
+        return ops.PackedConv(w, cb, bn, self.k, self.dt)
 
-    def __call__(self, x, dt):
+    def pack_fp8(self, xq):
+        from mgdt_yolo_amd import ops
+        w, cb, bn = self.dev_args()
+        return ops.PackedConvFp8(w, cb, bn, self.k, xq)
+
+    def __call__(self, x, dt, stride=1):
         import torch.nn.functional as F
-        return F.conv2d(x, self.wq.to(dt), self.bq.to(dt), 1, self.k // 2)
+        return F.conv2d(x, self.wq.to(dt), self.bq.to(dt), stride, self.k // 2)
 
 
 def _silu(t):
@@ -354,3 +361,70 @@ def ref_detect_decode(feat, nc, stride, aug=None):
         if aug[1]:
             y[:, 0] = aug[2] - y[:, 0]
     return y
+
+
+# ------------------------------------------------------------------------------------------------ fused convolution (test_conv_kernels.py)
+_ACTS = {'none': lambda t: t, 'silu': _silu, 'relu': torch.relu, 'gelu': lambda t: 0.5 * t * (1.0 + torch.erf(t * 0.70710678118654752))}
+
+
+def ref_conv2d(x, cp, stride, act, store, x2=None, in_scale=None, in_shift=None, r1=None, r2=None, dt=torch.float64):
+    """mgdt_conv2d_fwd:  y = act(conv((x [+ x2]) [* in_scale[n, c] + in_shift[c]]) + bias) [+ r1] [+ r2], zero padding k // 2, cp = ConvP.
+    Rounding points read off conv_igemm_kernel (load_chunk): with bf16 views (`store` = BF16) the sum x + x2 is formed in fp32 and rounded to bf16
+    (frag_add), and the affine result is rounded to bf16 once more (frag_affine) - it is the MFMA operand; padding pixels stay zero (the affine is
+    applied to in-image taps only).  With fp32 views nothing is rounded.  Returns y BEFORE its final rounding."""
+    rnd = _rb if store == BF16 else (lambda t: t)
+    a = x.to(dt)
+    if x2 is not None:
+        a = rnd(a + x2.to(dt))
+    if in_scale is not None or in_shift is not None:
+        if in_scale is not None:
+            a = a * in_scale.to(dt)[:, :, None, None]
+        if in_shift is not None:
+            a = a + in_shift.to(dt)[None, :, None, None]
+        a = rnd(a)
+    y = _ACTS[act](cp(a, dt, stride))
+    for r in (r1, r2):
+        if r is not None:
+            y = y + r.to(dt)
+    return y
+
+
+def _e4m3(t):
+    """OCP e4m3fn quantisation as the gfx950 conversion does it: round to nearest even after clamping to the finite range (+-448)."""
+    return t.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
+
+
+def ref_conv2d_fp8(x, cp, stride, act, xq, x2=None, r1=None, r2=None):
+    """mgdt_conv2d_fp8_fwd as test_conv_fp8_matches_e4m3_emulation states it: BN folded in fp32, per-output-channel weight scale ws = max|w'| / 448,
+    panel = e4m3(w' / ws), activations e4m3(bf16(x [+ x2]) * xq) with the product formed in fp32, the exact product sum times ws / xq plus the
+    fp32 bias, activation, residuals.  Float64 from the quantised operands on.
+    The master weights of an fp8 case are plain fp32 values (ConvP(wrep=F32)), as in that test: w' / ws of bf16-representable weights is a ratio of
+    8-bit integers times 448 and lands EXACTLY on e4m3 rounding ties (19/28 * 448 = 304, between 288 and 320) for a few weights of most channels;
+    with a BN fold the fp32 values on either side of such a tie are one ulp apart and the device's 1-ulp sqrtf / division decides them the other
+    way (measured: 25 of 36 864 panel bytes of a 64 -> 64 3x3 layer one e4m3 step off, output error 1.006 of the bound at one pixel).  Both
+    are correct quantisations; generic fp32 weights do not sit on ties."""
+    import torch.nn.functional as F
+    w = cp.w.float()
+    if cp.bn is not None:
+        g, _, _, var, eps = cp.bn
+        w = w * (g / torch.sqrt(torch.tensor(eps, dtype=F32) + var)).view(-1, 1, 1, 1)
+    ws = w.abs().amax(dim=(1, 2, 3)) / 448.0
+    wq = _e4m3(w / ws[:, None, None, None])
+    a = x.float()
+    if x2 is not None:
+        a = (a + x2.float()).to(BF16).float()
+    acc = F.conv2d(_e4m3(a * xq).double(), wq.double(), None, stride, cp.k // 2) * (ws / xq).double()[None, :, None, None] + cp.bq[None, :, None, None]
+    y = _ACTS[act](acc)
+    for r in (r1, r2):
+        if r is not None:
+            y = y + r.double()
+    return y
+
+
+def _check_fp8(got, ref, what=''):
+    """The bound of test_conv_fp8_matches_e4m3_emulation: max |got - ref| < 8e-3 * max(1, max|ref|); prints how much of it the case uses."""
+    got = got.detach().double().cpu().reshape(ref.shape)
+    assert torch.isfinite(got).all(), (what, 'non-finite output')
+    err = (got - ref).abs().max().item() / max(1.0, ref.abs().max().item())
+    print(f'{what}: uses {err / 8e-3:.3f} of the fp8 bound')
+    assert err < 8e-3, (what, err)
