@@ -403,6 +403,21 @@ int mgdt_gt_masks_resample_fwd(const uint8_t* gt, int gt_index_map, const int32_
 int mgdt_val_match_iou_fwd(const float* iou, int n, int max_lab, int max_det, const float* det_cls, int det_stride, const int32_t* ndet,
                            const float* lab_cls, int lab_stride, const int32_t* nlab, const float* iouv, int n_iou, uint8_t* correct, mgdt_stream s);
 
+/* ---- pose validation (reference yolo/utils/metrics.py:150-169 kpt_iou, yolo/v8/pose/val.py:110-141) ------------------------------------
+ * kpt_iou: oks [n][max_lab][max_det] fp32, the object keypoint similarity of every (label, detection) pair of a batch in one launch, laid out like
+ *   mgdt_mask_iou_fwd's matrix (mgdt_val_match_iou_fwd consumes it unchanged).  pred: keypoint 0 of detection 0 of image 0; detection d of image i
+ *   starts (i * max_det + d) * pred_stride floats further and holds nkpt keypoints of pred_ndim (2 or 3) floats [x, y(, visibility)]: for the rows
+ *   [n][max_det][6 + nk] of mgdt_nms_masks_fwd pass rows + 6 and 6 + nk, for a dense [n][max_det][nkpt][pred_ndim] tensor nkpt * pred_ndim.  Only the
+ *   keypoint floats of the first min(counts[i], max_det) detections are read.  gt_kpts fp32 [n][max_lab][nkpt][3] (x, y, visibility; zero-padded),
+ *   area fp32 [n][max_lab], nlab int32 [n], sigma fp32 [nkpt].  With d = dx^2 + dy^2 of label and detection keypoint k (each operation rounded):
+ *   oks = sum_k exp(-d / (2 sigma_k)^2 / (area + eps) / 2) [vis_k != 0] / (sum_k [vis_k != 0] + eps), computed as exp(-d * coef) with
+ *   coef = 1 / ((2 sigma_k)^2 (area + eps) 2) and multiplied by 1 / (count + eps).  A label without a visible keypoint gives 0; a zero-area label gives
+ *   no NaN for eps > 0 (0 where d > 0, a term of 1 where d = 0).  Entries with label >= nlab[i] or detection >= counts[i] are WRITTEN as 0.
+ *   Limits (MGDT_BAD_SHAPE before any launch): n <= 65535, max_det <= 1024, max_lab <= 256, nkpt <= 120, pred_ndim in {2, 3},
+ *   nkpt * pred_ndim <= pred_stride <= 2^20, n * max_lab * max_det < 2^31. */
+int mgdt_kpt_iou_fwd(const float* pred, int pred_stride, int pred_ndim, const int32_t* counts, int n, int max_det, const float* gt_kpts,
+                     const float* area, const int32_t* nlab, int max_lab, int nkpt, const float* sigma, float eps, float* oks, mgdt_stream s);
+
 /* ---- validator matching: DetectionValidator._process_batch, yolo/v8/detect/val.py:152-175, for a batch ----------
  * det [n][max_det][6] (x1,y1,x2,y2,conf,cls; the layout mgdt_nms_fwd writes) with ndet[n] valid rows, labels [n][max_lab][5]
  * (cls,x1,y1,x2,y2 in the same pixel frame) with nlab[n] valid rows, iouv[n_iou] ascending IoU levels (n_iou <= 16).

@@ -169,6 +169,7 @@ PROTOTYPES = {
     'mgdt_mask_iou_fwd': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _sz, _vp]),
     'mgdt_gt_masks_resample_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mgdt_val_match_iou_fwd': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    'mgdt_kpt_iou_fwd': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _vp]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define MGDT_WAVE 64
+#define POSE_MAX_NK 240            // keypoint values of one detection (pose.hip's LDS tile: nk * 65 * 4 bytes <= 62.4 KB; poseval.hip takes nkpt <= POSE_MAX_NK / 2)
 
 // ---- error plumbing (thread-local text, int status across the C boundary) ----
 void mgdt_set_error(const char* fmt, ...);

@@ -16,7 +16,6 @@
 #define POSE_MAX_LEVELS 4
 #define POSE_TA 64                 // anchors per workgroup
 #define POSE_SROW (POSE_TA + 1)    // LDS row stride (floats): odd, so the channel-major phase-1 writes spread over the banks
-#define POSE_MAX_NK 240            // LDS: nk * 65 * 4 bytes <= 62.4 KB
 
 struct PoseCatArgs {
   const float* y; float* out; float* raw;

@@ -1234,6 +1234,51 @@ def val_match_iou(iou, det_rows, ndet, labels, nlab, iouv):
     return correct.view(torch.bool)
 
 
+# ------------------------------------------------------------------ pose validation (object keypoint similarity)
+KPT_IOU_MAX_DET, KPT_IOU_MAX_LAB, KPT_IOU_MAX_NKPT = 1024, 256, 120
+
+
+def kpt_iou_batch(pred, counts_dev, max_det, gt_kpts, area, nlab, sigma, eps=1e-7, out=None):
+    """mgdt_kpt_iou_fwd: pred the padded NMS rows (B, max_det, 6 + nkpt * ndim) fp32 of `nms_masks` (keypoints read in place behind the six
+    detection columns) or a dense (B, max_det, nkpt, ndim) fp32 tensor, ndim 2 or 3, + counts_dev (B,) int32; gt_kpts (B, max_lab, nkpt, 3) fp32
+    [x, y, visibility] zero-padded, area (B, max_lab) fp32, nlab (B,) int32, sigma (nkpt,) fp32 on the device -> oks (B, max_lab, max_det)
+    float32, zero past nlab[i] / counts[i] (the layout `val_match_iou` takes).  `out`: a caller's buffer (tests: guards)."""
+    _need_gpu(pred)
+    _need_gpu(gt_kpts)
+    b = counts_dev.numel()
+    if gt_kpts.dtype != torch.float32 or gt_kpts.dim() != 4 or gt_kpts.shape[0] != b or gt_kpts.shape[3] != 3 or not gt_kpts.is_contiguous():
+        raise RuntimeError(f'kpt_iou: label keypoints are a contiguous float32 (B={b}, max_lab, nkpt, 3) tensor, got {tuple(gt_kpts.shape)} {gt_kpts.dtype}')
+    max_lab, nkpt = gt_kpts.shape[1], gt_kpts.shape[2]
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() not in (3, 4) or pred.shape[0] != b or pred.shape[1] != max_det:
+        raise RuntimeError(f'kpt_iou: predictions are a contiguous float32 (B={b}, max_det={max_det}, 6 + nk) or (B, max_det, nkpt, ndim) tensor, got '
+                           f'{tuple(pred.shape)} {pred.dtype}')
+    if pred.dim() == 4:
+        lead, stride, ndim, ok = 0, pred.shape[2] * pred.shape[3], pred.shape[3], pred.shape[2] == nkpt
+    else:
+        lead, stride = 6, pred.shape[2]
+        ndim, ok = (stride - 6) // max(nkpt, 1), nkpt > 0 and stride > 6 and (stride - 6) % nkpt == 0
+    if not ok or ndim not in (2, 3):
+        raise RuntimeError(f'kpt_iou: predictions {tuple(pred.shape)} do not hold nkpt={nkpt} keypoints of 2 or 3 values')
+    if area.dtype != torch.float32 or tuple(area.shape) != (b, max_lab) or not area.is_contiguous():
+        raise RuntimeError(f'kpt_iou: area must be a contiguous float32 (B={b}, max_lab={max_lab}) tensor, got {tuple(area.shape)} {area.dtype}')
+    if not torch.is_tensor(sigma) or sigma.dtype != torch.float32 or sigma.numel() != nkpt or not sigma.is_contiguous():
+        raise RuntimeError(f'kpt_iou: sigma must be a contiguous float32 tensor of nkpt={nkpt} values on the device')
+    _need_gpu(area)
+    _need_gpu(sigma)
+    _i32(counts_dev, b, 'kpt_iou: counts')
+    _i32(nlab, b, 'kpt_iou: nlab')
+    if out is None:
+        out = torch.empty(b, max_lab, max_det, dtype=torch.float32, device=pred.device)
+    elif out.dtype != torch.float32 or out.numel() < b * max_lab * max_det or not out.is_contiguous():
+        raise RuntimeError('kpt_iou: `out` must be a contiguous float32 buffer of B x max_lab x max_det elements')
+    if _PROF is not None:
+        _META['kpt_iou_fwd'] = dict(shape=(b, max_lab, max_det, nkpt, ndim), flops=8.0 * b * max_lab * max_det * nkpt,
+                                    bytes=float(4 * (b * max_det * nkpt * ndim + gt_kpts.numel() + b * max_lab * max_det)))
+    _launch('kpt_iou_fwd', 'mgdt_kpt_iou_fwd', C.c_void_p(pred.data_ptr() + 4 * lead), stride, ndim, ptr(counts_dev), b, max_det, ptr(gt_kpts), ptr(area),
+            ptr(nlab), max_lab, nkpt, ptr(sigma), float(eps), ptr(out), stream())
+    return out
+
+
 # ------------------------------------------------------------------ detection loss (assigner + BCE/CIoU/DFL)
 def _view_array(ts):
     views = [view(t) for t in ts]

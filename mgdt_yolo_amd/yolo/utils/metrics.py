@@ -1,6 +1,7 @@
-"""Box and mask overlap functions and the validator's AP reduction with the reference's names (reference: yolo/utils/metrics.py).
+"""Box, mask and keypoint overlap functions and the validator's AP reduction with the reference's names (reference: yolo/utils/metrics.py).
 
-`box_iou`, `bbox_iou` (IoU / GIoU / DIoU / CIoU, forward values) and `mask_iou` run as HIP kernels (mgdt_box_iou / mgdt_bbox_iou / mgdt_mask_iou_fwd).  `ap_per_class` keeps
+`box_iou`, `bbox_iou` (IoU / GIoU / DIoU / CIoU, forward values), `mask_iou` and `kpt_iou` run as HIP kernels (mgdt_box_iou / mgdt_bbox_iou /
+mgdt_mask_iou_fwd / mgdt_kpt_iou_fwd).  `ap_per_class` keeps
 the reference's signature and return tuple: the O(detections) part - per-class cumulative TP / FP, recall / precision curves, compute_ap's
 envelope, 101-point interpolation and integration, the 1000-point P / R-vs-confidence curves - runs on the device in fp64 with numpy's own
 arithmetic order (mgdt_ap_per_class: the AP matrix equals the reference's bit for bit); grouping the detections by (class, confidence) is a
@@ -10,6 +11,8 @@ import torch
 
 from ... import _lib as L
 from ... import ops as hip
+
+OKS_SIGMA = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0     # the COCO keypoint constants (metrics.py:15)
 
 
 def box_iou(box1, box2, eps=1e-7):
@@ -64,6 +67,34 @@ def mask_iou(mask1, mask2, eps=1e-7):
             b = m2[j:j + hip.MASK_IOU_MAX_DET]
             out[i:i + a.shape[0], j:j + b.shape[0]] = hip.mask_iou_batch(b.view(-1, 1, n), cnt(b.shape[0]), zero, b.shape[0], a.view(-1, 1, n),
                                                                          cnt(a.shape[0]), a.shape[0], index_map=False, lab_offsets=zero, eps=eps)[0]
+    return out
+
+
+def kpt_iou(kpt1, kpt2, area, sigma, eps=1e-7):
+    """Object keypoint similarity: kpt1 (N, nkpt, 3) ground truth [x, y, visibility], kpt2 (M, nkpt, 2 | 3) predictions, area (N,) of the ground
+    truth, sigma nkpt keypoint scales (list / numpy / tensor) -> (N, M) float32 (metrics.py:150-169), one mgdt_kpt_iou_fwd launch.  More rows than
+    the kernel's limits (256 / 1024) are processed in blocks."""
+    hip._need_gpu(kpt1)
+    hip._need_gpu(kpt2)
+    if kpt1.dim() != 3 or kpt2.dim() != 3 or kpt1.shape[2] != 3 or kpt2.shape[2] not in (2, 3) or kpt1.shape[1] != kpt2.shape[1]:
+        raise RuntimeError(f'kpt_iou: (N, nkpt, 3) labels and (M, nkpt, 2 | 3) predictions expected, got {tuple(kpt1.shape)} and {tuple(kpt2.shape)}')
+    dev = kpt1.device
+    g, p = kpt1.float().contiguous(), kpt2.float().contiguous()
+    a = (area if torch.is_tensor(area) else torch.as_tensor(np.asarray(area))).to(dev).float().contiguous().view(-1)
+    sg = (sigma if torch.is_tensor(sigma) else torch.as_tensor(np.asarray(sigma, dtype=np.float32))).to(dev).float().contiguous().view(-1)
+    N, M, nkpt = g.shape[0], p.shape[0], g.shape[1]
+    if a.numel() != N or sg.numel() != nkpt:
+        raise RuntimeError(f'kpt_iou: {a.numel()} areas for {N} labels, {sg.numel()} sigmas for {nkpt} keypoints')
+    out = torch.zeros(N, M, dtype=torch.float32, device=dev)
+    if N == 0 or M == 0 or nkpt == 0:
+        return out
+    cnt = lambda k: torch.full((1,), k, dtype=torch.int32, device=dev)
+    for i in range(0, N, hip.KPT_IOU_MAX_LAB):
+        gi, ai = g[i:i + hip.KPT_IOU_MAX_LAB], a[i:i + hip.KPT_IOU_MAX_LAB]
+        for j in range(0, M, hip.KPT_IOU_MAX_DET):
+            pj = p[j:j + hip.KPT_IOU_MAX_DET]
+            out[i:i + gi.shape[0], j:j + pj.shape[0]] = hip.kpt_iou_batch(pj[None], cnt(pj.shape[0]), pj.shape[0], gi[None], ai[None], cnt(gi.shape[0]), sg,
+                                                                        eps=eps)[0]
     return out
 
 
