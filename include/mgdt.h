@@ -565,6 +565,28 @@ int mgdt_tood_layer_attn_bwd(const float* sums, const float* dscale, int n, int 
 int mgdt_dcn_im2col(const mgdt_view* x, const mgdt_view* om, const mgdt_view* col, int dtype, mgdt_stream s);
 int mgdt_dcn_col2im_bwd(const mgdt_view* gcol, const mgdt_view* x, const mgdt_view* om, float* gx_f32, const mgdt_view* gom, int dtype, mgdt_stream s);
 
+/* ---- image classification (nn/modules/head.py:256-272 Classify, yolo/utils/loss.py:395-401, yolo/utils/metrics.py:197-207, :934-977) ----
+ * mgdt_classify_pool_fwd: pooled[n][cout] (fp32) = mean over the pixels of SiLU(conv1x1(x, w) + bias): Classify.conv (BatchNorm folded by the caller
+ *   into w [cout][c1] in `dtype`, row-major, and bias fp32[cout]) + AdaptiveAvgPool2d(1) in one launch on the matrix cores; the (n, cout, h, w) map is
+ *   never stored.  Bit-reproducible (no floating-point atomics).  Refused before any launch: k != 1, groups != 1, act != MGDT_ACT_SILU (MGDT_BAD_ARG:
+ *   those go through the unfused chain), x not NHWC, c1 % 8, cout % 16, pixel rows or w not 16-byte aligned, n > 65535.
+ * mgdt_classify_linear_fwd: logits[n][nc] = pooled[n][k] @ w[nc][k]^T + bias (w in `dtype`, pooled / bias / logits fp32, fp32 accumulation; bias may
+ *   be NULL); probs != NULL: the row softmax as well (a second launch).  k % 4 == 0, any nc >= 1.
+ * mgdt_cls_softmax_fwd: probs = softmax(logits, dim 1), the row maximum subtracted; in place allowed.
+ * mgdt_cls_loss_fwd: loss[0] = cross_entropy(logits, labels, reduction='sum') / 64 (the reference's constant, not the batch size); row_loss[n] is a
+ *   caller-owned buffer that receives the per-row terms.  mgdt_cls_loss_bwd: dlogits = (softmax - onehot) / 64 * gscale.  labels: int64 on the
+ *   device; a label outside [0, nc) gives a NaN loss and a zero gradient row, and nothing is read out of bounds.
+ * mgdt_cls_topk_fwd: topk[n][min(nc, 5)] (int64) = indices of the largest values of each row of probs[n][nc], descending, equal values by lower
+ *   index first.  matrix != NULL (int32 [nc][nc], accumulated: zero it first): matrix[topk[i][0]][targets[i]] += 1 (integer atomics). */
+int mgdt_classify_pool_fwd(const mgdt_view* x, const void* w, const float* bias, int cout, int k, int groups, int act, float* pooled, int dtype,
+                           mgdt_stream s);
+int mgdt_classify_linear_fwd(const float* pooled, const void* w, const float* bias, int n, int k, int nc, float* logits, float* probs, int dtype,
+                             mgdt_stream s);
+int mgdt_cls_softmax_fwd(const float* logits, int n, int nc, float* probs, mgdt_stream s);
+int mgdt_cls_loss_fwd(const float* logits, const int64_t* labels, int n, int nc, float* row_loss, float* loss, mgdt_stream s);
+int mgdt_cls_loss_bwd(const float* logits, const int64_t* labels, int n, int nc, float gscale, float* dlogits, mgdt_stream s);
+int mgdt_cls_topk_fwd(const float* probs, int n, int nc, int64_t* topk, const int64_t* targets, int32_t* matrix, mgdt_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,9 +103,22 @@ POSE_CONFIGS = {
 }
 
 
+# [depth, width, max_channels] of models/v8/yolov8-cls.yaml: every scale keeps max_channels 1024 (the detection YAMLs cut m / l / x)
+CLS_SCALES = {'n': [0.33, 0.25, 1024], 's': [0.33, 0.50, 1024], 'm': [0.67, 0.75, 1024], 'l': [1.00, 1.00, 1024], 'x': [1.00, 1.25, 1024]}
+
+
+def _cls_cfg(nc):
+    """models/v8/yolov8-cls.yaml: the yolov8 backbone without SPPF, then Classify [nc]."""
+    return {'nc': nc, 'scales': deepcopy(CLS_SCALES), 'backbone': _backbone('C2f')[:-1], 'head': [[-1, 1, 'Classify', ['nc']]]}
+
+
+# image-classification graph: the reference's models/v8/yolov8-cls.yaml (nc 1000)
+CLS_CONFIGS = {'yolov8-cls': lambda nc=1000: _cls_cfg(nc)}
+
+
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
-    table = CONFIGS if name in CONFIGS else SEG_CONFIGS if name in SEG_CONFIGS else POSE_CONFIGS
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    table = CONFIGS if name in CONFIGS else SEG_CONFIGS if name in SEG_CONFIGS else CLS_CONFIGS if name in CLS_CONFIGS else POSE_CONFIGS
     d = table[name]() if nc is None else table[name](nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale
     d['yaml_file'] = f'{name}.yaml'

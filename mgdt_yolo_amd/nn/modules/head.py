@@ -14,7 +14,7 @@ from ... import ops
 from .block import DFL, Proto
 from .conv import Conv, HipModule
 
-__all__ = ('Detect', 'Segment', 'Pose', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
+__all__ = ('Detect', 'Segment', 'Pose', 'Classify', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
 
 
 class _HeadConv(HipModule):
@@ -329,6 +329,117 @@ class Pose(Detect):
 
     def backward(self, grads):
         raise NotImplementedError(POSE_TRAIN_MSG)
+
+
+class Classify(HipModule):
+    """YOLOv8 classification head (reference head.py:256-272): x (b, c1, h, w) -> (b, c2).  `conv` (Conv c1 -> 1280), `pool`, `drop` (p = 0: the
+    identity) and `linear` carry the reference's names, so state_dict keys and shapes match.  Eval returns the softmax (b, c2) fp32 in two launches:
+    mgdt_classify_pool_fwd (conv + BatchNorm + SiLU + spatial mean, the 1280-channel map never stored) and mgdt_classify_linear_fwd (+ softmax);
+    where the fused kernel does not apply (k != 1, groups, another activation, hooks, ops.FUSED_CLS_HEAD off) the unfused chain runs: Conv.forward,
+    adaptive_avgpool, the linear as a 1x1 convolution on the (b, 1280, 1, 1) map, the softmax kernel.  Train returns the raw logits (b, c2) fp32
+    through the unfused chain (batch-statistics BatchNorm in Conv.train_fwd) and keeps the context of `backward`."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1):
+        super().__init__()
+        c_ = 1280                                             # efficientnet_b0 size
+        self.conv = Conv(c1, c_, k, s, p, g)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.drop = nn.Dropout(p=0.0, inplace=True)
+        self.linear = nn.Linear(c_, c2)
+
+    def q8_site(self, key, x, x2=None):
+        return None                                           # fp8 for the Classify head is not built
+
+    def _fusable(self, x, dt):
+        c = self.conv
+        if self.training or c._forward_hooks or self.pool._forward_hooks or not c.plain_affine() or not isinstance(c.act, nn.SiLU):
+            return False
+        cv = c.conv
+        return (cv.stride == (1, 1) and cv.padding == (0, 0) and cv.dilation == (1, 1) and cv.kernel_size == (1, 1)
+                and ops.classify_pool_supported(x, cv.in_channels, cv.out_channels, 1, cv.groups, ops.ACT_SILU, dt))
+
+    def _pool_panel(self, dt):
+        c = self.conv
+
+        def build():
+            if hasattr(c, 'bn'):
+                from ...yolo.utils.torch_utils import fuse_conv_and_bn
+                f = fuse_conv_and_bn(c.conv, c.bn)            # the arithmetic of BaseModel.fuse(): the panel is bit-equal before and after it
+                return ops.PackedClsPool(f.weight, f.bias, dt)
+            return ops.PackedClsPool(c.conv.weight, c.conv.bias, dt)
+        return self._cached(('clspool', dt), c.affine_tensors(), build)
+
+    def _linear_map(self, pm, dt):
+        """the linear as a 1x1 convolution on the (b, 1280, 1, 1) map -> (b, nc, 1, 1); class counts the MFMA kernel does not take go the direct way"""
+        lin, nc = self.linear, self.linear.out_features
+        out = ops.new_act(pm.shape[0], nc, 1, 1, dt, pm.device)
+        mfma = nc % 4 == 0 and ops.conv_can_mfma(pm, lin.in_features, nc, 1, 1, 1, dt)
+        pk = self._cached(('lin1x1', dt, mfma), [lin.weight, lin.bias],
+                          lambda: ops.PackedConv(lin.weight.reshape(nc, lin.in_features, 1, 1), lin.bias, None, 1, dt, direct=not mfma))
+        return ops.conv2d(pm, pk, 1, ops.ACT_NONE, out=out)
+
+    @staticmethod
+    def _rows_f32(m):
+        """(b, c, 1, 1) map -> contiguous (b, c) fp32"""
+        b, c = m.shape[:2]
+        if m.dtype == torch.float32:
+            return m.reshape(b, c)
+        out = torch.empty(b, c, 1, 1, dtype=torch.float32, device=m.device)
+        return ops.copy(m, out).reshape(b, c)
+
+    def forward(self, x):
+        if isinstance(x, list):
+            self._split = [t.shape[1] for t in x]
+            b, _, h, w = x[0].shape
+            cat = ops.new_act(b, sum(self._split), h, w, x[0].dtype, x[0].device)
+            c0 = 0
+            for t in x:
+                ops.copy(t, cat[:, c0:c0 + t.shape[1]])
+                c0 += t.shape[1]
+            x = cat
+        else:
+            self._split = None
+        dt = self.conv.out_dtype(x)
+        if self._fusable(x, dt):
+            lin = self.linear
+            wl = self._cached(('lin', dt), [lin.weight], lambda: lin.weight.detach().to(dt).contiguous())
+            bl = self._cached(('linb',), [lin.bias], lambda: None if lin.bias is None else lin.bias.detach().float().contiguous())
+            return ops.classify_linear(ops.classify_pool(x, self._pool_panel(dt)), wl, bl, softmax=True)[1]
+        z = self.conv(x)                                      # eval: folded BN; train: batch statistics + context
+        pm = ops.adaptive_avgpool(z, ops.new_act(z.shape[0], z.shape[1], 1, 1, z.dtype, z.device))
+        logits = self._rows_f32(self._linear_map(pm, z.dtype))
+        if self.training:
+            self._save_ctx((pm, tuple(z.shape)))
+            return logits
+        return ops.cls_softmax(logits)
+
+    def backward(self, g):
+        """g: d loss / d logits (b, nc).  Fills .grad of linear.weight / linear.bias and of `conv`; returns the gradient of the head's input (a list
+        of channel slices for a list input)."""
+        if isinstance(g, (list, tuple)):
+            g = g[0]
+        pm, zshape = self._ctx.pop()
+        lin, nc = self.linear, self.linear.out_features
+        b = pm.shape[0]
+        gm = ops.new_act(b, nc, 1, 1, pm.dtype, pm.device)
+        ops.copy(g.reshape(b, nc, 1, 1), gm)
+        xw = pm
+        if (nc % 4 or pm.shape[1] % 4) and pm.dtype != torch.float32:          # the generic weight-gradient kernel reads its input as fp32
+            xw = ops.copy(pm, ops.new_act(b, pm.shape[1], 1, 1, torch.float32, pm.device))
+        ops.grad_buf(lin.weight)
+        if lin.bias is not None:
+            ops.grad_buf(lin.bias)
+        ops.conv_wgrad(xw, gm, 1, 1, lin.weight.grad, dbias=None if lin.bias is None else lin.bias.grad)
+        dp = ops.conv_dgrad(gm, lin.weight, 1, 1, ops.new_act(b, pm.shape[1], 1, 1, pm.dtype, pm.device))
+        gz = ops.adaptive_avgpool_bwd(dp, ops.new_act(*zshape, pm.dtype, pm.device))
+        gx = self.conv.backward(gz)
+        if self._split is None:
+            return gx
+        out, c0 = [], 0
+        for c in self._split:
+            out.append(gx[:, c0:c0 + c])
+            c0 += c
+        return out
 
 
 # ====================================================================================================================

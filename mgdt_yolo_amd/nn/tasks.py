@@ -18,12 +18,12 @@ import torch.nn as nn
 
 from .. import ops
 from ..yolo.utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts, make_divisible
-from .modules import (C2f, IFM, MSPA_C2f, SPPF, Bottleneck, Concat, Conv, Detect, DWConv, InjectionMultiSum_Auto_pool,
+from .modules import (C2f, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, Detect, DWConv, InjectionMultiSum_Auto_pool,
                       Pose, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
 
 # names a YAML row may use -> class (the reference resolves them with globals()[m] / getattr(torch.nn, ...), tasks.py:630)
 REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, MSPA_C2f, SPPF, SimFusion_4in, SimFusion_3in, IFM,
-                                    InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose)}
+                                    InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose, Classify)}
 REGISTRY['nn.Upsample'] = Upsample
 
 
@@ -41,13 +41,19 @@ class _TrainForwardFn(torch.autograd.Function):
         with ops.force_ctx():
             feats = model._predict_once(x)
         ctx.model = model
+        ctx.single = torch.is_tensor(feats)             # a classification head: one (B, nc) logits tensor instead of a list of maps
+        if ctx.single:
+            return feats
         ctx.n = len(feats)
         return tuple(feats)
 
     @staticmethod
     def backward(ctx, *gfeats):
         model = ctx.model
-        gfeats = [g if g.is_contiguous(memory_format=torch.channels_last) else g.contiguous(memory_format=torch.channels_last) for g in gfeats]
+        if ctx.single:
+            gfeats = gfeats[0].contiguous()
+        else:
+            gfeats = [g if g.is_contiguous(memory_format=torch.channels_last) else g.contiguous(memory_format=torch.channels_last) for g in gfeats]
         acc = model._accumulate_snapshot() if getattr(model, 'grad_accumulate', False) else None
         model.backward(gfeats)
         if acc is not None:
@@ -74,7 +80,8 @@ class BaseModel(nn.Module):
             # training call form of the reference: the outputs carry a grad_fn, `loss.backward()` runs the HIP reverse pass
             if not hasattr(self, '_anchor'):
                 self._anchor = torch.zeros((), device=x.device, requires_grad=True)
-            return list(_TrainForwardFn.apply(self, x, self._anchor))
+            out = _TrainForwardFn.apply(self, x, self._anchor)
+            return out if torch.is_tensor(out) else list(out)
         return self._predict_once(x)
 
     def _predict_once(self, x, profile=False, visualize=False):
@@ -272,7 +279,7 @@ class BaseModel(nn.Module):
 
     def backward(self, head_grads, layer_done=None):
         """Explicit reverse pass over the layer list (the counterpart of `_predict_once`; replaces torch.autograd on the
-        hot path): `head_grads` = d loss / d raw head maps (list, one per level).  Every module's `backward` launches its HIP
+        hot path): `head_grads` = d loss / d raw head maps (list, one per level; a classification head: the one (B, nc) tensor).  Every module's `backward` launches its HIP
         adjoint kernels and fills `.grad` of its parameters (overwrite semantics); gradients of tensors with several
         consumers (the save-list) are summed with the HIP add kernel.  `layer_done(i)` is called after layer i's kernels are queued (the
         trainer hangs its bucketed gradient all-reduce on it)."""
@@ -407,7 +414,7 @@ class BaseModel(nn.Module):
             ops.Q8_CALIB, ops.Q8_CALIB_PCT = None, None
             self.train(was_training)
         names = {m: n for n, m in self.named_modules()}
-        exclude = tuple(exclude) + tuple(n + '.' for n, m in self.named_modules() if isinstance(m, (Segment, Pose)))     # fp8 for the Segment / Pose heads is not built
+        exclude = tuple(exclude) + tuple(n + '.' for n, m in self.named_modules() if isinstance(m, (Segment, Pose, Classify)))     # fp8 for the Segment / Pose / Classify heads is not built
         table = {}
         for (m, key), amax in stats.items():
             if any(e in names.get(m, '?') + '.' for e in exclude):
@@ -567,16 +574,76 @@ class PoseModel(DetectionModel):
                            '(the reference has no pose-specific augmentation either); run the plain single pass')
 
 
+class ClassificationModel(BaseModel):
+    """YOLOv8 classification model (reference tasks.py:338-408).  Eval forward -> probabilities (B, nc) fp32; train forward -> raw logits (B, nc) fp32;
+    `model(batch)` with batch = {'img': ..., 'cls': int64 (B,)} -> (loss, loss.detach()) of v8ClassificationLoss, and `loss.backward()` runs the HIP
+    reverse pass.  The torchvision branch of the reference (`model=`: `_from_detection_model`) is not built."""
+
+    def __init__(self, cfg='yolov8n-cls.yaml', model=None, ch=3, nc=None, cutoff=10, verbose=True):
+        super().__init__()
+        if model is not None:
+            self._from_detection_model(model, nc, cutoff)
+        else:
+            self._from_yaml(cfg, ch, nc, verbose)
+
+    def _from_detection_model(self, model, nc=1000, cutoff=10):
+        raise NotImplementedError('ClassificationModel._from_detection_model is not built: build the model from a -cls YAML '
+                                  "(ClassificationModel('yolov8n-cls.yaml', nc=...)); cutting a detection model's backbone is the reference's YOLOv5 path")
+
+    def _from_yaml(self, cfg, ch, nc, verbose):
+        self.yaml = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
+        ch = self.yaml['ch'] = self.yaml.get('ch', ch)
+        if nc and nc != self.yaml['nc']:
+            if verbose:
+                print(f"Overriding model.yaml nc={self.yaml['nc']} with nc={nc}")
+            self.yaml['nc'] = nc
+        elif not nc and not self.yaml.get('nc', None):
+            raise ValueError('nc not specified. Must specify nc in model.yaml or function arguments.')
+        self.model, self.save, reductions = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
+        self._reductions = list(reductions)
+        self.stride = torch.Tensor([1])                     # no stride constraints
+        self.names = {i: f'{i}' for i in range(self.yaml['nc'])}
+        self.nc = self.yaml['nc']
+        self.inplace = self.yaml.get('inplace', True)
+        self.compute_dtype = torch.float32
+        self.args = None
+        # no initialize_weights here: the reference's ClassificationModel (tasks.py:367-381) never calls it, so its BatchNorm layers keep
+        # nn.BatchNorm2d's defaults (eps 1e-5, momentum 0.1), not the detection models' eps 1e-3 / momentum 0.03
+        if verbose:
+            self.info()
+
+    @staticmethod
+    def reshape_outputs(model, nc):
+        """Give the Classify head `nc` outputs if it has another count (reference tasks.py:383-402, the YOLO Classify() branch)."""
+        name, m = list((model.model if hasattr(model, 'model') else model).named_children())[-1]
+        if isinstance(m, Classify):
+            if m.linear.out_features != nc:
+                m.linear = nn.Linear(m.linear.in_features, nc).to(m.linear.weight.device)
+                m.__dict__.pop('_pk', None)
+        else:
+            raise NotImplementedError(f'reshape_outputs: {type(m).__name__} heads (torchvision backbones) are not built')
+
+    def init_criterion(self):
+        from ..yolo.utils.loss import v8ClassificationLoss
+        return v8ClassificationLoss()
+
+    def predict(self, x, profile=False, visualize=False, augment=False):
+        if augment:
+            raise RuntimeError('augment=True is not built for ClassificationModel: test-time augmentation merges detection boxes '
+                               '(the reference has no classification form of it); run the plain single pass')
+        return super().predict(x, profile=profile, visualize=visualize)
+
+
 def model_class_of(cfg):
-    """SegmentationModel / PoseModel for a YAML dict whose head ends in Segment / Pose, DetectionModel otherwise."""
-    return {'segment': SegmentationModel, 'pose': PoseModel}.get(guess_model_task(cfg), DetectionModel)
+    """SegmentationModel / PoseModel / ClassificationModel for a YAML dict whose head ends in Segment / Pose / Classify, DetectionModel otherwise."""
+    return {'segment': SegmentationModel, 'pose': PoseModel, 'classify': ClassificationModel}.get(guess_model_task(cfg), DetectionModel)
 
 
 def guess_model_task(model):
-    """'detect' / 'segment' / 'pose' from a YAML dict, a model object or a file name (reference tasks.py:738-790, the tasks that are built here)."""
+    """'detect' / 'segment' / 'pose' / 'classify' from a YAML dict, a model object or a file name (reference tasks.py:738-790, the tasks that are built here)."""
     def cfg2task(cfg):
         m = str(cfg['head'][-1][-2]).lower()
-        return 'segment' if m == 'segment' else 'pose' if m == 'pose' else 'detect'
+        return 'segment' if m == 'segment' else 'pose' if m == 'pose' else 'classify' if m == 'classify' else 'detect'
     if isinstance(model, dict):
         return cfg2task(model)
     if isinstance(model, nn.Module):
@@ -589,12 +656,16 @@ def guess_model_task(model):
                 return 'segment'
             if isinstance(m, Pose):
                 return 'pose'
+            if isinstance(m, Classify):
+                return 'classify'
             if isinstance(m, Detect):
                 return 'detect'
     if isinstance(model, (str, Path)):
         stem = Path(model).stem
         if '-seg' in stem or 'segment' in Path(model).parts:
             return 'segment'
+        if '-cls' in stem or 'classify' in Path(model).parts:
+            return 'classify'
         return 'pose' if ('-pose' in stem or 'pose' in Path(model).parts) else 'detect'
     return 'detect'
 
@@ -680,6 +751,11 @@ def parse_model(d, ch, verbose=True):
                 args.insert(2, n)
                 n = 1
             r_out = r_in * (args[3] if m in (Conv, DWConv) and len(args) > 3 else 1)
+        elif m is Classify:                     # tasks.py:655-656 of the upstream parser: c1 = ch[f], c2 = nc
+            c1 = ch[f] if isinstance(f, int) else sum(ch[x] for x in f)
+            c2 = args[0]
+            args = [c1, c2, *args[1:]]
+            r_out = red[f] if isinstance(f, int) else red[f[0]]
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
             r_out = red[f[0]]
@@ -802,7 +878,7 @@ def yaml_model_load(path):
     """Load a model YAML in the reference's schema; '...yolov8n.yaml' resolves to '...yolov8.yaml' + scale n (tasks.py:702-717).
     Names of the built-in graphs (mgdt_yolo_amd.models.CONFIGS) resolve without a file."""
     import yaml
-    from ..models import CONFIGS, POSE_CONFIGS, SEG_CONFIGS, get_config
+    from ..models import CLS_CONFIGS, CONFIGS, POSE_CONFIGS, SEG_CONFIGS, get_config
     path = Path(path)
     scale = guess_model_scale(path)
     unified = Path(re.sub(r'(\d+)([nslmx])(.+)?$', r'\1\3', str(path)))
@@ -813,7 +889,7 @@ def yaml_model_load(path):
             d['scale'] = scale
             d['yaml_file'] = str(path)
             return d
-    if unified.stem in CONFIGS or unified.stem in SEG_CONFIGS or unified.stem in POSE_CONFIGS:
+    if unified.stem in CONFIGS or unified.stem in SEG_CONFIGS or unified.stem in POSE_CONFIGS or unified.stem in CLS_CONFIGS:
         d = get_config(unified.stem, scale or 'n')
         d['scale'] = scale
         d['yaml_file'] = str(path)

@@ -1654,3 +1654,121 @@ def sgd_ema_step_dev(p, g, buf, wd, ema, data, hyper, nesterov, first, clip=None
 
 def ema_update(ema, p, decay):
     _launch('ema_update', 'mgdt_ema_update', ptr(ema), ptr(p), p.numel(), float(decay), stream())
+
+
+# ------------------------------------------------------------------ image classification (csrc/classify.hip)
+FUSED_CLS_HEAD = True    # tests / tools/cls_bench.py flip this: Classify.conv + the spatial mean in one launch vs conv, pooling, linear as a 1x1 conv, softmax
+CLS_FUSED_MAX_HW = None  # the fused head runs for maps of at most this many pixels (None: every size)
+
+
+class PackedClsPool:
+    """Classify.conv folded for mgdt_classify_pool_fwd: w (cout, c1) row-major in the compute dtype, bias fp32 (cout).  `weight` / `bias` are the
+    folded fp32 parameters (fuse_conv_and_bn's arithmetic, so the panel is the same bit for bit before and after BaseModel.fuse())."""
+    __slots__ = ('w', 'bias', 'cin', 'cout', 'dtype')
+
+    def __init__(self, weight, bias, dtype):
+        _need_gpu(weight)
+        self.cout, self.cin, self.dtype = weight.shape[0], weight.shape[1], dtype
+        self.w = weight.detach().float().reshape(self.cout, self.cin).to(dtype).contiguous()
+        self.bias = (torch.zeros(self.cout, device=weight.device) if bias is None else bias.detach().float()).contiguous()
+
+
+def classify_pool(x, pk, k=1, groups=1, act=ACT_SILU):
+    """pooled (B, cout) fp32 = mean over the pixels of act(conv1x1(x) + bias): mgdt_classify_pool_fwd (refuses what it does not take)."""
+    _need_gpu(x)
+    if x.dtype != pk.dtype:
+        raise RuntimeError(f'classify_pool: the weights are prepared for {pk.dtype}, the input is {x.dtype}')
+    if x.shape[1] != pk.cin:
+        raise RuntimeError(f'classify_pool: the input has {x.shape[1]} channels, the weights {pk.cin}')
+    pooled = torch.empty(x.shape[0], pk.cout, dtype=torch.float32, device=x.device)
+    _launch('classify_pool_fwd', 'mgdt_classify_pool_fwd', vp(x), ptr(pk.w), ptr(pk.bias), pk.cout, k, groups, act, ptr(pooled), dtype_code(pk.dtype), stream())
+    return pooled
+
+
+def classify_pool_supported(x, cin, cout, k, groups, act, dtype):
+    pe = 8
+    hw = x.shape[2] * x.shape[3]
+    return (FUSED_CLS_HEAD and k == 1 and groups == 1 and act == ACT_SILU and cin % 8 == 0 and cout % 16 == 0 and x.dtype == dtype and is_nhwc(x)
+            and (x.shape[3] == 1 or x.stride(3) % pe == 0) and (x.shape[2] == 1 or x.stride(2) % pe == 0) and (x.shape[0] == 1 or x.stride(0) % pe == 0)
+            and x.data_ptr() % 16 == 0 and (CLS_FUSED_MAX_HW is None or hw <= CLS_FUSED_MAX_HW))
+
+
+def classify_linear(pooled, w, bias, softmax=False):
+    """(logits, probs or None): pooled (B, k) fp32 @ w (nc, k, compute dtype)^T + bias, fp32; `softmax`: the row softmax as well."""
+    _need_gpu(pooled)
+    if pooled.dtype != torch.float32 or not pooled.is_contiguous() or not w.is_contiguous() or w.shape[1] != pooled.shape[1]:
+        raise RuntimeError('classify_linear: pooled must be a contiguous fp32 (B, k) tensor and w a contiguous (nc, k) one')
+    n, k = pooled.shape
+    nc = w.shape[0]
+    logits = torch.empty(n, nc, dtype=torch.float32, device=pooled.device)
+    probs = torch.empty_like(logits) if softmax else None
+    _launch('classify_linear_fwd', 'mgdt_classify_linear_fwd', ptr(pooled), ptr(w), ptr(bias), n, k, nc, ptr(logits), ptr(probs), dtype_code(w.dtype), stream())
+    return logits, probs
+
+
+def cls_softmax(logits, out=None):
+    _need_gpu(logits)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
+        raise RuntimeError('cls_softmax: logits must be a contiguous fp32 (B, nc) tensor')
+    out = torch.empty_like(logits) if out is None else out
+    _launch('cls_softmax_fwd', 'mgdt_cls_softmax_fwd', ptr(logits), logits.shape[0], logits.shape[1], ptr(out), stream())
+    return out
+
+
+def _cls_labels(labels, n, nc, device):
+    """int64 (B,) labels on the device; labels that are still on the host are range-checked here (on the device the kernels give NaN / zero rows)."""
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(labels)
+    if labels.dtype != torch.int64:
+        raise RuntimeError(f"classification labels are int64 class indices (batch['cls']), got {labels.dtype}")
+    labels = labels.reshape(-1)
+    if labels.numel() != n:
+        raise RuntimeError(f'classification labels: {labels.numel()} labels for {n} rows')
+    if not labels.is_cuda:
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= nc):
+            raise ValueError(f'classification label outside [0, {nc}): min {int(labels.min())}, max {int(labels.max())}')
+        labels = labels.to(device)
+    return labels.contiguous()
+
+
+def _cls_logits(logits):
+    _need_gpu(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise RuntimeError('classification logits must be a fp32 (B, nc) tensor')
+    return logits.contiguous()
+
+
+def cls_loss_fwd(logits, labels):
+    """(loss fp32 scalar tensor = cross_entropy(sum) / 64, labels on the device)"""
+    logits = _cls_logits(logits)
+    n, nc = logits.shape
+    labels = _cls_labels(labels, n, nc, logits.device)
+    rows = torch.empty(n, dtype=torch.float32, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    _launch('cls_loss_fwd', 'mgdt_cls_loss_fwd', ptr(logits), ptr(labels), n, nc, ptr(rows), ptr(loss), stream())
+    return loss, labels
+
+
+def cls_loss_bwd(logits, labels, gscale=1.0):
+    logits = _cls_logits(logits)
+    n, nc = logits.shape
+    labels = _cls_labels(labels, n, nc, logits.device)
+    d = torch.empty_like(logits)
+    _launch('cls_loss_bwd', 'mgdt_cls_loss_bwd', ptr(logits), ptr(labels), n, nc, float(gscale), ptr(d), stream())
+    return d
+
+
+def cls_topk(probs, targets=None, matrix=None):
+    """(B, min(nc, 5)) int64 indices of the largest probabilities per row, descending (equal values: lower index first).  `matrix` (nc, nc) int32 on
+    the device: matrix[top1][target] += 1 in the same launch."""
+    probs = _cls_logits(probs)
+    n, nc = probs.shape
+    out = torch.empty(n, min(nc, 5), dtype=torch.int64, device=probs.device)
+    if matrix is not None:
+        if targets is None:
+            raise RuntimeError('cls_topk: the confusion matrix needs the targets')
+        if matrix.dtype != torch.int32 or tuple(matrix.shape) != (nc, nc) or not matrix.is_contiguous() or not matrix.is_cuda:
+            raise RuntimeError(f'cls_topk: matrix must be a contiguous int32 ({nc}, {nc}) device tensor')
+        targets = _cls_labels(targets, n, nc, probs.device)
+    _launch('cls_topk_fwd', 'mgdt_cls_topk_fwd', ptr(probs), n, nc, ptr(out), ptr(targets) if matrix is not None else None, ptr(matrix), stream())
+    return out

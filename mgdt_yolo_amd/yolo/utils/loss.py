@@ -87,3 +87,37 @@ def loss_and_head_grads(crit, feats, batch, gscale=1.0):
     grads = ops.detect_loss_bwd(st, gscale)
     crit.epoch += 1
     return st.out5[0], st.out5[1:4], grads
+
+
+class _ClsLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits = logits.detach()
+        loss, labels = ops.cls_loss_fwd(logits, labels)
+        ctx.logits, ctx.labels = logits, labels
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.cls_loss_bwd(ctx.logits, ctx.labels, 1.0) * g, None
+
+
+class v8ClassificationLoss:
+    """Criterion of the classification task (reference loss.py:395-401): cross_entropy(preds, batch['cls'], reduction='sum') / 64 - the constant
+    64, not the batch size.  preds: raw logits (B, nc) fp32 on the device; batch['cls']: int64 (B,) class indices (on the host they are
+    range-checked; on the device a label outside [0, nc) gives a NaN loss and a zero gradient row)."""
+
+    def __call__(self, preds, batch):
+        preds = preds[1] if isinstance(preds, (list, tuple)) else preds
+        if preds.requires_grad:
+            loss = _ClsLossFn.apply(preds, batch['cls'])
+        else:
+            loss = ops.cls_loss_fwd(preds, batch['cls'])[0]
+        return loss, loss.detach()
+
+
+def cls_loss_and_head_grad(logits, batch, gscale=1.0):
+    """(loss, d(loss * gscale) / d logits) without torch.autograd: the entry the explicit backward pass (`model.backward(grad)`) starts from -
+    the classification counterpart of `loss_and_head_grads`."""
+    loss, labels = ops.cls_loss_fwd(logits.detach(), batch['cls'])
+    return loss, ops.cls_loss_bwd(logits.detach(), labels, gscale)

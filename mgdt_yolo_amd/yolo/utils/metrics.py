@@ -152,3 +152,32 @@ def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, on_plot=None, save_
     tp_out = (r * nt).round()
     fp_out = (tp_out / (p + eps) - tp_out).round()
     return tp_out, fp_out, p, r, f1, ap, unique_classes.astype(int)
+
+
+class ClassifyMetrics:
+    """Top-1 / top-5 accuracy of the classification task (reference metrics.py:934-977).  `process(targets, pred)`: lists of per-batch targets
+    (n,) and predicted class indices (n, min(nc, 5)), best first - the rows mgdt_cls_topk_fwd writes.  The comparison is a few integers per image
+    and runs wherever the tensors live (host tensors after the validator's one read)."""
+
+    def __init__(self):
+        self.top1 = 0
+        self.top5 = 0
+        self.speed = {'preprocess': 0.0, 'inference': 0.0, 'loss': 0.0, 'postprocess': 0.0}
+
+    def process(self, targets, pred):
+        pred, targets = torch.cat(list(pred)), torch.cat(list(targets))
+        correct = (targets.reshape(-1)[:, None] == pred).float()
+        acc = torch.stack((correct[:, 0], correct.max(1).values), dim=1)          # (top1, top5) accuracy
+        self.top1, self.top5 = acc.mean(0).tolist()
+
+    @property
+    def fitness(self):
+        return self.top5
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ['fitness'], [self.top1, self.top5, self.fitness]))
+
+    @property
+    def keys(self):
+        return ['metrics/accuracy_top1', 'metrics/accuracy_top5']
