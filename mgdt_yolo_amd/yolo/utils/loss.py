@@ -44,9 +44,12 @@ class v8DetectionLoss:
         self.use_dfl = m.reg_max > 1
 
     def preprocess(self, batch, batch_size, imgsz_hw):
-        """batch dict -> dense (B, Nmax, 5) [cls, xyxy px] on the device (loss.py:132-148,177-181)."""
+        """batch dict -> dense (B, Nmax, 5) [cls, xyxy px] on the device (loss.py:132-148,177-181).  Labels outside [0, nc) are refused here: the
+        assigner kernel indexes the class map with the label as it is (the reference's gather fails on such a label too)."""
         idx = batch['batch_idx'].detach().cpu().numpy().reshape(-1).astype(np.int64)
         cls = batch['cls'].detach().cpu().numpy().reshape(-1, 1).astype(np.float32)
+        if cls.size and not (cls.min() >= 0 and cls.max() < self.nc):          # also catches NaN
+            raise ValueError(f'v8DetectionLoss: class labels must lie in [0, {self.nc}), got {float(cls.min())} .. {float(cls.max())}')
         box = batch['bboxes'].detach().cpu().numpy().reshape(-1, 4).astype(np.float32)
         if idx.size == 0:
             return torch.zeros(batch_size, 0, 5, device=self.device)

@@ -21,12 +21,14 @@ MAX_EPOCHS = 100  # tal.py:168
 EPS = 1e-9
 
 
-def assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, call_count, nc):
+def assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, call_count, nc, aux=None):
     """pd_scores (B,A,nc) sigmoid-ed, pd_bboxes (B,A,4) xyxy px, anc_points (A,2) px,
     gt_labels (B,N,1), gt_bboxes (B,N,4) xyxy px, mask_gt (B,N,1) float.
 
     Returns target_labels (B,A) int64, target_bboxes (B,A,4), target_scores (B,A,nc), fg_mask (B,A) bool,
-    target_gt_idx (B,A) int64.
+    target_gt_idx (B,A) int64.  Evaluated in the dtype of the predictions.  A dict passed as `aux` receives the intermediates the decisions are taken
+    on: align / overlaps (B,N,A), raw_iou (the CIoU before its clamp), in_gts (in-box and valid, bool), deltas_min (anchor-to-edge distance, px),
+    topk (B,N,K anchor indices), claims (B,A: GTs claiming the anchor before the multi-claim resolution).
     """
     B, A, _ = pd_scores.shape
     N = gt_bboxes.shape[1]
@@ -60,6 +62,8 @@ def assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, call
     count.scatter_add_(-1, order, torch.ones_like(order, dtype=torch.int32))
     count[count > 1] = 0
     mask_pos = count.to(pd_scores.dtype) * in_gts * mask_gt         # tal.py:240
+    if aux is not None:
+        aux.update(align=align, overlaps=overlaps, raw_iou=iou.squeeze(-1), in_gts=m, deltas_min=deltas.amin(-1), topk=order, claims=mask_pos.sum(-2))
 
     # select_highest_overlaps fed with align_metric (fork change), tal.py:29-54,222
     fg = mask_pos.sum(-2)

@@ -428,3 +428,146 @@ def _check_fp8(got, ref, what=''):
     err = (got - ref).abs().max().item() / max(1.0, ref.abs().max().item())
     print(f'{what}: uses {err / 8e-3:.3f} of the fp8 bound')
     assert err < 8e-3, (what, err)
+
+
+# ------------------------------------------------------------------------------------------------ detection loss / assigner (test_loss_kernels.py)
+def loss_maps(gen, B, R, nc, levels, dt):
+    """Raw head maps, one (B, 4R + nc, H, W) CPU fp64 tensor per level (H, W, stride), every value representable in dt.  The DFL logits lean
+    towards the far bins (boxes of a few cells), the class logits sit around -2 as after the head's bias initialisation."""
+    out = []
+    for h, w, _ in levels:
+        f = torch.randn(B, 4 * R + nc, h, w, generator=gen) * 1.2
+        f[:, :4 * R] += (torch.arange(R, dtype=F32) / max(R - 1, 1) * 2.5 - 1.0).repeat(4).view(1, -1, 1, 1)
+        f[:, 4 * R:] -= 2.0
+        out.append(f.to(dt).double())
+    return out
+
+
+def loss_gt_random(gen, B, N, nc, width, height, counts, lo=10.0, hi=60.0):
+    """(B, N, 5) fp32 [cls, x1, y1, x2, y2] px: counts[b] random boxes in image b (sides lo..hi px, clipped to the image), the other rows zero
+    (padding).  The first two boxes drawn carry the labels 0 and nc - 1."""
+    gt = torch.zeros(B, N, 5, dtype=F32)
+    k = 0
+    for b in range(B):
+        for j in range(counts[b]):
+            cx, cy = (torch.rand(2, generator=gen) * torch.tensor([width, height])).tolist()
+            bw, bh = (torch.rand(2, generator=gen) * (hi - lo) + lo).tolist()
+            lab = (0, nc - 1)[k] if k < 2 else int(torch.randint(0, nc, (1,), generator=gen))
+            gt[b, j] = torch.tensor([lab, max(cx - bw / 2, 0.0), max(cy - bh / 2, 0.0), min(cx + bw / 2, width), min(cy + bh / 2, height)])
+            k += 1
+    return gt
+
+
+def loss_reference(maps, gt, strides, R, nc, call_count, want_grad=True):
+    """oracle.loss.detection_loss in float64 on the given (already rounded) maps with the dense fp32 targets upcast as they are; the gradient of
+    total (= loss * B) by torch.autograd.  Returns a dict: total, items, grads (list, NCHW), fg, gt_idx, tscore (B, A), tss, aux."""
+    from oracle import loss as OLoss
+    fs = [m.clone().requires_grad_(want_grad) for m in maps]
+    assert all(f.dtype == torch.float64 for f in fs)
+    total, items, aux = OLoss.detection_loss(fs, None, [float(s) for s in strides], R, nc, call_count=call_count, targets=gt)
+    assert total.dtype == torch.float64 and items.dtype == torch.float64 and aux['target_scores'].dtype == torch.float64
+    grads = None
+    if want_grad:
+        total.backward()
+        grads = [f.grad for f in fs]
+    ts = aux['target_scores'].sum(-1)
+    return dict(total=total.detach(), items=items, grads=grads, fg=aux['fg_mask'], gt_idx=aux['target_gt_idx'], tscore=ts,
+                tss=torch.as_tensor(max(float(ts.sum()), 1.0), dtype=torch.float64), aux=aux)
+
+
+def _rows_identical(gt, b, j1, j2):
+    return (gt[b, j1] == gt[b, j2]).all(-1)
+
+
+def _top2_over_gts(aux, gt):
+    """For every (image, anchor): the largest and second largest align metric over the GT rows and whether the two rows are identical."""
+    align = aux['align']
+    B, N, A = align.shape
+    if N < 2:
+        z = torch.zeros(B, A, dtype=align.dtype)
+        return align[:, 0], z - 1, torch.zeros(B, A, dtype=torch.bool), torch.zeros(B, A, dtype=torch.long), torch.zeros(B, A, dtype=torch.long)
+    v, j = align.sort(dim=1, descending=True, stable=True)
+    bi = torch.arange(B)[:, None].expand(B, A)
+    return v[:, 0], v[:, 1], _rows_identical(gt, bi, j[:, 0], j[:, 1]), j[:, 0], j[:, 1]
+
+
+def loss_margins(ref, gt, R, what=''):
+    """The conditions on the INPUTS under which an fp32 evaluation cannot take another decision than the float64 reference (see
+    test_loss_kernels.py): asserted on the reference alone, for every GT and anchor of the case."""
+    aux = ref['aux']
+    align, raw, in_gts, topk, claims = aux['align'], aux['raw_iou'], aux['in_gts'], aux['topk'], aux['claims']
+    B, N, A = align.shape
+    assert A > 10, 'top-k margins need more than 10 anchors'
+    valid = aux['mask_gt'].bool().squeeze(-1)
+    # (a) 10th vs 11th largest align of every valid GT
+    srt = align.sort(-1, descending=True)[0]
+    a10, a11 = srt[..., 9], srt[..., 10]
+    ok_a = (((a10 - a11) >= 1e-4 * a10) & (a10 > 0)) | ((a10 == 0) & (a11 == 0))
+    assert ok_a[valid].all(), (what, '(a) top-k boundary within 1e-4', ((a10 - a11) / a10.clamp(min=1e-300))[valid & ~ok_a].tolist())
+    # (b) best vs second-best align over the GTs at every multiply claimed anchor
+    best, second, same, _, _ = _top2_over_gts(aux, gt)
+    multi = claims > 1
+    ok_b = (((best - second) >= 1e-4 * best) & (best > 0)) | ((best == second) & same)
+    assert ok_b[multi].all(), (what, '(b) multi-claim within 1e-4', int((multi & ~ok_b).sum()))
+    # (c) the clamp of the CIoU at 0: no in-box member of a top-k sits on it;  (e) nor does its align metric leave the fp32 normal range
+    inbox_k = torch.gather(in_gts, 2, topk) & valid[..., None]
+    raw_k, al_k = torch.gather(raw, 2, topk), torch.gather(align, 2, topk)
+    assert (raw_k[inbox_k].abs() >= 1e-5).all(), (what, '(c) a CIoU within 1e-5 of its clamp')
+    assert (al_k[inbox_k & (al_k > 0)] >= 1e-30).all(), (what, '(e) a positive align metric below 1e-30')
+    # (d) min / max ties of the CIoU: no predicted coordinate equals its target's
+    fg = ref['fg']
+    tb = (aux['target_bboxes'] / aux['stride_tensor'])[fg]
+    assert (aux['pred_bboxes'][fg] != tb).all(), (what, '(d) a predicted coordinate equals the target coordinate')
+
+
+def loss_census(ref, gt, R, nc):
+    """How many of each decision edge the reference of one case contains (counts; test_loss_kernels.py sums them over its cases)."""
+    aux = ref['aux']
+    in_gts, claims, fg, gi = aux['in_gts'], aux['claims'], ref['fg'], ref['gt_idx']
+    B, N, A = in_gts.shape
+    valid = aux['mask_gt'].bool().squeeze(-1)
+    best, second, same, j1, j2 = _top2_over_gts(aux, gt)
+    multi = claims > 1
+    n_in = in_gts.sum(-1)
+    lab = torch.gather(gt[..., 0].long(), 1, gi)
+    tb = aux['target_bboxes'] / aux['stride_tensor']
+    ltrb = torch.cat((aux['anchor_points'] - tb[..., :2], tb[..., 2:] - aux['anchor_points']), -1)
+    has = valid.any(1)
+    return {'multi_claim_by_margin': int((multi & (best > second)).sum()),
+            'gt_with_1_to_9_anchors': int((valid & (n_in >= 1) & (n_in <= 9)).sum()),
+            'gt_without_anchor': int((valid & (n_in == 0)).sum()),
+            'padded_gt_row': int((~valid).sum()),
+            'empty_image_in_labelled_batch': int((~has).sum()) if has.any() else 0,
+            'dfl_target_clamped': int((ltrb[fg] > R - 1 - 0.01).sum()),
+            'positive_label_0': int((fg & (lab == 0)).sum()),
+            'positive_label_last': int((fg & (lab == nc - 1)).sum()),
+            'centre_on_gt_edge': int(((aux['deltas_min'] == 0) & valid[..., None]).sum()),
+            'duplicate_rows_tie_to_lower': int((multi & fg & (best == second) & same & (gi == torch.minimum(j1, j2))).sum())}
+
+
+# ------------------------------------------------------------------------------------------------ optimizer (test_loss_kernels.py)
+def f32r(x):
+    """A Python scalar as the C ABI receives it: rounded to fp32."""
+    return float(torch.tensor(x, dtype=F32))
+
+
+def ref_clip(g, max_norm):
+    """mgdt_grad_clip_coef in float64: (norm, min(1, max_norm / (norm + 1e-6)))."""
+    norm = g.double().pow(2).sum().sqrt()
+    return norm, torch.clamp(f32r(max_norm) / (norm + f32r(1e-6)), max=1.0)
+
+
+def ref_sgd(p, g, buf, wd, lr, lr_bias, momentum, nesterov, first, coef):
+    """mgdt_sgd_step in float64 (trainer.py:462-470 with the flat per-element groups): returns the new (p, buf).  wd[i] > 0 decays, wd[i] < 0
+    is the bias group stepping with lr_bias, coef the clip coefficient (1 without)."""
+    p, g, buf = p.double(), g.double(), buf.double()
+    w = torch.zeros_like(p) if wd is None else wd.double()
+    gi = coef * g + torch.where(w > 0, w * p, torch.zeros_like(p))
+    b = gi if first else f32r(momentum) * buf + gi
+    step = gi + f32r(momentum) * b if nesterov else b
+    return p - torch.where(w < 0, torch.full_like(p, f32r(lr_bias)), torch.full_like(p, f32r(lr))) * step, b
+
+
+def ref_ema(ema, p, d):
+    """mgdt_ema_update in float64 (ModelEMA.update, torch_utils.py:342-361), d as the C ABI receives it."""
+    return f32r(d) * ema.double() + (1.0 - f32r(d)) * p.double()
