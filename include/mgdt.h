@@ -425,6 +425,26 @@ int mgdt_kpt_iou_fwd(const float* pred, int pred_stride, int pred_ndim, const in
 int mgdt_val_match_fwd(const float* det, const int32_t* ndet, int n, int max_det, const float* labels, const int32_t* nlab, int max_lab,
                        const float* iouv, int n_iou, uint8_t* correct, mgdt_stream s);
 
+/* ---- validator statistics beyond mAP: confusion matrix + counting metrics, one launch per batch ----------------------------------------
+ * det / ndet / labels / nlab as mgdt_val_match_fwd takes them, in one native pixel frame.  Both outputs are ADDED to with integer atomics (the caller
+ * clears them once per validation run; replays are bit-equal); either may be NULL, not both.
+ * matrix int32 [(nc+1)][(nc+1)], row = predicted class, column = true class, index nc = background: ConfusionMatrix.process_batch
+ *   (yolo/utils/metrics.py:209-253) per image.  Detections with conf > cm_conf; pairs with box_iou > cm_iou (fp32, the operation order of
+ *   mgdt_val_match_fwd); each detection keeps its highest-IoU label, each label the highest-IoU detection among those that chose it (the two
+ *   np.unique of the reference, NOT a greedy matching).  A label with a winner adds matrix[cls(det)][cls(label)], another matrix[nc][cls(label)];
+ *   a kept detection that won no label adds matrix[cls(det)][nc], but only in an image with at least one match (the reference's `if n:`).
+ * counts int64 [nc][MGDT_COUNT_SLOTS]: nn/cal_counting_metrics.py:70-121 for nc classes.  Per image and class c: t labels, p detections with
+ *   conf > cnt_conf; each label takes the FIRST such detection in NMS order with IoU > cnt_iou (a detection may serve several labels); TP per
+ *   match, FN per label without, FP = p - distinct matched detections.  The IoU is the script's (max(0, .) on both sides, 0 unless union > 0),
+ *   in fp32, on label corners truncated toward zero when cnt_trunc_labels != 0 (the script's int()).
+ *   Slots: images, sum t, sum p, sum t^2, sum t*p, sum (t-p)^2, sum |t-p|, TP, FP, FN.
+ * Classes are the float columns truncated toward zero; a row whose class is outside [0, nc) adds nothing.  Exact IoU ties resolve to the lower index.
+ * Limits (MGDT_BAD_SHAPE before any launch): n <= 65535, max_det <= 1024, max_lab <= 256, nc <= 4096. */
+#define MGDT_COUNT_SLOTS 10
+int mgdt_val_confusion_fwd(const float* det, const int32_t* ndet, int n, int max_det, const float* labels, const int32_t* nlab, int max_lab,
+                           int nc, float cm_conf, float cm_iou, float cnt_conf, float cnt_iou, int cnt_trunc_labels, int32_t* matrix,
+                           int64_t* counts, mgdt_stream s);
+
 /* ---- v8DetectionLoss: assigner + BCE/CIoU/DFL + gradient w.r.t. the head maps -----------------------------------------
  * yolo/utils/loss.py:108-208 (v8DetectionLoss.__call__, BboxLoss :56-89), yolo/utils/tal.py:56-353
  * (HeuristicPositiveSampleAssigner_v1 -> TaskAlignedAssigner, topk 10, alpha = 0.5*(100 - call_count/161)/100, beta 8),

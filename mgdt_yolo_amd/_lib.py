@@ -170,6 +170,7 @@ PROTOTYPES = {
     'mgdt_gt_masks_resample_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mgdt_val_match_iou_fwd': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     'mgdt_kpt_iou_fwd': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _vp]),
+    'mgdt_val_confusion_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
     'mgdt_classify_pool_fwd': (_i, [VP, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     'mgdt_classify_linear_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     'mgdt_cls_softmax_fwd': (_i, [_vp, _i, _i, _vp, _vp]),

@@ -1139,6 +1139,44 @@ def val_match(det, ndet, labels, nlab, iouv):
     return correct.view(torch.bool)
 
 
+COUNT_SLOTS = 10                   # == MGDT_COUNT_SLOTS: images, sum t, sum p, sum t^2, sum t*p, sum (t-p)^2, sum |t-p|, TP, FP, FN
+VAL_CONFUSION_MAX_DET, VAL_CONFUSION_MAX_LAB, VAL_CONFUSION_MAX_NC = 1024, 256, 4096
+
+
+def val_confusion(det, ndet, labels, nlab, nc, matrix=None, counts=None, cm_conf=0.25, cm_iou=0.45, cnt_conf=0.25, cnt_iou=0.5, trunc_labels=True):
+    """Confusion matrix and counting metrics of a batch in one launch (mgdt_val_confusion_fwd): det (B, max_det, 6) fp32 + ndet (B,) int32 as returned
+    by `nms`, labels (B, max_lab, 5) fp32 [cls, x1, y1, x2, y2] + nlab (B,) int32, in one pixel frame.  `matrix` ((nc+1, nc+1) int32, row = predicted
+    class, column = true class, nc = background) and `counts` ((nc, COUNT_SLOTS) int64) are ADDED to on the device; either may be None, not both.
+    Returns (matrix, counts)."""
+    _need_gpu(det)
+    _need_gpu(labels)
+    nc = int(nc)
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous():
+        raise RuntimeError(f'val_confusion: det must be a contiguous float32 (B, max_det, 6) tensor, got {tuple(det.shape)} {det.dtype}')
+    b, md = det.shape[0], det.shape[1]
+    if labels.dim() != 3 or labels.shape[0] != b or labels.shape[2] != 5 or labels.dtype != torch.float32 or not labels.is_contiguous():
+        raise RuntimeError(f'val_confusion: labels must be a contiguous float32 (B={b}, max_lab, 5) tensor, got {tuple(labels.shape)} {labels.dtype}')
+    _i32(ndet, b, 'val_confusion: ndet')
+    _i32(nlab, b, 'val_confusion: nlab')
+    if matrix is None and counts is None:
+        raise RuntimeError('val_confusion: neither a matrix nor counts to add to')
+    if matrix is not None:
+        _need_gpu(matrix)
+        if matrix.dtype != torch.int32 or matrix.numel() != (nc + 1) * (nc + 1) or not matrix.is_contiguous():
+            raise RuntimeError(f'val_confusion: matrix must be a contiguous int32 tensor of (nc + 1)^2 = {(nc + 1) ** 2} elements, got {tuple(matrix.shape)} {matrix.dtype}')
+    if counts is not None:
+        _need_gpu(counts)
+        if counts.dtype != torch.int64 or counts.numel() != nc * COUNT_SLOTS or not counts.is_contiguous():
+            raise RuntimeError(f'val_confusion: counts must be a contiguous int64 tensor of nc x {COUNT_SLOTS} = {nc * COUNT_SLOTS} elements, got {tuple(counts.shape)} {counts.dtype}')
+    ml = labels.shape[1]
+    if _PROF is not None:
+        _META['val_confusion_fwd'] = dict(shape=(b, md, ml, nc), flops=16.0 * b * md * ml * ((matrix is not None) + (counts is not None)),
+                                          bytes=float(4 * (det.numel() + labels.numel())))
+    _launch('val_confusion_fwd', 'mgdt_val_confusion_fwd', ptr(det), ptr(ndet), b, md, ptr(labels), ptr(nlab), ml, nc, float(cm_conf), float(cm_iou),
+            float(cnt_conf), float(cnt_iou), 1 if trunc_labels else 0, ptr(matrix), ptr(counts), stream())
+    return matrix, counts
+
+
 # ------------------------------------------------------------------ instance-segmentation validation (mask IoU, matching from an IoU matrix)
 MASK_IOU_MAX_DET, MASK_IOU_MAX_LAB, MASK_IOU_MAX_HW = 1024, 256, 1 << 24
 

@@ -181,3 +181,126 @@ class ClassifyMetrics:
     @property
     def keys(self):
         return ['metrics/accuracy_top1', 'metrics/accuracy_top5']
+
+
+def _one_image(detections, labels, dev):
+    """The per-image arguments of the reference in the batch layout of `ops.nms`: -> det (1, max(n, 1), 6), ndet, labels (1, max(m, 1), 5), nlab."""
+    cnt = lambda k: torch.full((1,), k, dtype=torch.int32, device=dev)
+    if labels.dim() == 1:                                   # the class vector of the `detections is None` call (val.py:88)
+        labels = torch.cat((labels.float().view(-1, 1), torch.zeros(labels.shape[0], 4, device=dev)), 1)
+    if labels.dim() != 2 or labels.shape[1] != 5:
+        raise RuntimeError(f'process_batch: labels are (M, 5) [cls, x1, y1, x2, y2] or, without detections, (M,) classes, got {tuple(labels.shape)}')
+    if detections is None:
+        detections = torch.zeros(0, 6, device=dev)
+    if detections.dim() != 2 or detections.shape[1] != 6:
+        raise RuntimeError(f'process_batch: detections are (N, 6) [x1, y1, x2, y2, conf, cls], got {tuple(detections.shape)}')
+    n, m = detections.shape[0], labels.shape[0]
+    det = detections.float().contiguous() if n else torch.zeros(1, 6, device=dev)
+    lab = labels.float().contiguous() if m else torch.zeros(1, 5, device=dev)
+    return det[None], cnt(n), lab[None], cnt(m)
+
+
+class ConfusionMatrix:
+    """The detection confusion matrix (reference metrics.py:176-264) accumulated on the device by mgdt_val_confusion_fwd: int32 counts,
+    row = predicted class, column = true class, index nc = background.  `process_batch(detections, labels)` has the reference's per-image
+    signature; `process_batch_dev` takes a whole batch as `ops.nms` returns it.  Reading `matrix` is the only synchronisation."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, task='detect'):
+        if task != 'detect':
+            raise RuntimeError(f"ConfusionMatrix: task='{task}': the classification counts are kept by ClassificationValidator (confusion_matrix); "
+                               "this class is the detection matrix")
+        self.task, self.nc, self.conf, self.iou_thres = task, int(nc), conf, iou_thres
+        self._dev = None
+
+    def _buffer(self, dev):
+        if self._dev is None:
+            self._dev = torch.zeros(self.nc + 1, self.nc + 1, dtype=torch.int32, device=dev)
+        return self._dev
+
+    def process_batch_dev(self, det, ndet, labels, nlab):
+        """det (B, max_det, 6) + ndet (B,) int32, labels (B, max_lab, 5) + nlab (B,) int32, one pixel frame per image: one launch, no sync."""
+        hip._need_gpu(det)
+        hip.val_confusion(det, ndet, labels, nlab, self.nc, matrix=self._buffer(det.device), cm_conf=self.conf, cm_iou=self.iou_thres)
+
+    def process_batch(self, detections, labels):
+        """detections (N, 6) [x1, y1, x2, y2, conf, cls] or None, labels (M, 5) [cls, x1, y1, x2, y2] (with detections=None also (M,) classes)."""
+        hip._need_gpu(labels)
+        if detections is not None:
+            hip._need_gpu(detections)
+        self.process_batch_dev(*_one_image(detections, labels, labels.device))
+
+    @property
+    def matrix(self):
+        if self._dev is None:
+            return np.zeros((self.nc + 1, self.nc + 1))
+        return self._dev.cpu().numpy().astype(np.float64)
+
+    def tp_fp(self):
+        """True and false positives per class, background dropped (metrics.py:259-264)."""
+        m = self.matrix
+        tp = m.diagonal()
+        fp = m.sum(1) - tp
+        return tp[:-1], fp[:-1]
+
+    def plot(self, *args, **kwargs):
+        raise RuntimeError('ConfusionMatrix: plotting and printing the matrix are host-side tooling outside the validation path (read `matrix`)')
+
+    print = plot
+
+
+class CountMetrics:
+    """Counting metrics of a detection model (reference nn/cal_counting_metrics.py and nn/cal_model_count_error.py, for nc classes): per class TP /
+    FP / FN at IoU `iou`, true and predicted counts per image, MAE, RMSE and R^2, from int64 sums accumulated on the device by
+    mgdt_val_confusion_fwd.  Reading `slots` / `results_dict` is the only synchronisation."""
+
+    def __init__(self, nc, conf=0.25, iou=0.5, trunc_labels=True):
+        self.nc, self.conf, self.iou, self.trunc_labels = int(nc), conf, iou, bool(trunc_labels)
+        self._dev = None
+
+    def _buffer(self, dev):
+        if self._dev is None:
+            self._dev = torch.zeros(self.nc, hip.COUNT_SLOTS, dtype=torch.int64, device=dev)
+        return self._dev
+
+    def process_batch_dev(self, det, ndet, labels, nlab):
+        hip._need_gpu(det)
+        hip.val_confusion(det, ndet, labels, nlab, self.nc, counts=self._buffer(det.device), cnt_conf=self.conf, cnt_iou=self.iou, trunc_labels=self.trunc_labels)
+
+    def process_batch(self, detections, labels):
+        """One image, the arguments of ConfusionMatrix.process_batch (an image without detections or without labels still counts as an image)."""
+        hip._need_gpu(labels)
+        if detections is not None:
+            hip._need_gpu(detections)
+        self.process_batch_dev(*_one_image(detections, labels, labels.device))
+
+    @property
+    def slots(self):
+        """(nc, COUNT_SLOTS) int64: images, sum t, sum p, sum t^2, sum t*p, sum (t-p)^2, sum |t-p|, TP, FP, FN."""
+        if self._dev is None:
+            return np.zeros((self.nc, hip.COUNT_SLOTS), np.int64)
+        return self._dev.cpu().numpy()
+
+    @staticmethod
+    def from_slots(slots):
+        """Integer slots -> dict of (nc,) arrays, float64.  R^2 is sklearn.metrics.r2_score behind the script's guard: 0 with fewer than two
+        images; with SS_tot = 0, 1 where SS_res = 0 and 0 elsewhere.  n * SS_tot = n * sum t^2 - (sum t)^2 is formed in integers."""
+        s = np.asarray(slots, dtype=np.int64)
+        n, st, stt, d2 = s[:, 0], s[:, 1], s[:, 3], s[:, 5]
+        nf = np.maximum(n, 1).astype(np.float64)
+        n_ss_tot = n * stt - st * st
+        with np.errstate(divide='ignore', invalid='ignore'):
+            r2 = 1.0 - (d2.astype(np.float64) * nf) / n_ss_tot.astype(np.float64)
+        r2 = np.where(n_ss_tot == 0, np.where(d2 == 0, 1.0, 0.0), r2)
+        r2 = np.where(n < 2, 0.0, r2)
+        return dict(tp=s[:, 7].astype(np.float64), fp=s[:, 8].astype(np.float64), fn=s[:, 9].astype(np.float64), gt=st.astype(np.float64),
+                    pred=s[:, 2].astype(np.float64), mae=np.where(n > 0, s[:, 6] / nf, 0.0), rmse=np.where(n > 0, np.sqrt(d2 / nf), 0.0), r2=r2)
+
+    @property
+    def keys(self):
+        return [f'metrics/count_{k}({c})' for c in range(self.nc) for k in ('tp', 'fp', 'fn', 'gt', 'pred', 'mae', 'rmse', 'r2')]
+
+    @property
+    def results_dict(self):
+        """Flat: 'metrics/count_<tp|fp|fn|gt|pred|mae|rmse|r2>(<class>)' -> float."""
+        r = self.from_slots(self.slots)
+        return {f'metrics/count_{k}({c})': float(r[k][c]) for c in range(self.nc) for k in ('tp', 'fp', 'fn', 'gt', 'pred', 'mae', 'rmse', 'r2')}

@@ -16,6 +16,7 @@ class DetectionValidator:
         self.device = torch.device(device)
         self.iouv = torch.linspace(0.5, 0.95, 10, device=self.device)     # val.py:60: IoU vector for mAP@0.5:0.95
         self.niou = self.iouv.numel()
+        self.confusion_matrix = self.count_metrics = None      # init_metrics(confusion=True, counting=True)
 
     def _process_batch(self, detections, labels):
         """detections (N, 6) [x1, y1, x2, y2, conf, cls], labels (M, 5) [cls, x1, y1, x2, y2] -> correct (N, 10) bool on detections.device."""
@@ -28,9 +29,28 @@ class DetectionValidator:
         return hip.val_match(det, cnt(n), lab, cnt(m), self.iouv.to(det.device))[0]
 
     # ---- the per-batch metric update and the final reduction (val.py:73-117, :123-131; metrics.py:410-497) -------------------------------
-    def init_metrics(self, nc=80, conf=0.001, iou=0.7, max_det=300):
+    def init_metrics(self, nc=80, conf=0.001, iou=0.7, max_det=300, confusion=False, counting=False):
+        """confusion / counting (both off by default): also accumulate the reference's ConfusionMatrix (val.py:54, fed as val.py:88 and :109 do) /
+        the counting metrics of nn/cal_counting_metrics.py on the device; `get_stats` then adds `confusion_matrix` and the `metrics/count_*` keys."""
+        from ...utils.metrics import ConfusionMatrix, CountMetrics
         self.nc, self.conf, self.iou, self.max_det = nc, conf, iou, max_det     # validator.py:85-86 / default.yaml
         self.seen, self.stats = 0, []
+        self.confusion_matrix = ConfusionMatrix(nc=nc) if confusion else None
+        self.count_metrics = CountMetrics(nc=nc) if counting else None
+
+    def _update_extras(self, predn, labelsn):
+        """One image in native space: predn (n, 6) or None, labelsn (m, 5).  The confusion matrix skips an image without labels like val.py:84-109;
+        the counting metrics count every image, as the script does."""
+        from ...utils.metrics import _one_image
+        cm, ct, dev = self.confusion_matrix, self.count_metrics, labelsn.device
+        matrix = cm._buffer(dev) if cm is not None and labelsn.shape[0] else None
+        counts = ct._buffer(dev) if ct is not None else None
+        if matrix is None and counts is None:
+            return
+        kw = dict(cm_conf=cm.conf, cm_iou=cm.iou_thres) if cm is not None else {}
+        if ct is not None:
+            kw.update(cnt_conf=ct.conf, cnt_iou=ct.iou, trunc_labels=ct.trunc_labels)
+        hip.val_confusion(*_one_image(predn, labelsn, dev), self.nc, matrix=matrix, counts=counts, **kw)      # both parts in one launch
 
     def postprocess(self, preds):
         """val.py:63-71: NMS with the validator's settings (multi_label)."""
@@ -51,11 +71,21 @@ class DetectionValidator:
             bbox = batch['bboxes'].to(dev)[idx].float()
             nl, npr = cls.shape[0], pred.shape[0]
             shape = batch['ori_shape'][si]
+            extras = self.confusion_matrix is not None or self.count_metrics is not None
+            labelsn = torch.zeros(0, 5, device=dev)
             correct = torch.zeros(npr, self.niou, dtype=torch.bool, device=dev)
             self.seen += 1
             if npr == 0:
                 if nl:
                     self.stats.append((correct, *torch.zeros((2, 0), device=dev), cls.squeeze(-1)))
+                if extras:
+                    if nl and self.count_metrics is not None:      # the counting metrics compare boxes even without detections: native-space labels
+                        tbox = ops.xywh2xyxy(bbox.contiguous()) * whwh
+                        ops.scale_boxes(batch['img'][si].shape[1:], tbox, shape, ratio_pad=batch['ratio_pad'][si])
+                        labelsn = torch.cat((cls.view(-1, 1), tbox), 1)
+                    elif nl:
+                        labelsn = torch.cat((cls.view(-1, 1), torch.zeros(nl, 4, device=dev)), 1)
+                    self._update_extras(None, labelsn)
                 continue
             predn = pred.clone()
             ops.scale_boxes(batch['img'][si].shape[1:], predn, shape, ratio_pad=batch['ratio_pad'][si])      # native-space pred
@@ -64,10 +94,21 @@ class DetectionValidator:
                 ops.scale_boxes(batch['img'][si].shape[1:], tbox, shape, ratio_pad=batch['ratio_pad'][si])   # native-space labels
                 labelsn = torch.cat((cls.view(-1, 1), tbox), 1)
                 correct = self._process_batch(predn, labelsn)
+            if extras:
+                self._update_extras(predn, labelsn)
             self.stats.append((correct, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
 
     def get_stats(self):
-        """val.py:123-131 + DetMetrics.process: (tp, fp, p, r, f1, ap, ap_class) per class and the summary dict."""
+        """val.py:123-131 + DetMetrics.process: (tp, fp, p, r, f1, ap, ap_class) per class and the summary dict; with init_metrics(confusion=True /
+        counting=True) also `confusion_matrix` (the object) and the flat `metrics/count_*` keys."""
+        out = self._map_stats()
+        if self.confusion_matrix is not None:
+            out['confusion_matrix'] = self.confusion_matrix
+        if self.count_metrics is not None:
+            out.update(self.count_metrics.results_dict)
+        return out
+
+    def _map_stats(self):
         import numpy as np
         from ...utils.metrics import ap_per_class
         if not self.stats:
