@@ -16,21 +16,63 @@ struct InjArgs {
   char* y; int ysn, ysh, ysw; uint32_t y_bytes;
   const char* wpk; const float* bias;
   int N, H, W, Cin, Cout, Hg, Wg, PH, PW, tiles_x, tiles_y;
+  FastDiv fd_tx, fd_ty;                                  // patch -> (n, ty, tx) without the runtime division sequence
+  float ry, rx;                                          // (float)Hg / (float)H, (float)Wg / (float)W: the ratio inj_lerp divides out, once on the host
 };
 
 constexpr int INJ_TH = 4, INJ_TW = 16, INJ_THREADS = 256, INJ_CPAD = 8;   // channel stride of an LDS patch pixel: Cout + 8 (bank spread)
 
 // F.interpolate(bilinear, align_corners=False): src = max(0, (dst+0.5)*in/out - 0.5), upper neighbour clamped
 // (no fma contraction: the host sizes the LDS patch with this same function and must get the same integers as the device)
-__device__ __host__ inline void inj_lerp(int o, int isz, int osz, int& i0, int& i1, float& l1) {
+// inj_lerp_r takes the ratio (float)isz / (float)osz ready made: one correctly rounded division, the same bits wherever it is evaluated
+__device__ __host__ inline void inj_lerp_r(int o, float scale, int isz, int& i0, int& i1, float& l1) {
 #pragma clang fp contract(off)
-  const float scale = (float)isz / (float)osz;
   float src = scale * ((float)o + 0.5f) - 0.5f;
   if (src < 0.f) src = 0.f;
   i0 = (int)src;
   if (i0 > isz - 1) i0 = isz - 1;
   i1 = i0 + (i0 < isz - 1 ? 1 : 0);
   l1 = src - (float)i0;
+}
+__device__ __host__ inline void inj_lerp(int o, int isz, int osz, int& i0, int& i1, float& l1) {
+#pragma clang fp contract(off)
+  inj_lerp_r(o, (float)isz / (float)osz, isz, i0, i1, l1);
+}
+
+// two floats -> two bf16 (round to nearest even) in one 32-bit word, and each half of such a word back as a float
+typedef __attribute__((ext_vector_type(2))) float inj_f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 inj_bf16x2;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+__device__ __forceinline__ uint32_t inj_pk_bf16(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(inj_f32x2{lo, hi}, inj_bf16x2));
+}
+__device__ __forceinline__ float inj_bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float inj_bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+
+// One patch of the persistent loops below: image, tile, and the source rows / columns its first and last output row / column touch.  All of it
+// is wave-uniform.  pwm divides a source-pixel index by pw: p / pw == (p * pwm) >> 16 for p * pw < 65536 (pwm = 65536 / pw + 1, round-up magic).
+struct InjGeo { int n, ty, tx, py0, px0, ph, pw; uint32_t pwm; };
+__device__ __forceinline__ uint32_t inj_pw_magic(int pw) {
+  uint32_t m = (uint32_t)(65536.f * __builtin_amdgcn_rcpf((float)pw));   // 65536 / pw give or take one; the two corrections make it exact
+  m -= (m * (uint32_t)pw > 65536u);
+  m += ((m + 1) * (uint32_t)pw <= 65536u);
+  return m + 1;
+}
+template <int TH>
+__device__ __forceinline__ InjGeo inj_geom(const InjArgs& a, int patch) {
+  InjGeo q;
+  const uint32_t row = fdiv((uint32_t)patch, a.fd_tx);
+  q.tx = patch - (int)row * a.tiles_x;
+  q.n = (int)fdiv(row, a.fd_ty);
+  q.ty = (int)row - q.n * a.tiles_y;
+  int py1, px1, t0, t1; float tl;
+  inj_lerp_r(q.ty * TH, a.ry, a.Hg, q.py0, t1, tl);
+  inj_lerp_r(min(q.ty * TH + TH - 1, a.H - 1), a.ry, a.Hg, t0, py1, tl);
+  inj_lerp_r(q.tx * INJ_TW, a.rx, a.Wg, q.px0, t1, tl);
+  inj_lerp_r(min(q.tx * INJ_TW + INJ_TW - 1, a.W - 1), a.rx, a.Wg, t0, px1, tl);
+  q.ph = py1 - q.py0 + 1; q.pw = px1 - q.px0 + 1;       // <= PH, PW (host bound)
+  q.pwm = inj_pw_magic(q.pw);
+  return q;
 }
 
 template <typename T, int KC, int NB>
@@ -52,9 +94,8 @@ __global__ __launch_bounds__(INJ_THREADS) void conv1x1_inject_kernel(const InjAr
   const int npatch = a.N * a.tiles_x * a.tiles_y;
 #pragma unroll 1
   for (int patch = blockIdx.x; patch < npatch; patch += gridDim.x) {
-  int b = patch;
-  const int tx = b % a.tiles_x; b /= a.tiles_x;
-  const int ty = b % a.tiles_y, n = b / a.tiles_y;
+  const InjGeo q = inj_geom<INJ_TH>(a, patch);
+  const int n = q.n, ty = q.ty, tx = q.tx, py0 = q.py0, px0 = q.px0, ph = q.ph, pw = q.pw;
   const int oy = ty * INJ_TH + wave, ox = tx * INJ_TW + r;
   const bool pv = oy < a.H && ox < a.W;
 
@@ -66,20 +107,13 @@ __global__ __launch_bounds__(INJ_THREADS) void conv1x1_inject_kernel(const InjAr
     const int cb = (kc * 4 + g) * 16;
     P[kc] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(xrs, (cb < a.Cin * SZ) ? (uint32_t)(xo + cb) : (uint32_t)MGDT_OOB, 0, 0));
   }
-  // source patch of this workgroup: rows/cols touched by its first and last output row/col (uniform)
-  int py0, py1, px0, px1, t0, t1; float tl;
-  inj_lerp(ty * INJ_TH, a.Hg, a.H, py0, t1, tl);
-  inj_lerp(min(ty * INJ_TH + INJ_TH - 1, a.H - 1), a.Hg, a.H, t0, py1, tl);
-  inj_lerp(tx * INJ_TW, a.Wg, a.W, px0, t1, tl);
-  inj_lerp(min(tx * INJ_TW + INJ_TW - 1, a.W - 1), a.Wg, a.W, t0, px1, tl);
-  const int ph = py1 - py0 + 1, pw = px1 - px0 + 1;       // <= PH, PW (host bound)
   __syncthreads();                                         // the previous patch's tail is done with the LDS maps
   {
     constexpr int VPP = NB * 16 / 8;                        // 16-byte vectors per pixel
     const int nvec = ph * pw * VPP;
     for (int i = tid; i < nvec; i += INJ_THREADS) {
       const int v = i % VPP, p = i / VPP;
-      const int sy = p / pw, sx = p - sy * pw;
+      const int sy = (int)(((uint32_t)p * q.pwm) >> 16), sx = p - sy * pw;
       const long go = (long)n * a.gsn + (long)(py0 + sy) * a.gsh + (long)(px0 + sx) * a.gsw + v * 16;
       const uint4 va = *(const uint4*)(a.ga + go), vf = *(const uint4*)(a.gf + go);
       *(uint4*)((char*)sg + ((size_t)p * CS + v * 8) * SZ) = va;
@@ -98,8 +132,8 @@ __global__ __launch_bounds__(INJ_THREADS) void conv1x1_inject_kernel(const InjAr
 
   // bilinear taps of my pixel inside the patch
   int y0, y1, x0, x1; float wy1, wx1;
-  inj_lerp(min(oy, a.H - 1), a.Hg, a.H, y0, y1, wy1);
-  inj_lerp(min(ox, a.W - 1), a.Wg, a.W, x0, x1, wx1);
+  inj_lerp_r(min(oy, a.H - 1), a.ry, a.Hg, y0, y1, wy1);
+  inj_lerp_r(min(ox, a.W - 1), a.rx, a.Wg, x0, x1, wx1);
   const int o00 = ((y0 - py0) * pw + (x0 - px0)) * CS + 4 * g, o01 = ((y0 - py0) * pw + (x1 - px0)) * CS + 4 * g;
   const int o10 = ((y1 - py0) * pw + (x0 - px0)) * CS + 4 * g, o11 = ((y1 - py0) * pw + (x1 - px0)) * CS + 4 * g;
   const int yo = pv ? n * a.ysn + oy * a.ysh + ox * a.ysw : MGDT_OOB;
@@ -196,60 +230,56 @@ __global__ __launch_bounds__(64 * TH) void conv1x1_inject_conv_kernel(const InjC
   static_assert(!GCONV || (2 * NB) % TH == 0, "cout blocks per wave");
   constexpr int GB = GCONV ? (2 * NB) / TH : 1;
   bf16x8 Ag[GB];
-  f32x4 bg[GB];
   if (GCONV) {
 #pragma unroll
-    for (int t = 0; t < GB; ++t) {
-      Ag[t] = *(const bf16x8*)(A.wg + ((size_t)(wave * GB + t) * 64 + lane) * 16);
-      bg[t] = *(const f32x4*)(A.bias_g + (wave * GB + t) * 16 + 4 * g);
-    }
+    for (int t = 0; t < GB; ++t) Ag[t] = *(const bf16x8*)(A.wg + ((size_t)(wave * GB + t) * 64 + lane) * 16);
   }
   const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void*)(GCONV ? A.gx : a.x), 0, GCONV ? A.gx_bytes : 0u, 0x00020000);
   const int npatch = a.N * a.tiles_x * a.tiles_y;
   // Everything a patch reads from HBM - this lane's x fragments and (GCONV) the source pixels of the global convs - is requested ONE PATCH
   // AHEAD, right after the LDS patch of the current one is built: with one 8-wave workgroup per CU nothing else hides that round trip.
   constexpr int NG = 4;                                    // 16-pixel groups of a source patch (host: PH * PW <= 64)
-  auto geom = [&](int patch, int& n, int& ty, int& tx, int& py0, int& px0, int& ph, int& pw) __attribute__((always_inline)) {
-    int b = patch;
-    tx = b % a.tiles_x; b /= a.tiles_x;
-    ty = b % a.tiles_y; n = b / a.tiles_y;
-    int py1, px1, t0, t1; float tl;
-    inj_lerp(ty * TH, a.Hg, a.H, py0, t1, tl);
-    inj_lerp(min(ty * TH + TH - 1, a.H - 1), a.Hg, a.H, t0, py1, tl);
-    inj_lerp(tx * INJ_TW, a.Wg, a.W, px0, t1, tl);
-    inj_lerp(min(tx * INJ_TW + INJ_TW - 1, a.W - 1), a.Wg, a.W, t0, px1, tl);
-    ph = py1 - py0 + 1; pw = px1 - px0 + 1;
-  };
-  auto request = [&](int patch, frag(&Pq)[KC], frag(&Bq)[NG]) __attribute__((always_inline)) {
-    int n, ty, tx, py0, px0, ph, pw;
+  // GCONV: the two global convs run with the operands swapped - source pixels on the M side, this wave's output channels on the N side - so that a
+  // lane ends with FOUR CONSECUTIVE source pixels of ONE channel: 8 contiguous bytes of that channel's fragment slot, one 8-byte LDS store per
+  // (group, block) where the channel-major form needed four 2-byte ones.  The bias is then the lane's channel's.
+  f32x4 bgl[GB];
+  if (GCONV) {
+#pragma unroll
+    for (int t = 0; t < GB; ++t) {
+      const float b = A.bias_g[(wave * GB + t) * 16 + r];
+      bgl[t] = f32x4{b, b, b, b};
+    }
+  }
+  // The geometry of a patch is worked out ONCE, when its reads are requested, and carried into the iteration that consumes them.
+  auto request = [&](int patch, InjGeo& gq, frag(&Pq)[KC], frag(&Bq)[NG]) __attribute__((always_inline)) {
     const bool live = patch < npatch;
-    geom(live ? patch : 0, n, ty, tx, py0, px0, ph, pw);
-    const int oy = ty * TH + wave, ox = tx * INJ_TW + r;
-    const int xo = (live && oy < a.H && ox < a.W) ? n * a.xsn + oy * a.xsh + ox * a.xsw : MGDT_OOB;
+    gq = inj_geom<TH>(a, live ? patch : 0);
+    const int oy = gq.ty * TH + wave, ox = gq.tx * INJ_TW + r;
+    const int xo = (live && oy < a.H && ox < a.W) ? gq.n * a.xsn + oy * a.xsh + ox * a.xsw : MGDT_OOB;
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int cb = (kc * 4 + g) * 16;
       Pq[kc] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(xrs, (cb < a.Cin * SZ) ? (uint32_t)(xo + cb) : (uint32_t)MGDT_OOB, 0, 0));
     }
     if (GCONV) {
-      const int npx = ph * pw;
+      const int npx = gq.ph * gq.pw;
+      const int gbase = gq.n * A.gxsn + gq.py0 * A.gxsh + gq.px0 * A.gxsw + g * 16;
 #pragma unroll
       for (int grp = 0; grp < NG; ++grp) {
         const int p = grp * 16 + r;
-        const bool v_ = live && p < npx;
-        const int sy = (v_ ? p : 0) / pw, sx = (v_ ? p : 0) - sy * pw;
-        const uint32_t go = v_ ? (uint32_t)(n * A.gxsn + (py0 + sy) * A.gxsh + (px0 + sx) * A.gxsw + g * 16) : (uint32_t)MGDT_OOB;
-        Bq[grp] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(grs, go, 0, 0));      // 32 input channels = one K chunk
+        const int sy = (int)(((uint32_t)p * gq.pwm) >> 16), sx = p - sy * gq.pw;
+        const uint32_t go = (live && p < npx) ? (uint32_t)(gbase + sy * A.gxsh + sx * A.gxsw) : (uint32_t)MGDT_OOB;
+        Bq[grp] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(grs, go, 0, 0));      // 32 input channels = one K chunk; zeros past the patch
       }
     }
   };
   frag P[KC], Pn[KC], Bgc[NG], Bgn[NG];
-  request((int)blockIdx.x, P, Bgc);
+  InjGeo q, qn;
+  request((int)blockIdx.x, q, P, Bgc);
 #pragma unroll 1
   for (int patch = blockIdx.x; patch < npatch; patch += gridDim.x) {
-    int n, ty, tx, py0, px0, ph, pw;
-    geom(patch, n, ty, tx, py0, px0, ph, pw);
-    const int oy = ty * TH + wave, ox = tx * INJ_TW + r;
+    const int n = q.n, py0 = q.py0, px0 = q.px0, ph = q.ph, pw = q.pw;
+    const int oy = q.ty * TH + wave, ox = q.tx * INJ_TW + r;
     const bool pv = oy < a.H && ox < a.W;
     __syncthreads();                                       // the previous patch's tail is done with the LDS maps
     if (GCONV) {
@@ -257,21 +287,20 @@ __global__ __launch_bounds__(64 * TH) void conv1x1_inject_conv_kernel(const InjC
 #pragma unroll
       for (int grp = 0; grp < NG; ++grp) {
         if (grp * 16 >= npx) break;                          // uniform
-        const int p = grp * 16 + r;
-        const bool v_ = p < npx;
         const frag Bg = Bgc[grp];
 #pragma unroll
         for (int t = 0; t < GB; ++t) {
           const int nbg = wave * GB + t;                    // uniform
-          const f32x4 o = mma(Ag[t], Bg, bg[t]);
+          const f32x4 o = mma(Bg, Ag[t], bgl[t]);           // o[i] = map[source pixel grp*16 + 4g + i][channel nbg*16 + r]
           const bool gate = nbg < NB;                        // uniform
-          char* base = (gate ? hgT : gfT) + ((size_t)((nbg % NB) * 2 + (p >> 5)) * 64 + ((p & 31) >> 3) * 16 + 4 * g) * 16 + (p & 7) * 2;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float v = (float)(bf16)o[i];                     // the stored (rounded) global map value
-            if (gate) v = fminf(fmaxf(fmaf(v, 1.f / 6.f, 0.5f), 0.f), 1.f);      // h_sigmoid (block.py:344-350) before the interpolation (block.py:393)
-            if (v_) *(bf16*)(base + i * 16) = (bf16)v;       // lane slot (r = 4g + i, g' = source pixel / 8), element = source pixel % 8
+          uint2 w = make_uint2(inj_pk_bf16(o[0], o[1]), inj_pk_bf16(o[2], o[3]));      // the stored (rounded) global map values
+          if (gate) {                                        // h_sigmoid (block.py:344-350) before the interpolation (block.py:393), rounded once more
+            auto hsig = [](float v) __attribute__((always_inline)) { return fminf(fmaxf(fmaf(v, 1.f / 6.f, 0.5f), 0.f), 1.f); };
+            w = make_uint2(inj_pk_bf16(hsig(inj_bf16_lo(w.x)), hsig(inj_bf16_hi(w.x))), inj_pk_bf16(hsig(inj_bf16_lo(w.y)), hsig(inj_bf16_hi(w.y))));
           }
+          // fragment (nbg % NB, kc = grp / 2), lane slot (r, g' = source pixel % 32 / 8), elements source pixel % 8 = 4 * (g & 1) .. + 3.  Source pixels
+          // past the patch get the bias (their reads returned zeros): finite, and every tap weight they meet is zero
+          *(uint2*)((gate ? hgT : gfT) + ((size_t)((nbg % NB) * 2 + (grp >> 1)) * 64 + ((grp & 1) * 2 + (g >> 1)) * 16 + r) * 16 + 8 * (g & 1)) = w;
         }
       }
     } else {
@@ -279,15 +308,15 @@ __global__ __launch_bounds__(64 * TH) void conv1x1_inject_conv_kernel(const InjC
       const int nvec = ph * pw * VPP;
       for (int i = tid; i < nvec; i += THREADS) {
         const int v = i % VPP, p = i / VPP;
-        const int sy = p / pw, sx = p - sy * pw;
+        const int sy = (int)(((uint32_t)p * q.pwm) >> 16), sx = p - sy * pw;
         const long go = (long)n * a.gsn + (long)(py0 + sy) * a.gsh + (long)(px0 + sx) * a.gsw + v * 16;
         const uint4 va = *(const uint4*)(a.ga + go), vf = *(const uint4*)(a.gf + go);
         *(uint4*)((char*)sg + ((size_t)p * CS + v * 8) * SZ) = va;
         *(uint4*)((char*)sf + ((size_t)p * CS + v * 8) * SZ) = vf;
       }
     }
-    request(patch + (int)gridDim.x, Pn, Bgn);              // the next patch's HBM reads fly under this patch's GEMMs and tail
-    __syncthreads();
+    request(patch + (int)gridDim.x, qn, Pn, Bgn);          // the next patch's HBM reads fly under this patch's GEMMs and tail
+    // the local GEMM needs registers and the weight panel only: it runs BEFORE the barrier, under the other waves' share of the patch build
     f32x4 acc[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[nb] = *(const f32x4*)(a.bias + nb * 16 + 4 * g);
@@ -296,8 +325,45 @@ __global__ __launch_bounds__(64 * TH) void conv1x1_inject_conv_kernel(const InjC
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) acc[nb] = mma(*(const frag*)(wlane + (kc * NB + nb) * 1024), P[kc], acc[nb]);
     int y0, y1, x0, x1; float wy1, wx1;
-    inj_lerp(min(oy, a.H - 1), a.Hg, a.H, y0, y1, wy1);
-    inj_lerp(min(ox, a.W - 1), a.Wg, a.W, x0, x1, wx1);
+    inj_lerp_r(min(oy, a.H - 1), a.ry, a.Hg, y0, y1, wy1);
+    inj_lerp_r(min(ox, a.W - 1), a.rx, a.Wg, x0, x1, wx1);
+    // GCONV: this lane's pixel as an interpolation B operand: its four tap weights at their source-pixel slots (coinciding taps add up), zeros elsewhere.
+    // Taps that share a slot are summed first, in the order ((w00 + w01) + w10) + w11, and the later one is retired; the (up to) four sums are rounded
+    // to bf16 once and each lands in the 32-bit word of its slot: 2 compare-selects per tap and word instead of 4 compare-select-adds + a rounding per
+    // slot.  Slot s belongs to lane group (s % 32) / 8, K chunk s / 32, element s % 8: relative to this lane's first slot (8g) that is word
+    // (s - 8g) >> 1 of 0..3 (chunk 0) or 16..19 (chunk 1), anything else is another lane's.
+    frag WB[2];
+    if (GCONV) {
+      const int dy = (y1 - y0) * pw, dx = x1 - x0;           // x1 - x0 and y1 - y0 are 0 or 1; pw == 1 implies dx == 0, so dx == dy needs both 0
+      const int s00 = (y0 - py0) * pw + (x0 - px0) - 8 * g;
+      const float w00 = (1.f - wy1) * (1.f - wx1), w01 = (1.f - wy1) * wx1, w10 = wy1 * (1.f - wx1), w11 = wy1 * wx1;
+      float m0, m1, m2, m3;                                  // merged weights of slots s00, s00 + dx, s00 + dy, s00 + dy + dx
+      {
+#pragma clang fp contract(off)                             // plain sums of the rounded products, as the per-slot form had them
+        if (dx == 0 && dy == 0) { m0 = w00 + w01 + w10 + w11; m1 = m2 = m3 = 0.f; }
+        else if (dx == 0) { m0 = w00 + w01; m2 = w10 + w11; m1 = m3 = 0.f; }
+        else if (dy == 0) { m0 = w00 + w10; m1 = w01 + w11; m2 = m3 = 0.f; }
+        else { m0 = w00; m1 = w01; m2 = w10; m3 = w11; }
+      }
+      const int sl[4] = {s00, dx ? s00 + dx : -2, dy ? s00 + dy : -2, (dx && dy) ? s00 + dy + dx : -2};      // -2: retired (word -1 matches nothing)
+      const float mw[4] = {m0, m1, m2, m3};
+      int wd[4]; uint32_t bits[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        wd[t] = sl[t] >> 1;
+        bits[t] = (uint32_t)__builtin_bit_cast(unsigned short, (bf16)mw[t]) << ((sl[t] & 1) * 16);
+      }
+#pragma unroll
+      for (int kc = 0; kc < 2; ++kc) {
+        u32x4 wv;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          wv[k] = (wd[0] == kc * 16 + k ? bits[0] : 0u) | (wd[1] == kc * 16 + k ? bits[1] : 0u) | (wd[2] == kc * 16 + k ? bits[2] : 0u) |
+                  (wd[3] == kc * 16 + k ? bits[3] : 0u);
+        WB[kc] = __builtin_bit_cast(frag, wv);
+      }
+    }
+    __syncthreads();                                       // the patch is built
     const int o00 = ((y0 - py0) * pw + (x0 - px0)) * CS + 4 * g, o01 = ((y0 - py0) * pw + (x1 - px0)) * CS + 4 * g;
     const int o10 = ((y1 - py0) * pw + (x0 - px0)) * CS + 4 * g, o11 = ((y1 - py0) * pw + (x1 - px0)) * CS + 4 * g;
     auto ld = [&](const T* base, int off) __attribute__((always_inline)) {
@@ -313,47 +379,35 @@ __global__ __launch_bounds__(64 * TH) void conv1x1_inject_conv_kernel(const InjC
     f32x4 acc2[NB2];
 #pragma unroll
     for (int nb = 0; nb < NB2; ++nb) acc2[nb] = *(const f32x4*)(A.bias2 + nb * 16 + 4 * g);
-    // GCONV: this lane's pixel as an interpolation B operand: its four tap weights at their source-pixel slots (coinciding taps add up), zeros elsewhere
-    frag WB[2];
-    if (GCONV) {
-      const int s00 = (y0 - py0) * pw + (x0 - px0), s01 = (y0 - py0) * pw + (x1 - px0), s10 = (y1 - py0) * pw + (x0 - px0), s11 = (y1 - py0) * pw + (x1 - px0);
-      const float w00 = (1.f - wy1) * (1.f - wx1), w01 = (1.f - wy1) * wx1, w10 = wy1 * (1.f - wx1), w11 = wy1 * wx1;
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int sidx = kc * 32 + 8 * g + e;
-          const float w = (sidx == s00 ? w00 : 0.f) + (sidx == s01 ? w01 : 0.f) + (sidx == s10 ? w10 : 0.f) + (sidx == s11 ? w11 : 0.f);
-          WB[kc][e] = (bf16)w;
-        }
-    }
     const char* const hglane = hgT + lane * 16;
     const char* const gflane = gfT + lane * 16;
 #pragma unroll
     for (int j = 0; j < KC2; ++j) {
-      frag B2;
+      u32x4 B2w;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
+        const int nb = 2 * j + h;
+        f32x4 sig, feat;
         if constexpr (GCONV) {
-          const int nb = 2 * j + h;
-          f32x4 sig = f32x4{0.f, 0.f, 0.f, 0.f}, feat = f32x4{0.f, 0.f, 0.f, 0.f};
+          sig = f32x4{0.f, 0.f, 0.f, 0.f}; feat = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int kc = 0; kc < 2; ++kc) {
             sig = mma(*(const frag*)(hglane + (nb * 2 + kc) * 1024), WB[kc], sig);
             feat = mma(*(const frag*)(gflane + (nb * 2 + kc) * 1024), WB[kc], feat);
           }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) B2[h * 4 + i] = (T)((float)(T)acc[nb][i] * sig[i] + feat[i]);
-          continue;
+        } else {
+          const int c = nb * 16;
+          sig = (hs(ld(sg, o00 + c)) * (1.f - wx1) + hs(ld(sg, o01 + c)) * wx1) * (1.f - wy1) +
+                (hs(ld(sg, o10 + c)) * (1.f - wx1) + hs(ld(sg, o11 + c)) * wx1) * wy1;
+          feat = (ld(sf, o00 + c) * (1.f - wx1) + ld(sf, o01 + c) * wx1) * (1.f - wy1) +
+                 (ld(sf, o10 + c) * (1.f - wx1) + ld(sf, o11 + c) * wx1) * wy1;
         }
-        const int c = (2 * j + h) * 16;
-        const f32x4 sig = (hs(ld(sg, o00 + c)) * (1.f - wx1) + hs(ld(sg, o01 + c)) * wx1) * (1.f - wy1) +
-                          (hs(ld(sg, o10 + c)) * (1.f - wx1) + hs(ld(sg, o11 + c)) * wx1) * wy1;
-        const f32x4 feat = (ld(sf, o00 + c) * (1.f - wx1) + ld(sf, o01 + c) * wx1) * (1.f - wy1) +
-                           (ld(sf, o10 + c) * (1.f - wx1) + ld(sf, o11 + c) * wx1) * wy1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) B2[h * 4 + i] = (T)((float)(T)acc[2 * j + h][i] * sig[i] + feat[i]);   // both roundings of the unfused pair
+        // both roundings of the unfused pair (the local map, then the injected one), two values per conversion
+        const uint32_t a01 = inj_pk_bf16(acc[nb][0], acc[nb][1]), a23 = inj_pk_bf16(acc[nb][2], acc[nb][3]);
+        B2w[h * 2] = inj_pk_bf16(inj_bf16_lo(a01) * sig[0] + feat[0], inj_bf16_hi(a01) * sig[1] + feat[1]);
+        B2w[h * 2 + 1] = inj_pk_bf16(inj_bf16_lo(a23) * sig[2] + feat[2], inj_bf16_hi(a23) * sig[3] + feat[3]);
       }
+      const frag B2 = __builtin_bit_cast(frag, B2w);
 #pragma unroll
       for (int nb = 0; nb < NB2; ++nb) acc2[nb] = mma(*(const frag*)(w2lane + (j * NB2 + nb) * 1024), B2, acc2[nb]);
     }
@@ -370,6 +424,7 @@ __global__ __launch_bounds__(64 * TH) void conv1x1_inject_conv_kernel(const InjC
     for (int kc = 0; kc < KC; ++kc) P[kc] = Pn[kc];
 #pragma unroll
     for (int grp = 0; grp < NG; ++grp) Bgc[grp] = Bgn[grp];
+    q = qn;
   }
 }
 
@@ -436,6 +491,8 @@ extern "C" int mgdt_conv1x1_inject_fwd(const mgdt_view* x, const void* packed_w,
   a.N = y->n; a.H = y->h; a.W = y->w; a.Cin = x->c; a.Cout = y->c; a.Hg = ga->h; a.Wg = ga->w;
   inj_patch(a.H, a.W, a.Hg, a.Wg, &a.PH, &a.PW);
   a.tiles_x = cdiv(a.W, INJ_TW); a.tiles_y = cdiv(a.H, INJ_TH);
+  a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_ty = make_fastdiv((uint32_t)a.tiles_y);
+  a.ry = (float)a.Hg / (float)a.H; a.rx = (float)a.Wg / (float)a.W;
   const int kc = inj_kc(a.Cin), nb = a.Cout / 16;
   const size_t lds = inj_lds(kc, nb, a.PH, a.PW);
   hipStream_t st = (hipStream_t)s;
@@ -528,6 +585,8 @@ extern "C" int mgdt_conv1x1_inject_conv_fwd(const mgdt_view* x, const void* pack
   a.N = x->n; a.H = x->h; a.W = x->w; a.Cin = x->c; a.Cout = ga->c; a.Hg = ga->h; a.Wg = ga->w;
   inj_patch_th(a.H, a.W, a.Hg, a.Wg, INJ2_TH, &a.PH, &a.PW);
   a.tiles_x = cdiv(a.W, INJ_TW); a.tiles_y = cdiv(a.H, INJ2_TH);
+  a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_ty = make_fastdiv((uint32_t)a.tiles_y);
+  a.ry = (float)a.Hg / (float)a.H; a.rx = (float)a.Wg / (float)a.W;
   A.w2 = (const char*)packed_w2; A.bias2 = bias2; A.act2 = act2; A.C2 = y2->c;
   A.y2 = (char*)y2->p; A.y2sn = (int)(y2->sn * sz); A.y2sh = (int)(y2->sh * sz); A.y2sw = (int)(y2->sw * sz); A.y2_bytes = (uint32_t)ext(y2);
   const int kc = inj_kc(a.Cin), nb2 = cdiv(y2->c, 16);
