@@ -535,6 +535,30 @@ int mgdt_ema_update(float* ema, const float* p, long n, float decay, mgdt_stream
  * buffers (EMA only; ema may be NULL).  Reference: yolo/engine/trainer.py:317-326 (warm-up values), :462-470, yolo/utils/torch_utils.py:342. */
 int mgdt_sgd_ema_step_dev(float* p, const float* g, float* buf, const float* wd, long n_param, float* ema, long n_total, const float* hyper4,
                           int nesterov, int first, const float* clip2, mgdt_stream s);
+/* Adam / AdamW / RMSProp on the same flat buffers (build_optimizer yolo/engine/trainer.py:651-654; `optimizer: auto` -> AdamW, :635-639), in
+ * the operation order of torch's single-tensor path, one fp32 rounding per operation.  wd and clip2 as for mgdt_sgd_step (wd > 0 decayed group,
+ * wd == 0 norm group, wd < 0 bias group stepping with lr_bias; either may be NULL).  Host scalars are doubles (Python floats); the entry points
+ * derive 1 - beta, lr / bc1 and sqrt(bc2) in double, as torch does, and hand them to the kernel rounded to fp32 once.
+ * adam: m = exp_avg, v = exp_avg_sq, step 1-based (bc1 = 1 - beta1^step, bc2 = 1 - beta2^step).  decoupled = 0 is torch.optim.Adam
+ *   (g' = clip*g + wd*p), 1 is AdamW (p *= 1 - lr*wd, g' = clip*g); then m += (g' - m)*(1 - beta1); v = beta2*v + (1 - beta2)*g'*g';
+ *   p -= (lr_group / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).  No amsgrad, no maximize.
+ * rmsprop: torch.optim.RMSprop(centered=False): g' = clip*g + wd*p; sq = alpha*sq + (1 - alpha)*g'*g'; avg = sqrt(sq) + eps; with momentum > 0
+ *   buf = momentum*buf + g'/avg, p -= lr_group*buf; else p -= lr_group*g'/avg (buf is then not touched and may be NULL).
+ * *_ema_step_dev: the captured-step forms, bit-equal to the eager form followed by mgdt_ema_update: per-step scalars from device memory,
+ *   [0, n_param) parameters (step, then EMA of the new value), [n_param, n_total) buffers (EMA only); ema may be NULL.  hyper8 (fp32[8], all eight
+ *   readable; a family ignores what it has no use for):
+ *     [0] lr  [1] lr_bias  [2] beta1 (Adam) / momentum (RMSProp)  [3] ema_decay  [4] lr / bc1  [5] lr_bias / bc1  [6] sqrt(bc2)  [7] 1 - beta1
+ *   beta2 / alpha and eps are constants of a run and stay arguments.  Streaming kernels: 16-byte accesses when every array is 16-byte aligned
+ *   (scalar otherwise), 10 words per parameter with all four state arrays.                                                                     */
+#define MGDT_OPT_HYPER_LEN 8
+int mgdt_adam_step(float* p, const float* g, float* m, float* v, const float* wd, long n, double lr, double lr_bias, double beta1,
+                   double beta2, double eps, int step, int decoupled, const float* clip2, mgdt_stream s);
+int mgdt_adam_ema_step_dev(float* p, const float* g, float* m, float* v, const float* wd, long n_param, float* ema, long n_total,
+                           const float* hyper8, double beta2, double eps, int decoupled, const float* clip2, mgdt_stream s);
+int mgdt_rmsprop_step(float* p, const float* g, float* sq, float* buf, const float* wd, long n, double lr, double lr_bias, double alpha,
+                      double eps, double momentum, const float* clip2, mgdt_stream s);
+int mgdt_rmsprop_ema_step_dev(float* p, const float* g, float* sq, float* buf, const float* wd, long n_param, float* ema, long n_total,
+                              const float* hyper8, double alpha, double eps, int with_momentum, const float* clip2, mgdt_stream s);
 
 /* ---- box helpers, validator reductions, predictor preprocess; fp32 boxes, rows of `row` >= 4 floats ------------
  * box_convert: mode 0 = xywh2xyxy (yolo/utils/ops.py:362-377), 1 = xyxy2xywh (:345-359); columns >= 4 are copied.

@@ -149,6 +149,10 @@ PROTOTYPES = {
     'mgdt_sgd_step': (_i, [_vp, _vp, _vp, _vp, C.c_long, _f, _f, _f, _i, _i, _vp, _vp]),
     'mgdt_ema_update': (_i, [_vp, _vp, C.c_long, _f, _vp]),
     'mgdt_sgd_ema_step_dev': (_i, [_vp, _vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, _i, _i, _vp, _vp]),
+    'mgdt_adam_step': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_long] + [C.c_double] * 5 + [_i, _i, _vp, _vp]),
+    'mgdt_adam_ema_step_dev': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_double, C.c_double, _i, _vp, _vp]),
+    'mgdt_rmsprop_step': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_long] + [C.c_double] * 5 + [_vp, _vp]),
+    'mgdt_rmsprop_ema_step_dev': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_double, C.c_double, _i, _vp, _vp]),
     'mgdt_box_convert': (_i, [_vp, _vp, C.c_long, _i, _i, _vp]),
     'mgdt_box_iou': (_i, [_vp, _i, _vp, _i, _f, _vp, _vp]),
     'mgdt_bbox_iou': (_i, [_vp, _i, _vp, _i, C.c_long, _i, _i, _f, _vp, _vp]),

@@ -103,3 +103,166 @@ extern "C" int mgdt_sgd_ema_step_dev(float* p, const float* g, float* buf, const
   MGDT_CHECK_LAUNCH("sgd_ema_step_dev");
   return MGDT_OK;
 }
+
+// ---- Adam / AdamW / RMSProp on the same flat buffers ---------------------------------------------------------------------------------------
+// The reference's build_optimizer (yolo/engine/trainer.py:651-656) picks torch.optim.Adam / AdamW / RMSprop by name; `optimizer: auto` resolves to
+// AdamW for short runs (:635-639).  The arithmetic below is torch's single-tensor path, one rounding per operation (this file is built without
+// contraction).  Streaming kernels: 10 words per parameter (p, m, v, ema read and written; g, wd read), one 16-byte load / store per lane and
+// array where the four elements lie on one side of n_param, a scalar evaluation of the same element function for the straddling quad and the
+// tail - so the vector and the scalar path, and the eager and the captured-step form (one kernel, scalars from arguments or from `hyper`),
+// agree bit for bit.  No LDS, no scratch.
+//
+// hyper (fp32[8], MGDT_OPT_HYPER_LEN), shared by both families; a family ignores the slots it has no use for:
+//   [0] lr   [1] lr_bias   [2] beta1 (Adam) / momentum (RMSProp)   [3] ema_decay
+//   [4] lr / bc1   [5] lr_bias / bc1   [6] sqrt(bc2)   [7] 1 - beta1          (bc1 = 1 - beta1^step, bc2 = 1 - beta2^step; Adam only)
+struct OptScalars {
+  float lr, lr_bias, mom, d;              // hyper[0..3]
+  float step, step_bias, sqrt_bc2, omb1;  // hyper[4..7]
+  float beta2, omb2, eps;                 // constants of a run: beta2 / alpha, 1 - beta2 / 1 - alpha, eps
+  int flag;                               // Adam: decoupled weight decay (AdamW)
+};
+__device__ __forceinline__ void opt_load_hyper(OptScalars& a, const float* __restrict__ hyper) {
+  if (!hyper) return;
+  a.lr = hyper[0]; a.lr_bias = hyper[1]; a.mom = hyper[2]; a.d = hyper[3];
+  a.step = hyper[4]; a.step_bias = hyper[5]; a.sqrt_bc2 = hyper[6]; a.omb1 = hyper[7];
+}
+struct AdamElem {
+  static constexpr bool HAS_M = true;
+  // Adam: g' = c*g + wd*p; AdamW: p *= 1 - lr*wd, g' = c*g.  m.lerp_(g', 1 - beta1); v.mul_(beta2).addcmul_(g', g', 1 - beta2);
+  // denom = sqrt(v) / sqrt(bc2) + eps; p.addcdiv_(m, denom, -lr / bc1)
+  static __device__ __forceinline__ void run(float& p, float g, float& m, float& v, float w, const OptScalars& a, float c) {
+    float gi = c * g;
+    if (w > 0.f) { if (a.flag) p *= 1.f - a.lr * w; else gi += w * p; }
+    m += (gi - m) * a.omb1;
+    v = a.beta2 * v + (a.omb2 * gi) * gi;
+    const float denom = sqrtf(v) / a.sqrt_bc2 + a.eps;
+    p -= ((w < 0.f ? a.step_bias : a.step) * m) / denom;
+  }
+};
+template <bool MOM> struct RmsElem {
+  // g' = c*g + wd*p; sq.mul_(alpha).addcmul_(g', g', 1 - alpha); avg = sqrt(sq) + eps; momentum: buf.mul_(momentum).addcdiv_(g', avg),
+  // p.add_(buf, -lr); else p.addcdiv_(g', avg, -lr).  m is the momentum buffer (neither read nor written without momentum), v the square average.
+  static constexpr bool HAS_M = MOM;
+  static __device__ __forceinline__ void run(float& p, float g, float& m, float& v, float w, const OptScalars& a, float c) {
+    float gi = c * g;
+    if (w > 0.f) gi += w * p;
+    v = a.beta2 * v + (a.omb2 * gi) * gi;
+    const float avg = sqrtf(v) + a.eps;
+    const float lr = w < 0.f ? a.lr_bias : a.lr;
+    if (MOM) { m = a.mom * m + gi / avg; p -= lr * m; }
+    else p -= (lr * gi) / avg;
+  }
+};
+#define OPT_GRID_CAP 2048
+template <class E>
+__global__ __launch_bounds__(OPT_BLOCK) void moment_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                                const float* __restrict__ wd, long n_param, float* __restrict__ ema, long n_total, long nq,
+                                                                OptScalars a, const float* __restrict__ hyper, const float* __restrict__ clip) {
+  opt_load_hyper(a, hyper);
+  const float c = clip ? clip[1] : 1.f;
+  const long t0 = blockIdx.x * (long)OPT_BLOCK + threadIdx.x, stride = (long)gridDim.x * OPT_BLOCK;
+  for (long q = t0; q < nq; q += stride) {           // nq quads of four elements, every array 16-byte aligned (0 when one is not)
+    const long i = q * 4;
+    if (i + 4 <= n_param) {
+      float4 P = *(const float4*)(p + i), V = *(const float4*)(v + i), M = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (E::HAS_M) M = *(const float4*)(m + i);
+      const float4 G = *(const float4*)(g + i);
+      float4 W = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (wd) W = *(const float4*)(wd + i);
+      E::run(P.x, G.x, M.x, V.x, W.x, a, c);
+      E::run(P.y, G.y, M.y, V.y, W.y, a, c);
+      E::run(P.z, G.z, M.z, V.z, W.z, a, c);
+      E::run(P.w, G.w, M.w, V.w, W.w, a, c);
+      *(float4*)(p + i) = P; *(float4*)(v + i) = V;
+      if (E::HAS_M) *(float4*)(m + i) = M;
+      if (ema) {
+        float4 Q = *(const float4*)(ema + i);
+        Q.x = a.d * Q.x + (1.f - a.d) * P.x; Q.y = a.d * Q.y + (1.f - a.d) * P.y;
+        Q.z = a.d * Q.z + (1.f - a.d) * P.z; Q.w = a.d * Q.w + (1.f - a.d) * P.w;
+        *(float4*)(ema + i) = Q;
+      }
+    } else if (i >= n_param) {                       // float buffers (batch-norm statistics): EMA only
+      if (ema) {
+        const float4 P = *(const float4*)(p + i);
+        float4 Q = *(const float4*)(ema + i);
+        Q.x = a.d * Q.x + (1.f - a.d) * P.x; Q.y = a.d * Q.y + (1.f - a.d) * P.y;
+        Q.z = a.d * Q.z + (1.f - a.d) * P.z; Q.w = a.d * Q.w + (1.f - a.d) * P.w;
+        *(float4*)(ema + i) = Q;
+      }
+    } else {                                         // the one quad that straddles n_param
+      for (long j = i; j < i + 4; ++j) {
+        float x = p[j];
+        if (j < n_param) {
+          float mj = E::HAS_M ? m[j] : 0.f, vj = v[j];
+          E::run(x, g[j], mj, vj, wd ? wd[j] : 0.f, a, c);
+          p[j] = x; v[j] = vj;
+          if (E::HAS_M) m[j] = mj;
+        }
+        if (ema) ema[j] = a.d * ema[j] + (1.f - a.d) * x;
+      }
+    }
+  }
+  for (long j = nq * 4 + t0; j < n_total; j += stride) {      // tail (n_total % 4 elements), or everything when an array is not 16-byte aligned
+    float x = p[j];
+    if (j < n_param) {
+      float mj = E::HAS_M ? m[j] : 0.f, vj = v[j];
+      E::run(x, g[j], mj, vj, wd ? wd[j] : 0.f, a, c);
+      p[j] = x; v[j] = vj;
+          if (E::HAS_M) m[j] = mj;
+    }
+    if (ema) ema[j] = a.d * ema[j] + (1.f - a.d) * x;
+  }
+}
+template <class E>
+static int moment_launch(const char* what, float* p, const float* g, float* m, float* v, const float* wd, long n_param, float* ema, long n_total,
+                         const OptScalars& a, const float* hyper, const float* clip2, mgdt_stream s) {
+  const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)wd | (uintptr_t)ema;      // NULL contributes nothing
+  const long nq = (bits & 15) ? 0 : n_total / 4;
+  const long work = nq + (n_total - nq * 4);
+  const int nb = (int)std::min<long>((work + OPT_BLOCK - 1) / OPT_BLOCK, OPT_GRID_CAP);
+  moment_flat_kernel<E><<<nb, OPT_BLOCK, 0, (hipStream_t)s>>>(p, g, m, v, wd, n_param, ema, n_total, nq, a, hyper, clip2);
+  MGDT_CHECK_LAUNCH(what);
+  return MGDT_OK;
+}
+// lr / bc1 and sqrt(bc2) in double, as torch's _single_tensor_adam computes them in Python floats, then rounded to fp32 once
+static OptScalars adam_scalars(double lr, double lr_bias, double beta1, double beta2, double eps, int step, int decoupled) {
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  OptScalars a;
+  a.lr = (float)lr; a.lr_bias = (float)lr_bias; a.mom = (float)beta1; a.d = 0.f;
+  a.step = (float)(lr / bc1); a.step_bias = (float)(lr_bias / bc1); a.sqrt_bc2 = (float)sqrt(bc2); a.omb1 = (float)(1.0 - beta1);
+  a.beta2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.flag = decoupled ? 1 : 0;
+  return a;
+}
+static OptScalars rms_scalars(double lr, double lr_bias, double alpha, double eps, double momentum) {
+  OptScalars a;
+  a.lr = (float)lr; a.lr_bias = (float)lr_bias; a.mom = (float)momentum; a.d = 0.f;
+  a.step = a.step_bias = 0.f; a.sqrt_bc2 = 1.f; a.omb1 = 0.f;
+  a.beta2 = (float)alpha; a.omb2 = (float)(1.0 - alpha); a.eps = (float)eps; a.flag = 0;
+  return a;
+}
+extern "C" int mgdt_adam_step(float* p, const float* g, float* m, float* v, const float* wd, long n, double lr, double lr_bias, double beta1,
+                              double beta2, double eps, int step, int decoupled, const float* clip2, mgdt_stream s) {
+  if (!p || !g || !m || !v || n <= 0 || step < 1) MGDT_FAIL(MGDT_BAD_ARG, "adam_step: null/empty argument or step < 1");
+  return moment_launch<AdamElem>("adam_step", p, g, m, v, wd, n, nullptr, n, adam_scalars(lr, lr_bias, beta1, beta2, eps, step, decoupled), nullptr, clip2, s);
+}
+extern "C" int mgdt_adam_ema_step_dev(float* p, const float* g, float* m, float* v, const float* wd, long n_param, float* ema, long n_total,
+                                      const float* hyper8, double beta2, double eps, int decoupled, const float* clip2, mgdt_stream s) {
+  if (!p || !g || !m || !v || !hyper8 || n_param <= 0 || n_total < n_param) MGDT_FAIL(MGDT_BAD_ARG, "adam_ema_step_dev: null/empty argument");
+  return moment_launch<AdamElem>("adam_ema_step_dev", p, g, m, v, wd, n_param, ema, n_total, adam_scalars(0.0, 0.0, 0.0, beta2, eps, 1, decoupled), hyper8, clip2, s);
+}
+// buf may be NULL when momentum == 0 (it is not touched)
+extern "C" int mgdt_rmsprop_step(float* p, const float* g, float* sq, float* buf, const float* wd, long n, double lr, double lr_bias, double alpha,
+                                 double eps, double momentum, const float* clip2, mgdt_stream s) {
+  if (!p || !g || !sq || (!buf && momentum > 0.0) || n <= 0) MGDT_FAIL(MGDT_BAD_ARG, "rmsprop_step: null/empty argument");
+  const OptScalars a = rms_scalars(lr, lr_bias, alpha, eps, momentum);
+  return momentum > 0.0 ? moment_launch<RmsElem<true>>("rmsprop_step", p, g, buf, sq, wd, n, nullptr, n, a, nullptr, clip2, s)
+                        : moment_launch<RmsElem<false>>("rmsprop_step", p, g, nullptr, sq, wd, n, nullptr, n, a, nullptr, clip2, s);
+}
+extern "C" int mgdt_rmsprop_ema_step_dev(float* p, const float* g, float* sq, float* buf, const float* wd, long n_param, float* ema, long n_total,
+                                         const float* hyper8, double alpha, double eps, int with_momentum, const float* clip2, mgdt_stream s) {
+  if (!p || !g || !sq || (!buf && with_momentum) || !hyper8 || n_param <= 0 || n_total < n_param)
+    MGDT_FAIL(MGDT_BAD_ARG, "rmsprop_ema_step_dev: null/empty argument");
+  const OptScalars a = rms_scalars(0.0, 0.0, alpha, eps, 0.0);
+  return with_momentum ? moment_launch<RmsElem<true>>("rmsprop_ema_step_dev", p, g, buf, sq, wd, n_param, ema, n_total, a, hyper8, clip2, s)
+                       : moment_launch<RmsElem<false>>("rmsprop_ema_step_dev", p, g, nullptr, sq, wd, n_param, ema, n_total, a, hyper8, clip2, s);
+}

@@ -1694,6 +1694,49 @@ def ema_update(ema, p, decay):
     _launch('ema_update', 'mgdt_ema_update', ptr(ema), ptr(p), p.numel(), float(decay), stream())
 
 
+OPT_HYPER_LEN = 8        # MGDT_OPT_HYPER_LEN: {lr, lr_bias, beta1 | momentum, ema_decay, lr / bc1, lr_bias / bc1, sqrt(bc2), 1 - beta1}
+
+
+def adam_hyper(lr, lr_bias, beta1, beta2, step, ema_decay):
+    """The fp32[8] vector of the captured Adam / AdamW step as a list of Python floats: bias corrections in double, as torch computes them
+    (and as mgdt_adam_step derives them from the same arguments), rounded to fp32 when the list is copied to the device."""
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    return [lr, lr_bias, beta1, ema_decay, lr / bc1, lr_bias / bc1, bc2 ** 0.5, 1 - beta1]
+
+
+def rmsprop_hyper(lr, lr_bias, momentum, ema_decay):
+    return [lr, lr_bias, momentum, ema_decay, 0.0, 0.0, 1.0, 0.0]
+
+
+def adam_step(p, g, m, v, wd, lr, beta1, beta2, eps, step, decoupled, clip=None, lr_bias=None):
+    """torch.optim.Adam (decoupled False) / AdamW (True) over the flat buffers; `step` is 1-based."""
+    PARAM_EPOCH[0] += 1
+    _launch('adam_step', 'mgdt_adam_step', ptr(p), ptr(g), ptr(m), ptr(v), ptr(wd), p.numel(), float(lr), float(lr if lr_bias is None else lr_bias),
+            float(beta1), float(beta2), float(eps), int(step), int(decoupled), ptr(clip), stream())
+
+
+def adam_ema_step_dev(p, g, m, v, wd, ema, data, hyper, beta2, eps, decoupled, clip=None):
+    """Adam / AdamW over the parameters `p` (= data[:p.numel()]) and EMA over all of `data`, per-step scalars from the device tensor `hyper`
+    (fp32[8], adam_hyper): the form a captured training step uses."""
+    PARAM_EPOCH[0] += 1
+    _launch('adam_ema_step_dev', 'mgdt_adam_ema_step_dev', ptr(p), ptr(g), ptr(m), ptr(v), ptr(wd), p.numel(), ptr(ema), data.numel(), ptr(hyper),
+            float(beta2), float(eps), int(decoupled), ptr(clip), stream())
+
+
+def rmsprop_step(p, g, sq, buf, wd, lr, alpha, eps, momentum, clip=None, lr_bias=None):
+    """torch.optim.RMSprop(centered=False) over the flat buffers; `buf` may be None when momentum is 0."""
+    PARAM_EPOCH[0] += 1
+    _launch('rmsprop_step', 'mgdt_rmsprop_step', ptr(p), ptr(g), ptr(sq), ptr(buf), ptr(wd), p.numel(), float(lr), float(lr if lr_bias is None else lr_bias),
+            float(alpha), float(eps), float(momentum), ptr(clip), stream())
+
+
+def rmsprop_ema_step_dev(p, g, sq, buf, wd, ema, data, hyper, alpha, eps, with_momentum, clip=None):
+    """RMSProp + EMA with {lr, lr_bias, momentum, ema_decay} from the device tensor `hyper` (fp32[8], rmsprop_hyper)."""
+    PARAM_EPOCH[0] += 1
+    _launch('rmsprop_ema_step_dev', 'mgdt_rmsprop_ema_step_dev', ptr(p), ptr(g), ptr(sq), ptr(buf), ptr(wd), p.numel(), ptr(ema), data.numel(), ptr(hyper),
+            float(alpha), float(eps), int(with_momentum), ptr(clip), stream())
+
+
 # ------------------------------------------------------------------ image classification (csrc/classify.hip)
 FUSED_CLS_HEAD = True    # tests / tools/cls_bench.py flip this: Classify.conv + the spatial mean in one launch vs conv, pooling, linear as a 1x1 conv, softmax
 CLS_FUSED_MAX_HW = None  # the fused head runs for maps of at most this many pixels (None: every size; see DESIGN 3.26)

@@ -6,6 +6,7 @@ preprocess (uint8 batch handed to the stem as is: /255 is fused into the first c
 fused assigner+loss (HIP) -> reverse pass (HIP; reachable from `loss.backward()` too) with the flat gradient buffer
 all-reduced in layer-ordered buckets while the earlier layers are still running backward (RCCL over xGMI) -> every
 `accumulate` batches: clip(10) + SGD(Nesterov, the reference's three parameter groups) + EMA on the flat parameter buffer.
+`optimizer=` selects Adam / AdamW / RMSProp instead of SGD, or 'auto' (the reference's default, build_optimizer trainer.py:635-639).
 """
 import math
 
@@ -30,10 +31,30 @@ def param_groups(model):
     return out
 
 
+OPTIMIZERS = ('SGD', 'Adam', 'AdamW', 'RMSProp')
+NOT_BUILT = ('Adamax', 'NAdam', 'RAdam')          # names the reference's build_optimizer accepts (trainer.py:651) that have no kernel here
+ADAM_BETA2, OPT_EPS, RMS_ALPHA = 0.999, 1e-8, 0.99   # build_optimizer passes betas=(momentum, 0.999); eps / alpha are torch's defaults
+
+
+def resolve_optimizer(name, nc, iterations, lr0, momentum, warmup_bias_lr):
+    """build_optimizer's name handling (trainer.py:635-639,651-661) -> (name, lr0, optimizer momentum, warmup_bias_lr).  'auto': AdamW with
+    lr0 = round(0.002 * 5 / (4 + nc), 6) up to 10 000 iterations, SGD with lr0 0.01 beyond; momentum 0.9 and warmup_bias_lr 0 in both."""
+    if name == 'auto':
+        if iterations is None:
+            raise ValueError("optimizer='auto' needs `iterations` (ceil(len(dataset) / max(batch, nbs)) * epochs, trainer.py:252)")
+        name, lr0, momentum = ('SGD', 0.01, 0.9) if iterations > 10000 else ('AdamW', round(0.002 * 5 / (4 + nc), 6), 0.9)
+        warmup_bias_lr = 0.0
+    if name in NOT_BUILT:
+        raise NotImplementedError(f"Optimizer '{name}' is not built: there is no HIP kernel for it (built: {', '.join(OPTIMIZERS)}, auto).")
+    if name not in OPTIMIZERS:
+        raise NotImplementedError(f"Optimizer '{name}' not found in list of available optimizers [Adam, AdamW, NAdam, RAdam, RMSProp, SGD, auto].")
+    return name, lr0, momentum, warmup_bias_lr
+
+
 class FlatState:
     """All trainable parameters (and float buffers) of a model as views into one flat fp32 buffer; grads likewise."""
 
-    def __init__(self, model, weight_decay):
+    def __init__(self, model, weight_decay, second_moment=False):
         params = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         bufs = [(n, b) for n, b in model.named_buffers() if b.dtype.is_floating_point and b.numel() > 0 and 'anchors' not in n and 'strides' not in n]
         dev = params[0][1].device
@@ -65,7 +86,9 @@ class FlatState:
             b.data = self.data[off:off + k].view(b.shape)
             off += k
         ops.LIVE_STORAGES.add(self.data.untyped_storage().data_ptr())       # packed panels built from these bytes may be refreshed in place (ops.repack_all)
-        self.momentum_buf = torch.zeros(self.n_param, dtype=torch.float32, device=dev)
+        self.momentum_buf = torch.zeros(self.n_param, dtype=torch.float32, device=dev)       # SGD / RMSProp momentum buffer, Adam's exp_avg
+        # Adam's exp_avg_sq / RMSProp's square_avg: only the optimizers that have one pay for it
+        self.second_moment = torch.zeros(self.n_param, dtype=torch.float32, device=dev) if second_moment else None
         self.ema = self.data.clone()
         self.steps = 0                     # optimizer steps taken (= ModelEMA.updates)
 
@@ -114,11 +137,20 @@ class BucketedAllReduce:
 class DetectionTrainer:
     """Per-step driver: `trainer.step(batch)` -> (loss*B, loss_items[3]).  Hyper-parameters follow yolo/cfg/default.yaml of the fork
     (lr0 0.001, lrf 0.01, momentum 0.937, weight_decay 5e-4, warmup 3 epochs / momentum 0.8 / bias lr 0.1, nbs 64, nesterov SGD; grad
-    clip 10.0; EMA decay 0.9999, tau 2000).  `batch_size` is the GLOBAL batch (trainer.py:238,250), `nb` the batches per epoch."""
+    clip 10.0; EMA decay 0.9999, tau 2000).  `batch_size` is the GLOBAL batch (trainer.py:238,250), `nb` the batches per epoch.
+
+    `optimizer`: 'SGD' (default), 'Adam', 'AdamW', 'RMSProp' or 'auto' (resolve_optimizer; needs `iterations`).  After construction
+    `optimizer` holds the resolved name, `lr0` its learning rate and `opt_momentum` the momentum the optimizer was built with (beta1 of Adam /
+    AdamW, where it stays constant with beta2 = 0.999: their groups have no 'momentum' key for the warm-up to move, trainer.py:325).  SGD and
+    RMSProp are warmed towards `momentum`, the constructor's argument, which is therefore what remains after the warm-up - also under
+    'auto' -> SGD, whose own 0.9 is visible only when no warm-up runs (batch_size=None).  `cos_lr`: one_cycle(1, lrf, epochs) instead of the
+    linear schedule (trainer.py:260-261)."""
 
     def __init__(self, model, lr0=0.001, lrf=0.01, momentum=0.937, weight_decay=5e-4, world_size=1, ema_decay=0.9999, ema_tau=2000.0,
                  batch_size=None, nb=None, epochs=100, nbs=64, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, overlap=True, amp=False,
-                 graph=False, graph_split=None):
+                 graph=False, graph_split=None, optimizer='SGD', iterations=None, cos_lr=False):
+        self.optimizer, lr0, self.opt_momentum, warmup_bias_lr = resolve_optimizer(optimizer, self._nc(model), iterations, lr0, momentum, warmup_bias_lr)
+        self.iterations, self.cos_lr = iterations, bool(cos_lr)
         self.model = model.train()
         # amp: the reference trains under autocast (trainer.py:223,329: fp16 + GradScaler); on this hardware the reduced-precision training path
         # is bfloat16 activations / gradients with fp32 master weights, fp32 accumulation and fp32 weight gradients - no loss scaling needed
@@ -135,10 +167,14 @@ class DetectionTrainer:
             self.accumulate = max(round(nbs / batch_size), 1)                                    # trainer.py:250
             wd = weight_decay * batch_size * self.accumulate / nbs                               # trainer.py:251
             self.nw = max(round(warmup_epochs * nb), 100)                                        # trainer.py:284
-        self.state = FlatState(model, wd)
+        self.weight_decay = wd                      # of the decayed group, scaled as trainer.py:251 does
+        self.state = FlatState(model, wd, second_moment=self.optimizer != 'SGD')
         model._flat_state = self.state
         self.ema_decay, self.ema_tau = ema_decay, ema_tau
-        self.ni, self.last_opt_step, self.lr, self.lr_bias, self.mom = 0, -1, lr0, lr0, momentum
+        self.ni, self.last_opt_step, self.lr, self.lr_bias, self.mom = 0, -1, lr0, lr0, self.opt_momentum
+        # Adam's `step` is st.steps + 1 (every optimizer step is an EMA update) unless a loaded optimizer state carried another count;
+        # a loaded SGD momentum buffer is continued instead of being re-initialised by the first step
+        self.opt_step_offset, self._loaded_momentum = 0, False
         # graph=True: from the second optimizer step on, the whole step (forward, loss, reverse pass, clip + SGD + EMA: ~500 launches) is one
         # hipGraph replay; lr / momentum / EMA decay / the assigner's call counter live in device memory so that the warm-up schedule and the
         # EMA ramp keep advancing between replays.  accumulate == 1 only (otherwise the eager path runs).  With several ranks (or
@@ -154,21 +190,35 @@ class DetectionTrainer:
             if overlap:
                 self.exchange = BucketedAllReduce(self.state, len(model.model))
 
+    @staticmethod
+    def _nc(model):
+        """build_optimizer reads getattr(model, 'nc', 10) (trainer.py:636); the reference's trainer has attached data['nc'] by then
+        (v8/detect/train.py:72), which is the class count the head was built with."""
+        nc = getattr(model, 'nc', None)
+        if nc is None:
+            nc = getattr(model.model[-1], 'nc', None) if hasattr(model, 'model') else None
+        return 10 if nc is None else int(nc)
+
     def lf(self, epoch):
-        """linear lr schedule (trainer.py:262)"""
+        """linear lr schedule (trainer.py:263), or with cos_lr one_cycle(1, lrf, epochs) (trainer.py:261, torch_utils.py:309-311)"""
+        if self.cos_lr:
+            return ((1 - math.cos(epoch * math.pi / self.epochs)) / 2) * (self.lrf - 1) + 1
         return (1 - epoch / self.epochs) * (1.0 - self.lrf) + self.lrf
 
     def warmup(self, epoch=0):
         """lr / momentum / accumulate of iteration self.ni (trainer.py:317-326); after warm-up the epoch's scheduled values."""
         base = self.lr0 * self.lf(epoch) if self.batch_size is not None else self.lr0
         self.lr = self.lr_bias = base
-        self.mom = self.momentum
+        # groups with a 'momentum' key (SGD, RMSProp) are left at the warm-up's target, the constructor's momentum; Adam's beta1 never moves
+        warmed = self.optimizer in ('SGD', 'RMSProp') and self.nw >= 0
+        self.mom = self.momentum if warmed else self.opt_momentum
         if self.ni <= self.nw:
             xi = [0, self.nw]
             self.accumulate = max(1, np.interp(self.ni, xi, [1, self.nbs / self.batch_size]).round())
             self.lr = float(np.interp(self.ni, xi, [0.0, base]))
             self.lr_bias = float(np.interp(self.ni, xi, [self.warmup_bias_lr, base]))
-            self.mom = float(np.interp(self.ni, xi, [self.warmup_momentum, self.momentum]))
+            if warmed:
+                self.mom = float(np.interp(self.ni, xi, [self.warmup_momentum, self.momentum]))
 
     def preprocess_batch(self, batch):
         """detect/train.py:62-65 moves the uint8 batch to the device and computes float()/255; here the uint8 tensor goes to the stem
@@ -180,11 +230,105 @@ class DetectionTrainer:
         """unscale (no loss scaling: fp32 / bf16) -> clip_grad_norm_(10) -> SGD -> zero_grad (implicit: overwrite) -> EMA (trainer.py:462-470)."""
         st = self.state
         clip = ops.grad_clip_coef(st.grad, 10.0)
-        ops.sgd_step(st.data[:st.n_param], st.grad, st.momentum_buf, st.wd, self.lr, self.mom, True, st.steps == 0, clip, lr_bias=self.lr_bias)
+        p = st.data[:st.n_param]
+        if self.optimizer == 'SGD':
+            ops.sgd_step(p, st.grad, st.momentum_buf, st.wd, self.lr, self.mom, True, st.steps == 0 and not self._loaded_momentum, clip,
+                         lr_bias=self.lr_bias)
+        elif self.optimizer == 'RMSProp':
+            ops.rmsprop_step(p, st.grad, st.second_moment, st.momentum_buf, st.wd, self.lr, RMS_ALPHA, OPT_EPS, self.mom, clip, lr_bias=self.lr_bias)
+        else:                                       # every optimizer step is an EMA update, so Adam's step count is st.steps
+            ops.adam_step(p, st.grad, st.momentum_buf, st.second_moment, st.wd, self.lr, self.mom, ADAM_BETA2, OPT_EPS,
+                          st.steps + self.opt_step_offset + 1, self.optimizer == 'AdamW', clip, lr_bias=self.lr_bias)
         st.steps += 1
         d = self.ema_decay * (1 - math.exp(-st.steps / self.ema_tau))      # torch_utils.py:342
         ops.ema_update(st.ema, st.data, d)
         ops.repack_all()                            # the packed panels of this step, refreshed for the next one in a few launches
+
+    # ---- optimizer state in torch's layout -------------------------------------------------------------------------------------------
+    def _reference_groups(self):
+        """Parameter names in the reference's optimizer order: param_groups [0] biases, [1] decayed weights, [2] norm weights
+        (build_optimizer trainer.py:652-664), each in named_modules order."""
+        groups = param_groups(self.model)
+        names = [[n for n, g in groups.items() if g == k] for k in (2, 0, 1)]
+        return names                               # frozen parameters (dfl.conv.weight) are members too; they never get a state entry
+
+    def _state_keys(self):
+        if self.optimizer in ('Adam', 'AdamW'):
+            return ('exp_avg', 'exp_avg_sq')
+        if self.optimizer == 'RMSProp':
+            return ('square_avg', 'momentum_buffer') if self.mom > 0 else ('square_avg',)
+        return ('momentum_buffer',)
+
+    def optimizer_state_dict(self):
+        """The optimizer state as torch's Optimizer.state_dict() of the reference's optimizer would hold it (what the reference saves in a
+        checkpoint's 'optimizer' entry): per-parameter `step` / `exp_avg` / `exp_avg_sq` (Adam, AdamW), `momentum_buffer` (SGD) or `step` /
+        `square_avg` [/ `momentum_buffer`] (RMSProp), indexed through the three groups.  Before the first step the state is empty, as torch's."""
+        st, names = self.state, self._reference_groups()
+        shapes = {n: p.shape for n, p in self.model.named_parameters()}
+        cls = {'SGD': torch.optim.SGD, 'Adam': torch.optim.Adam, 'AdamW': torch.optim.AdamW, 'RMSProp': torch.optim.RMSprop}[self.optimizer]
+        kw = dict(momentum=self.mom, nesterov=True) if self.optimizer == 'SGD' else dict(momentum=self.mom) if self.optimizer == 'RMSProp' \
+            else dict(betas=(self.mom, ADAM_BETA2), weight_decay=0.0)
+        # the hyper-parameter keys of the installed torch, from an optimizer over empty stand-ins
+        opt = cls([{'params': [nn.Parameter(torch.empty(0)) for _ in ns], 'weight_decay': w, 'lr': lr, 'initial_lr': self.lr0}
+                   for ns, w, lr in zip(names, (0.0, self.weight_decay, 0.0), (self.lr_bias, self.lr, self.lr))], lr=self.lr0, **kw)
+        groups = opt.state_dict()['param_groups']
+        state, steps = {}, st.steps + self.opt_step_offset
+        if steps > 0 or self._loaded_momentum:
+            bufs = {'exp_avg': st.momentum_buf, 'momentum_buffer': st.momentum_buf, 'exp_avg_sq': st.second_moment, 'square_avg': st.second_moment}
+            for i, n in enumerate(n for ns in names for n in ns):
+                if n not in st.offsets:
+                    continue
+                off, k = st.offsets[n]
+                e = {} if self.optimizer == 'SGD' else {'step': torch.tensor(float(steps))}
+                e.update({key: bufs[key][off:off + k].view(shapes[n]).clone() for key in self._state_keys()})
+                state[i] = e
+        return {'state': state, 'param_groups': groups}
+
+    def load_optimizer_state_dict(self, sd):
+        """Takes what optimizer_state_dict() returns - what the reference's resume_training hands to optimizer.load_state_dict
+        (trainer.py:589-590).  The moment buffers and the step count are restored; learning rates and momentum stay the trainer's own
+        schedule (the reference recomputes them from initial_lr every iteration / epoch as well).  A state of another optimizer type, other
+        group sizes or other tensor shapes raises ValueError."""
+        st, names = self.state, self._reference_groups()
+        flat = [n for ns in names for n in ns]
+        groups = sd['param_groups']
+        if [len(g['params']) for g in groups] != [len(ns) for ns in names]:
+            raise ValueError(f"optimizer state has groups of {[len(g['params']) for g in groups]} parameters, the model {[len(ns) for ns in names]}")
+        idx = [i for g in groups for i in g['params']]
+        state, keys = sd['state'], self._state_keys()
+        known = {'exp_avg', 'exp_avg_sq', 'square_avg', 'momentum_buffer', 'max_exp_avg_sq', 'grad_avg'}
+        shapes = {n: p.shape for n, p in self.model.named_parameters()}
+        bufs = {'exp_avg': st.momentum_buf, 'momentum_buffer': st.momentum_buf, 'exp_avg_sq': st.second_moment, 'square_avg': st.second_moment}
+        steps = set()
+        for i, n in zip(idx, flat):                # validate everything before anything is written
+            e = state.get(i, state.get(str(i)))
+            if n not in st.offsets:
+                continue
+            if e is None:
+                if state:
+                    raise ValueError(f'optimizer state has no entry for parameter {i} ({n})')
+                continue
+            have = {k for k in e if k in known and e[k] is not None}
+            if have != set(keys):
+                raise ValueError(f'optimizer state of parameter {i} ({n}) holds {sorted(have)}; {self.optimizer} needs {sorted(keys)}')
+            for k in keys:
+                if tuple(e[k].shape) != tuple(shapes[n]):
+                    raise ValueError(f'{k} of parameter {i} ({n}) has shape {tuple(e[k].shape)}, the parameter {tuple(shapes[n])}')
+            if 'step' in e:
+                steps.add(int(e['step']))
+        if self.optimizer in ('Adam', 'AdamW') and state and len(steps) != 1:
+            raise ValueError(f'Adam state needs one step count for all parameters, got {sorted(steps)}')
+        st.momentum_buf.zero_()
+        if st.second_moment is not None:
+            st.second_moment.zero_()
+        for i, n in zip(idx, flat):
+            e = state.get(i, state.get(str(i)))
+            if e is not None and n in st.offsets:
+                off, k = st.offsets[n]
+                for key in keys:
+                    bufs[key][off:off + k].copy_(e[key].reshape(-1))
+        self._loaded_momentum = bool(state) and self.optimizer == 'SGD'
+        self.opt_step_offset = (max(steps) if steps else 0) - st.steps if self.optimizer != 'SGD' else 0
 
     # ---- captured step -------------------------------------------------------------------------------------------------------------
     def _graph_ok(self):
@@ -204,7 +348,15 @@ class DetectionTrainer:
             if part == 'grad':
                 return
         clip = ops.grad_clip_coef(st.grad, 10.0)
-        ops.sgd_ema_step_dev(st.data[:st.n_param], st.grad, st.momentum_buf, st.wd, st.ema, st.data, S['hyper'], True, False, clip)
+        p = st.data[:st.n_param]
+        if self.optimizer == 'SGD':
+            ops.sgd_ema_step_dev(p, st.grad, st.momentum_buf, st.wd, st.ema, st.data, S['hyper'], True, False, clip)
+        elif self.optimizer == 'RMSProp':           # the momentum / no-momentum kernel is fixed at capture: see _graph_step
+            ops.rmsprop_ema_step_dev(p, st.grad, st.second_moment, st.momentum_buf, st.wd, st.ema, st.data, S['hyper'], RMS_ALPHA, OPT_EPS,
+                                     self.mom > 0, clip)
+        else:
+            ops.adam_ema_step_dev(p, st.grad, st.momentum_buf, st.second_moment, st.wd, st.ema, st.data, S['hyper'], ADAM_BETA2, OPT_EPS,
+                                  self.optimizer == 'AdamW', clip)
         S['panels'] = ops.repack_all()              # next step's packed weights, all convolutions in a few launches
 
     def _graph_step(self, batch):
@@ -215,7 +367,7 @@ class DetectionTrainer:
         nmax = max(16, -(-int(gt.shape[1]) // 16) * 16)             # label slots of the captured step (zero rows are padding, loss.py:177-181)
         S = self._static
         if S is None or S['img'].shape != img.shape or S['img'].dtype != img.dtype:
-            S = self._static = dict(img=torch.empty_like(img), hyper=torch.empty(4, dtype=torch.float32, device=img.device),
+            S = self._static = dict(img=torch.empty_like(img), hyper=torch.empty(ops.OPT_HYPER_LEN, dtype=torch.float32, device=img.device),
                                     calls=torch.zeros(1, dtype=torch.int32, device=img.device), gts={})
             self._graphs, self._pool = {}, None
         # Every captured graph reads - and, in its trailing re-pack, rewrites - the packed weight panels that were current when it was
@@ -224,6 +376,8 @@ class DetectionTrainer:
         # new ones and freeing these), and if anything else moved the weights without refreshing them the graphs are dropped.
         if any(not ops.pack_is_current(o) for _, _, panels in self._graphs.values() for o in panels):
             self._graphs, self._pool = {}, None
+        if self.optimizer == 'RMSProp' and S.setdefault('rms_mom', self.mom > 0) != (self.mom > 0):      # torch tests momentum > 0 every step
+            self._graphs, self._pool, S['rms_mom'] = {}, None, self.mom > 0
         if nmax not in S['gts']:
             S['gts'][nmax] = torch.zeros(b, nmax, 5, dtype=torch.float32, device=img.device)
         S['gt'] = S['gts'][nmax]
@@ -232,7 +386,11 @@ class DetectionTrainer:
         if gt.shape[1]:
             S['gt'][:, :gt.shape[1]].copy_(gt)
         d = self.ema_decay * (1 - math.exp(-(st.steps + 1) / self.ema_tau))      # torch_utils.py:342 with updates = steps + 1
-        S['hyper'].copy_(torch.tensor([self.lr, self.lr_bias, self.mom, d], dtype=torch.float32), non_blocking=True)
+        if self.optimizer in ('Adam', 'AdamW'):    # bias corrections of optimizer step st.steps + 1, in Python floats as torch computes them
+            hyper = ops.adam_hyper(self.lr, self.lr_bias, self.mom, ADAM_BETA2, st.steps + self.opt_step_offset + 1, d)
+        else:                                       # SGD reads the first four
+            hyper = ops.rmsprop_hyper(self.lr, self.lr_bias, self.mom, d)
+        S['hyper'].copy_(torch.tensor(hyper, dtype=torch.float32), non_blocking=True)
         S['calls'].fill_(int(self.crit.epoch))
         captured = nmax not in self._graphs
         if captured:
