@@ -102,6 +102,15 @@ static inline FastDiv make_fastdiv(uint32_t d) {
 }
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, FastDiv f) { return f.d == 1 ? n : (__umulhi(n, f.mul) >> f.sh); }
 
+// box_iou (reference yolo/utils/metrics.py:52-72, eps 1e-7 in the union) of a label box against a detection box of area `area_d`.  The validator
+// matcher (val_match.hip) and the confusion pass (valstats.hip) agree bit for bit through it: both files are built with -ffp-contract=off, so its
+// operations round one by one.
+__device__ __forceinline__ float box_iou(float lx1, float ly1, float lx2, float ly2, float x1, float y1, float x2, float y2, float area_d) {
+  const float iw = fmaxf(fminf(lx2, x2) - fmaxf(lx1, x1), 0.f), ih = fmaxf(fminf(ly2, y2) - fmaxf(ly1, y1), 0.f);
+  const float inter = iw * ih;
+  return inter / ((lx2 - lx1) * (ly2 - ly1) + area_d - inter + 1e-7f);
+}
+
 __device__ __forceinline__ float act_apply(float v, int act) {
   switch (act) {
     case MGDT_ACT_SILU: return v * fast_sigmoid(v);

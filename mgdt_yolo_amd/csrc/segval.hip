@@ -1,5 +1,6 @@
 // Instance-segmentation validation (reference yolo/v8/segment/val.py:131-166 SegmentationValidator._process_batch, yolo/utils/metrics.py:131-147
-// mask_iou): mask IoU of every (label, detection) pair of a batch, ground truth brought to the predictions' resolution, matching from an IoU matrix.
+// mask_iou): mask IoU of every (label, detection) pair of a batch, ground truth brought to the predictions' resolution.  The matching from the IoU
+// matrix is val_match.hip's.
 //
 //   mask_iou       inter[image][label][detection] = sum over pixels of gt * pred on the 0 / 1 mask BYTES with v_mfma_i32_16x16x64_i8: the labels are
 //                  the M rows (A operand), 16 detections the N columns (B operand), pixels are K.  A wave owns (image, 16 detections, a K range) and
@@ -15,7 +16,6 @@
 //                  0 / 1 sums are exact below 2^24.  Every predicted mask byte is read once.
 //   gt_resample    F.interpolate(bilinear, align_corners=False) + > 0.5 of each binary ground-truth mask (val.py:146-148), from either form, written as
 //                  instance masks at the predictions' size (the weights of seg_tap in segment.hip: PyTorch's CPU arithmetic).
-//   val_match_iou  the matching rule of val_match_kernel (nms.hip) on a given IoU matrix.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
@@ -248,65 +248,5 @@ extern "C" int mgdt_gt_masks_resample_fwd(const uint8_t* gt, int gt_index_map, c
   a.h = h; a.w = w; a.oh = out_h; a.ow = out_w; a.sy = (float)h / (float)out_h; a.sx = (float)w / (float)out_w;
   gt_resample_kernel<<<dim3(cdiv((long)out_h * out_w, 256), max_lab, n), 256, 0, (hipStream_t)s>>>(a);
   MGDT_CHECK_LAUNCH("gt_masks_resample_fwd");
-  return MGDT_OK;
-}
-
-// ================================================================================================ matching from an IoU matrix
-// The rule of val_match_kernel (nms.hip), with iou[image][label][detection] given instead of computed from boxes: per level, a detection chooses the
-// label with the largest IoU among {iou >= level, same class} (exact ties: the lower label index); a label keeps the lowest-index detection that chose it.
-#define VMI_T 16
-__global__ __launch_bounds__(256) void val_match_iou_kernel(const float* __restrict__ iou, int max_lab, int max_det, const float* __restrict__ det_cls,
-                                                            int det_stride, const int32_t* __restrict__ ndet, const float* __restrict__ lab_cls,
-                                                            int lab_stride, const int32_t* __restrict__ nlab, const float* __restrict__ iouv, int T,
-                                                            uint8_t* __restrict__ correct) {
-  extern __shared__ int winner[];     // [T][max_lab]
-  const int img = blockIdx.x, tid = threadIdx.x;
-  const int nd = min(ndet[img], max_det), nl = min(nlab[img], max_lab);
-  const float* I = iou + (long)img * max_lab * max_det;
-  const float* DC = det_cls + (long)img * max_det * det_stride;
-  const float* LC = lab_cls + (long)img * max_lab * lab_stride;
-  uint8_t* C = correct + (long)img * max_det * T;
-  for (int i = tid; i < T * max_lab; i += 256) winner[i] = 0x7fffffff;
-  __syncthreads();
-  for (int d0 = 0; d0 < max_det; d0 += 256) {     // uniform trip count: barriers inside
-    const int d = d0 + tid;
-    int best[VMI_T];
-    float bestv[VMI_T];
-#pragma unroll
-    for (int t = 0; t < VMI_T; ++t) { best[t] = -1; bestv[t] = -1.f; }
-    if (d < nd) {
-      const float cls = DC[(long)d * det_stride];
-      for (int l = 0; l < nl; ++l) {
-        if (LC[(long)l * lab_stride] != cls) continue;
-        const float v = I[(long)l * max_det + d];
-#pragma unroll
-        for (int t = 0; t < VMI_T; ++t)
-          if (t < T && v >= iouv[t] && v > bestv[t]) { bestv[t] = v; best[t] = l; }
-      }
-#pragma unroll
-      for (int t = 0; t < VMI_T; ++t)
-        if (t < T && best[t] >= 0) atomicMin(&winner[t * max_lab + best[t]], d);
-    }
-    __syncthreads();
-    if (d < max_det) {
-#pragma unroll
-      for (int t = 0; t < VMI_T; ++t)
-        if (t < T) C[d * T + t] = (d < nd && best[t] >= 0 && winner[t * max_lab + best[t]] == d) ? 1 : 0;
-    }
-    __syncthreads();
-  }
-}
-
-extern "C" int mgdt_val_match_iou_fwd(const float* iou, int n, int max_lab, int max_det, const float* det_cls, int det_stride, const int32_t* ndet,
-                                      const float* lab_cls, int lab_stride, const int32_t* nlab, const float* iouv, int n_iou, uint8_t* correct,
-                                      mgdt_stream s) {
-  if (!iou || !det_cls || !ndet || !lab_cls || !nlab || !iouv || !correct) MGDT_FAIL(MGDT_BAD_ARG, "val_match_iou: null pointer");
-  if (n < 1 || max_det < 1 || max_lab < 1 || det_stride < 1 || lab_stride < 1 || n_iou < 1 || n_iou > VMI_T ||
-      (size_t)n_iou * max_lab * sizeof(int) > 64 * 1024)
-    MGDT_FAIL(MGDT_BAD_SHAPE, "val_match_iou: n=%d max_det=%d max_lab=%d strides %d / %d n_iou=%d (<= %d levels, levels*max_lab <= 16384)", n, max_det,
-              max_lab, det_stride, lab_stride, n_iou, VMI_T);
-  val_match_iou_kernel<<<n, 256, (size_t)n_iou * max_lab * sizeof(int), (hipStream_t)s>>>(iou, max_lab, max_det, det_cls, det_stride, ndet, lab_cls,
-                                                                                           lab_stride, nlab, iouv, n_iou, correct);
-  MGDT_CHECK_LAUNCH("val_match_iou_fwd");
   return MGDT_OK;
 }

@@ -18,7 +18,7 @@
 //                  Classes are the float columns truncated like .int(); a label or detection whose class is outside [0, nc) takes part in the
 //                  matching but adds nothing (the reference raises an IndexError there).
 // Both accumulators are ADDED to with integer atomics only: the result does not depend on scheduling.
-// Compiled with -ffp-contract=off: box_iou's operations round one by one, in the order of val_match_kernel (nms.hip).
+// Compiled with -ffp-contract=off: the confusion pass calls the box_iou of common.h, whose operations then round one by one, as in val_match.hip.
 #include "common.h"
 
 #define VS_THREADS 256
@@ -92,10 +92,7 @@ __global__ __launch_bounds__(VS_THREADS) void val_confusion_kernel(const ValStat
     float bestv = 0.f;
     for (int l = 0; l < nl; ++l) {
       if (keep_cm) {
-        const float lx1 = Lb[l * 4], ly1 = Lb[l * 4 + 1], lx2 = Lb[l * 4 + 2], ly2 = Lb[l * 4 + 3];
-        const float iw = fmaxf(fminf(lx2, x2) - fmaxf(lx1, x1), 0.f), ih = fmaxf(fminf(ly2, y2) - fmaxf(ly1, y1), 0.f);
-        const float inter = iw * ih;
-        const float iou = inter / ((lx2 - lx1) * (ly2 - ly1) + area_d - inter + 1e-7f);
+        const float iou = box_iou(Lb[l * 4], Lb[l * 4 + 1], Lb[l * 4 + 2], Lb[l * 4 + 3], x1, y1, x2, y2, area_d);
         if (iou > a.cm_iou && (best < 0 || iou > bestv)) { bestv = iou; best = l; }
       }
       if (keep_cnt && Lc[l] == dc) {

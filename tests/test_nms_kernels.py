@@ -1,4 +1,5 @@
-"""Every route of nms_kernel / nms_best_kernel (mgdt_yolo_amd/csrc/nms.hip) and val_match_kernel against the CPU oracle, bit for bit.
+"""Every route of nms_kernel / nms_best_kernel (mgdt_yolo_amd/csrc/nms.hip) and both instantiations of val_match_kernel (val_match.hip) against the CPU
+oracle, bit for bit.
 
 Which route of nms_kernel runs depends on the data: how many candidates pass, how their scores fall into the 2048 histogram bins, how soon the
 greedy scan reaches max_det.  Every NMS case therefore STATES its route - per segment `selector.sort.np2` with selector hist | rank and sort
@@ -544,20 +545,52 @@ def test_val_match_inputs_hold_what_they_claim():
     assert c[:256].any() and c[256:512].any() and c[512:].any()
 
 
-@gpu
-@pytest.mark.parametrize('T', sorted(VM_LEVELS))
-def test_val_match_bit_equal(T):
-    from mgdt_yolo_amd import ops
-    imgs, iouv = _vm_images(), VM_LEVELS[T]
+@functools.lru_cache(maxsize=None)
+def _vm_batch():
+    """The images of `_vm_images` in the batch layout (host tensors): det, ndet, lab, nlab."""
+    imgs = _vm_images()
     b = len(imgs)
     det = torch.zeros(b, VM_MAX_DET, 6); lab = torch.zeros(b, VM_MAX_LAB, 5)
     ndet = torch.zeros(b, dtype=torch.int32); nlab = torch.zeros(b, dtype=torch.int32)
     for i, (_, d, l, nd, nl) in enumerate(imgs):
         det[i, :len(d)] = torch.from_numpy(d); lab[i, :len(l)] = torch.from_numpy(l)
         ndet[i], nlab[i] = nd, nl
-    correct = ops.val_match(det.to(DEV), ndet.to(DEV), lab.to(DEV), nlab.to(DEV), iouv.to(DEV)).cpu().numpy()
-    assert correct.shape == (b, VM_MAX_DET, T)
+    return det, ndet, lab, nlab
+
+
+def _vm_check(correct, iouv):
+    imgs = _vm_images()
+    assert correct.shape == (len(imgs), VM_MAX_DET, len(iouv))
     for i, (name, d, l, nd, nl) in enumerate(imgs):
         ref = OV.process_batch(torch.from_numpy(d), torch.from_numpy(l), iouv)
-        assert np.array_equal(correct[i, :len(d)], ref), (name, T)
-        assert not correct[i, len(d):].any(), (name, T)
+        assert np.array_equal(correct[i, :len(d)], ref), (name, len(iouv))
+        assert not correct[i, len(d):].any(), (name, len(iouv))
+
+
+@gpu
+@pytest.mark.parametrize('T', sorted(VM_LEVELS))
+def test_val_match_bit_equal(T):
+    from mgdt_yolo_amd import ops
+    iouv = VM_LEVELS[T]
+    det, ndet, lab, nlab = (t.to(DEV) for t in _vm_batch())
+    _vm_check(ops.val_match(det, ndet, lab, nlab, iouv.to(DEV)).cpu().numpy(), iouv)
+
+
+@gpu
+@pytest.mark.parametrize('T', sorted(VM_LEVELS))
+def test_val_match_iou_on_the_box_iou_matrix_equals_val_match(T):
+    """Both instantiations of val_match_kernel obey one rule: the matrix source, fed with the (B, max_lab, max_det) float32 box IoUs computed on the CPU
+    in the kernel's operation order (oracle.val.box_iou; zero past nlab / ndet), returns what the box source returns on the boxes, and what the oracle
+    returns.  The inputs hold no tie (test_val_match_inputs_have_no_tie), so the reference alone decides every entry."""
+    from mgdt_yolo_amd import ops
+    iouv = VM_LEVELS[T]
+    det, ndet, lab, nlab = _vm_batch()
+    iou = torch.zeros(len(det), VM_MAX_LAB, VM_MAX_DET)
+    for i, (_, d, l, _, _) in enumerate(_vm_images()):
+        if len(d) and len(l):
+            iou[i, :len(l), :len(d)] = OV.box_iou(torch.from_numpy(l[:, 1:]), torch.from_numpy(d[:, :4]))
+    assert iou.dtype == torch.float32
+    det, ndet, lab, nlab = (t.to(DEV) for t in (det, ndet, lab, nlab))
+    from_matrix = ops.val_match_iou(iou.to(DEV), det, ndet, lab, nlab, iouv.to(DEV))
+    assert torch.equal(from_matrix, ops.val_match(det, ndet, lab, nlab, iouv.to(DEV))), T
+    _vm_check(from_matrix.cpu().numpy(), iouv)

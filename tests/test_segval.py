@@ -468,3 +468,39 @@ def test_whole_chain_from_the_fixture_rows_and_protos():
     print('summary', num.tolist(), 'max |delta|', float(np.abs(num - g['chain_summary']).max()))
     if excepted == 0:
         assert np.abs(num - g['chain_summary']).max() <= 1e-6
+
+
+@pytest.mark.gpu
+def test_unsorted_batch_idx_with_instance_masks_through_update_metrics():
+    """overlap_mask=False: the instance masks are per-label rows and must follow the validator's stable re-sort of an unsorted batch_idx.  The rows,
+    protos, labels and instance masks of test_whole_chain_from_the_fixture_rows_and_protos as a dataloader dict (normalised labels, identity
+    letter-box); the labels once grouped by image, once interleaved: `stats` and `get_stats()` must be EQUAL."""
+    import seg_ref as SR
+    from mgdt_yolo_amd.yolo.v8.segment import SegmentationValidator
+    g, f = fixture(), SR.load_fixture()
+    tag, (H, W) = R.CHAIN_TAG, R.CHAIN_SHAPE
+    protos = torch.from_numpy(f[tag + '_p']).to(DEV)
+    b, mh, mw = protos.shape[0], protos.shape[2], protos.shape[3]
+    per = [torch.from_numpy(f[f'{tag}_nms_val_{i}']).to(DEV) for i in range(b)]
+    labs = [g[f'chain_{i}_lab'] for i in range(b)]
+    lab = np.concatenate(labs, 0).astype(np.float32)
+    bidx = np.concatenate([np.full(len(l), i, np.float32) for i, l in enumerate(labs)])
+    gt = np.concatenate([R.unpack(g[f'chain_{i}_gt'], (len(labs[i]), mh, mw)) for i in range(b)], 0).astype(np.uint8)
+    xywh = np.stack([(lab[:, 1] + lab[:, 3]) / 2 / W, (lab[:, 2] + lab[:, 4]) / 2 / H, (lab[:, 3] - lab[:, 1]) / W, (lab[:, 4] - lab[:, 2]) / H], 1).astype(np.float32)
+    perm = np.random.default_rng(2).permutation(len(lab))
+    assert min(len(l) for l in labs) > 1 and (np.diff(bidx[perm]) < 0).any()
+    res = {}
+    for order, p in (('sorted', np.arange(len(lab))), ('unsorted', perm)):
+        batch = dict(img=torch.zeros(b, 3, H, W), cls=torch.from_numpy(lab[p, :1]), bboxes=torch.from_numpy(xywh[p]), batch_idx=torch.from_numpy(bidx[p]),
+                     masks=torch.from_numpy(gt[p]), ori_shape=[(H, W)] * b, ratio_pad=[((1.0, 1.0), (0.0, 0.0))] * b)
+        v = SegmentationValidator(device=DEV)
+        v.init_metrics(nc=80, conf=0.001, iou=0.7, max_det=max(len(r) for r in per), overlap_mask=False)
+        v.update_metrics((per, protos), v.preprocess(batch))
+        assert v.seen == b and len(v.stats) == b
+        res[order] = (v.stats, v.get_stats())
+    assert res['sorted'][1]['metrics/mAP50(M)'] > 0, 'the mask matching must be non-trivial'
+    assert res['unsorted'][1] == res['sorted'][1]
+    # within an image the labels keep their shuffled order: the matches of a detection do not depend on it, the class list is a permutation
+    for got, want in zip(res['unsorted'][0], res['sorted'][0]):
+        assert all(torch.equal(a, e) for a, e in zip(got[:4], want[:4])) and torch.equal(got[4].sort().values, want[4].sort().values)
+

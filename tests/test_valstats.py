@@ -269,13 +269,10 @@ def test_untruncated_labels_and_other_thresholds_follow_the_restatement():
     assert np.array_equal(m.cpu().numpy(), want_m) and np.array_equal(k.cpu().numpy(), want_k)
 
 
-@pytest.mark.gpu
-def test_detection_validator_adds_the_new_keys_and_leaves_the_map_dict_unchanged():
-    """update_metrics + get_stats on the synthetic batch of test_validator_update_metrics_and_stats (tests/golden/inputs.py:val_match_inputs), with
-    and without the new statistics; one image without detections and one without labels are added."""
+def _validator_batch():
+    """The synthetic batch of test_validator_update_metrics_and_stats (tests/golden/inputs.py:val_match_inputs) with one image without detections and
+    one without labels added -> (preds, batch, labels per class); 60 detections by 9 labels in the other images."""
     import inputs as GI
-    from mgdt_yolo_amd.yolo.utils.metrics import ConfusionMatrix
-    from mgdt_yolo_amd.yolo.v8.detect import DetectionValidator
     B, H, W, nc = 5, 384, 640, 5
     ori = [(720, 1200), (384, 640), (500, 700), (384, 640), (384, 640)]
     preds, cls_l, box_l, idx_l, rp, nlab = [], [], [], [], [], np.zeros(nc, np.int64)
@@ -291,6 +288,17 @@ def test_detection_validator_adds_the_new_keys_and_leaves_the_map_dict_unchanged
         nlab += np.bincount(lab[:, 0].astype(int), minlength=nc)
     batch = dict(img=torch.zeros(B, 3, H, W, dtype=torch.uint8, device=DEV), cls=torch.from_numpy(np.concatenate(cls_l)),
                  bboxes=torch.from_numpy(np.concatenate(box_l)), batch_idx=torch.from_numpy(np.concatenate(idx_l)), ori_shape=ori, ratio_pad=rp)
+    return preds, batch, nlab
+
+
+@pytest.mark.gpu
+def test_detection_validator_adds_the_new_keys_and_leaves_the_map_dict_unchanged():
+    """update_metrics + get_stats on the synthetic batch of test_validator_update_metrics_and_stats (tests/golden/inputs.py:val_match_inputs), with
+    and without the new statistics; one image without detections and one without labels are added."""
+    from mgdt_yolo_amd.yolo.utils.metrics import ConfusionMatrix
+    from mgdt_yolo_amd.yolo.v8.detect import DetectionValidator
+    B, nc = 5, 5
+    preds, batch, nlab = _validator_batch()
     res = {}
     for on in (False, True):
         v = DetectionValidator(DEV)
@@ -310,3 +318,58 @@ def test_detection_validator_adds_the_new_keys_and_leaves_the_map_dict_unchanged
     assert (s[:, 0] == B).all() and np.array_equal(s[:, 1], nlab) and np.array_equal(s[:, 7] + s[:, 9], nlab) and s[:, 7].sum() >= 10
     assert (s[:, 8] >= 0).all() and (s[:, 8] <= s[:, 2]).all()
     assert all(res[True][f'metrics/count_gt({c})'] == float(nlab[c]) for c in range(nc))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('extras', [False, True], ids=['extras_off', 'extras_on'])
+def test_detection_validator_batch_path_equals_the_per_image_api(extras):
+    """update_metrics matches the whole batch in one launch and slices per image; the expectation is built image by image from the per-image public
+    API on the same native-space tensors: `_process_batch`, ConfusionMatrix.process_batch, CountMetrics.process_batch.  The batch of `_validator_batch`
+    (one image without detections, one without labels) with the label rows shuffled, so that batch_idx is unsorted.  Everything is EQUAL."""
+    from mgdt_yolo_amd.yolo.utils import ops as uops
+    from mgdt_yolo_amd.yolo.utils.metrics import ConfusionMatrix, CountMetrics
+    from mgdt_yolo_amd.yolo.v8.detect import DetectionValidator
+    nc = 5
+    preds, batch, _ = _validator_batch()
+    perm = torch.from_numpy(np.random.default_rng(3).permutation(len(batch['batch_idx'])))
+    batch = dict(batch, cls=batch['cls'][perm], bboxes=batch['bboxes'][perm], batch_idx=batch['batch_idx'][perm])
+    assert bool((batch['batch_idx'][1:] < batch['batch_idx'][:-1]).any()), 'batch_idx is unsorted'
+    H, W = batch['img'].shape[2:]
+    v = DetectionValidator(DEV)
+    v.init_metrics(nc=nc, confusion=extras, counting=extras)
+    # ---- image by image
+    want, seen, cm, ct = [], 0, ConfusionMatrix(nc), CountMetrics(nc)
+    whwh = torch.tensor((W, H, W, H), dtype=torch.float32, device=DEV)
+    for si, pred in enumerate(preds):
+        idx = batch['batch_idx'] == si
+        cls, bbox = batch['cls'][idx].to(DEV), batch['bboxes'][idx].to(DEV)
+        shape, rp = batch['ori_shape'][si], batch['ratio_pad'][si]
+        seen += 1
+        predn = pred.clone()
+        tbox = uops.xywh2xyxy(bbox.contiguous()) * whwh if len(cls) else torch.zeros(0, 4, device=DEV)
+        if len(pred):
+            uops.scale_boxes((H, W), predn, shape, ratio_pad=rp)
+        if len(cls):
+            uops.scale_boxes((H, W), tbox, shape, ratio_pad=rp)
+        labelsn = torch.cat((cls, tbox), 1)
+        if len(cls):                                                  # the matrix skips an image without labels, the counters count it
+            cm.process_batch(predn if len(pred) else None, labelsn)
+        ct.process_batch(predn if len(pred) else None, labelsn)
+        if len(pred):
+            want.append((v._process_batch(predn, labelsn), pred[:, 4], pred[:, 5], cls[:, 0]))
+        elif len(cls):
+            want.append((torch.zeros(0, 10, dtype=torch.bool, device=DEV), torch.zeros(0, device=DEV), torch.zeros(0, device=DEV), cls[:, 0]))
+    assert [len(p) for p in preds] == [60, 60, 60, 0, 60] and [len(w[3]) for w in want] == [9, 9, 9, 9, 0]
+    # ---- the batch
+    v.update_metrics(preds, batch)
+    assert v.seen == seen == 5 and len(v.stats) == len(want)
+    for si, (got, exp) in enumerate(zip(v.stats, want)):
+        assert len(got) == 4
+        for k, (g, e) in enumerate(zip(got, exp)):
+            assert g.dtype == e.dtype and g.shape == e.shape and torch.equal(g, e), (si, k)
+    assert any(bool(w[0].any()) for w in want)
+    if extras:
+        assert np.array_equal(v.confusion_matrix.matrix, cm.matrix) and cm.matrix.sum() > 0
+        assert np.array_equal(v.count_metrics.slots, ct.slots) and (ct.slots[:, 0] == 5).all()
+    else:
+        assert v.confusion_matrix is None and v.count_metrics is None
