@@ -70,9 +70,29 @@ __device__ __forceinline__ f32x4 lds_load4(const char* p) {
   return f32x4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};
 }
 
+// v_permlane32_swap: lanes 32-63 of `lo` trade places with lanes 0-31 of `hi`.  Returned: [0] = lo's lower half | hi's lower half,
+// [1] = lo's upper half | hi's upper half.
+__device__ __forceinline__ csp_raw2 csp_swap32(unsigned int lo, unsigned int hi) { return __builtin_amdgcn_permlane32_swap(lo, hi, false, false); }
+// two accumulators that are live in lanes 0-31 only -> one: a's live half in lanes 0-31, b's in lanes 32-63
+__device__ __forceinline__ f32x4 csp_merge(f32x4 va, f32x4 vb) {
+  f32x4 m;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float fa = va[j], fb = vb[j];                            // scalars first: a bit cast of a vector ELEMENT reads element 0 for every j
+    m[j] = __uint_as_float(csp_swap32(__float_as_uint(fa), __float_as_uint(fb))[0]);
+  }
+  return m;
+}
+
 // MODE 0 = MSPA_C2f, 1 = C2f.  WD = bottleneck width (8, 16, 32, 64).
-template <int WD, int MODE>
+// PAIR (WD = 8 only): a 16-row MFMA block carries 8 real output channels there, so lanes 32-63 (g = 2, 3) of every accumulator hold padding.
+// The paired form keeps every MFMA as it is and merges the accumulators of two pixel groups into one register set (group a in lanes 0-31,
+// group b in lanes 32-63; a lane's channels are 4 * (g & 1) ..) before the SiLU / round / store epilogue, which then runs once for both.
+// The front also loads a pair with all 64 lanes live and splits the rounded operand back into two B operands whose upper halves are real
+// zeros (0 * Inf of the neighbouring group must not reach this one).  Same arithmetic in the same order: the outputs are bit-identical.
+template <int WD, int MODE, bool PAIR = false>
 __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_kernel(const CspArgs a) {   // 4: two workgroups per CU (<= 128 VGPRs)
+  static_assert(!PAIR || (WD == 8 && MODE == 0), "the paired epilogue is the wd = 8 MSPA form");
   constexpr int CP = WD / 8;                         // 16-byte pieces per tap
   constexpr int NCHB = WD == 8 ? 2 : (WD == 16 ? 3 : (WD == 32 ? 5 : 8));   // K chunks of the back conv at n = 2 (concat <= 256 channels)
   constexpr int NB = WD >= 16 ? WD / 16 : 1;         // cout blocks of a wd -> wd conv
@@ -152,6 +172,62 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
     const float* bl = (const float*)(wl + (size_t)a.chain_words * 16);
     const int per = ngr / CSP_NW, rem = ngr - per * CSP_NW;   // balanced: the first `rem` waves take one group more
     const int gbeg = wave * per + min(wave, rem), gend = gbeg + per + (wave < rem ? 1 : 0);
+    if constexpr (PAIR) {
+      // groups in pairs: lane (r, g) holds channels 4 (g & 1) .. of pixel r of group g >> 1, so every load, SiLU and store lane is live
+      constexpr int UP = 3;                                      // pairs in flight (the unpaired form has 5 groups)
+      const int hb = lane >> 5, cl = 4 * (g & 1);
+      for (int g0 = gbeg; g0 < gend; g0 += 2 * UP) {
+        int go[UP], ct[UP];
+        csp_raw2 XR[UP][4];
+#pragma unroll
+        for (int u = 0; u < UP; ++u) {
+          const int grp = g0 + 2 * u + hb;
+          region_px(grp * 16 + r, go[u], ct[u]);
+          if (grp >= gend) go[u] = MGDT_OOB, ct[u] = -1;         // an odd run's last group is unpaired: its upper lanes load zeros and store nothing
+#pragma unroll
+          for (int i = 0; i < 4; ++i) XR[u][i] = __builtin_amdgcn_raw_buffer_load_b64(xrs, (uint32_t)go[u] + (uint32_t)((i * WD + cl) * 2), 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < UP; ++u) {
+          if (g0 + 2 * u >= gend) break;                         // wave-uniform
+          const bool hasb = g0 + 2 * u + 1 < gend;               // wave-uniform
+          const int q = (g0 + 2 * u + hb) * 16 + r;
+          f32x4 X[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bf16x4 o = __builtin_bit_cast(bf16x4, XR[u][i]);
+            X[i] = f32x4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};
+          }
+          f32x4 prev;
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            bf16x4 vb;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) vb[e] = (bf16)(X[i][e] + (i ? prev[e] : 0.f));
+            const csp_raw2 vw = __builtin_bit_cast(csp_raw2, vb);
+            // one swap per word against a zero register: [0] = group a's operand, [1] = group b's moved to lanes 0-31, both with lanes 32-63 zero
+            const csp_raw2 s0 = csp_swap32(vw[0], 0u), s1 = csp_swap32(vw[1], 0u);
+            typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int raw4;
+            const bf16x8 Ba = __builtin_bit_cast(bf16x8, (raw4){s0[0], s1[0], 0u, 0u});
+            const bf16x8 Bb = __builtin_bit_cast(bf16x8, (raw4){s0[1], s1[1], 0u, 0u});
+            const f32x4 bi = *(const f32x4*)(bl + i * 16 + 4 * g);
+            const bf16x8 Wf = *(const bf16x8*)(wlane + i * 1024);
+            const f32x4 acca = mma(Wf, Ba, bi);
+            f32x4 accb = bi;
+            if (hasb) accb = mma(Wf, Bb, bi);
+            f32x4 acc = csp_merge(acca, accb);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = (float)(bf16)csp_act(acc[j], a.act);
+            prev = acc;
+            if (ct[u] >= 0) lds_store4(catb + cat_at(ct[u], i * WD + cl), acc);
+          }
+          // bottleneck input = sp2 + x3 (the pending add of block.py:259), zero outside the image
+          f32x4 p0 = prev + X[3];
+          if (go[u] == MGDT_OOB) p0 = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (hb == 0 || hasb) lds_store4(Pb + pt_at(q, cl), p0);
+        }
+      }
+    } else
     for (int g0 = gbeg; g0 < gend; g0 += U) {
       int go[U], ct[U];
       csp_raw2 XR[U][4][NBK];
@@ -301,17 +377,18 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
         const int toff = (tap / 3 - 1) * a.RW + (tap % 3 - 1);
         boff[kc] = toff * PS + ((cp ^ csp_psw<WD>(lo + r + toff)) << 4);   // pixel = lo + 16 k + r: its swizzle is known here
       }
-      auto finish = [&](int q, f32x4 acc) __attribute__((always_inline)) {
+      // cc = the lane's first output channel, live = false: a lane that holds no pixel of its own (paired form without a second group)
+      auto finish = [&](int q, f32x4 acc, int cc, bool live) __attribute__((always_inline)) {
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) acc[jj] = csp_act(acc[jj], a.act);
-        if (q < hi && cch < WD) {
-          char* po = out + pt_at(q, cch);
+        if (live && q < hi && cc < WD) {
+          char* po = out + pt_at(q, cc);
           if (second && a.shortcut) acc += lds_load4(po);       // x + cv2(cv1(x)): `out` still holds the bottleneck's input at this pixel
           int go = 0, ct = -1;
           if (zchk || tocat) region_px(q, go, ct);
           if (zchk && go == MGDT_OOB) acc = f32x4{0.f, 0.f, 0.f, 0.f};
           lds_store4(po, acc);
-          if (tocat && ct >= 0) lds_store4(catb + cat_at(ct, slot0 + (j >> 1) * WD + cch), acc);
+          if (tocat && ct >= 0) lds_store4(catb + cat_at(ct, slot0 + (j >> 1) * WD + cc), acc);
         }
       };
       for (int grp = gv; grp < ng; grp += 2 * gst) {             // two pixel groups per step: two independent accumulator chains
@@ -326,8 +403,12 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
           acca = mma(A[kc], *(const bf16x8*)(pa + boff[kc]), acca);
           accb = mma(A[kc], *(const bf16x8*)(pb + boff[kc]), accb);
         }
-        finish(qa, acca);
-        if (hasb) finish(qb, accb);
+        if constexpr (PAIR) {
+          finish(lane < 32 ? qa : qb, csp_merge(acca, accb), 4 * (g & 1), lane < 32 || hasb);   // one epilogue for both groups, every lane live
+        } else {
+          finish(qa, acca, cch, true);
+          if (hasb) finish(qb, accb, cch, true);
+        }
       }
       __syncthreads();
       if (j == 0) stamp(4);
@@ -568,18 +649,21 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
     (void)hipMalloc((void**)&dbgbuf, dbgcap * 8);
   }
   a.dbg = getenv("MGDT_CSP_DBG") ? dbgbuf : nullptr;
-#define CSP_LAUNCH(WDV, MODEV)                                                                                              \
+  // experiment knob, read per call (not part of the ABI): MGDT_CSP_PAIR=0 = the unpaired wd = 8 form
+  const char* ep = getenv("MGDT_CSP_PAIR");
+  const bool pair = !(ep && ep[0] == '0');
+#define CSP_LAUNCH(...)                                                                                              \
   do {                                                                                                                      \
     static std::atomic<bool> attr{false};                                                                                            \
     if (!attr) {                                                                                                            \
-      hipError_t e_ = hipFuncSetAttribute((const void*)csp_block_kernel<WDV, MODEV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      hipError_t e_ = hipFuncSetAttribute((const void*)csp_block_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       if (e_ != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "csp_block: hipFuncSetAttribute: %s", hipGetErrorString(e_));         \
       attr = true;                                                                                                          \
     }                                                                                                                       \
-    csp_block_kernel<WDV, MODEV><<<grid, CSP_THREADS, g.lds, st>>>(a);                                                      \
+    csp_block_kernel<__VA_ARGS__><<<grid, CSP_THREADS, g.lds, st>>>(a);                                                      \
   } while (0)
   if (mode == 0) {
-    switch (wd) { case 8: CSP_LAUNCH(8, 0); break; case 16: CSP_LAUNCH(16, 0); break; case 32: CSP_LAUNCH(32, 0); break; default: CSP_LAUNCH(64, 0); break; }
+    switch (wd) { case 8: if (pair) CSP_LAUNCH(8, 0, true); else CSP_LAUNCH(8, 0); break; case 16: CSP_LAUNCH(16, 0); break; case 32: CSP_LAUNCH(32, 0); break; default: CSP_LAUNCH(64, 0); break; }
   } else {
     switch (wd) { case 16: CSP_LAUNCH(16, 1); break; case 32: CSP_LAUNCH(32, 1); break; default: CSP_LAUNCH(64, 1); break; }
   }
