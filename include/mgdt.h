@@ -134,7 +134,11 @@ int mgdt_cnx_mlp_fwd(const mgdt_view* t, const mgdt_view* res, const void* packe
  * Conv (nn/modules/block.py:336-338) - packed with mgdt_conv_pack(c, cout, 1, bf16) over input channels in the accumulator order of
  * mgdt_conv1x1_inject_conv_fwd's note (j < c / 32); y then has cout <= c channels and the block's own output is never stored. */
 int mgdt_cnx_block_supported(int n, int h, int w, int c, int dtype);
+/* mgdt_cnx_block_geometry: the tiling mgdt_cnx_block_fwd uses for an h x w map of c channels (no device needed): out[7] = {TH, TW, SEGS (5-pixel
+ * segments per tile row), tiles_x, tiles per image, 16-pixel groups per tile (one per wave, <= 16), dynamic LDS bytes}.  MGDT_BAD_SHAPE when c is
+ * not 32 / 64 / 96 or no tile exists; a map with more tiles than the chip has compute units still has a geometry (mgdt_cnx_block_supported refuses it). */
 size_t mgdt_cnx_block_workspace_bytes(int n, int h, int w, int c);
+int mgdt_cnx_block_geometry(int h, int w, int c, int* out);
 int mgdt_cnx_block_fwd(const mgdt_view* x, const float* dw_w49c, const float* dw_b, const float* ln_w, const float* ln_b, float eps, const void* packed,
                        const float* gamma, const float* beta, const void* tail_w, const float* tail_b, int tail_act, void* ws, size_t ws_bytes,
                        const mgdt_view* y, int dtype, mgdt_stream s);
@@ -304,6 +308,12 @@ int mgdt_image_pad4_fwd(const mgdt_view* x, int x_dtype, const mgdt_view* y, int
 int mgdt_dwconv7_ln_fwd(const mgdt_view* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                         float eps, const mgdt_view* y, int dtype, mgdt_stream s);
 int mgdt_grn_stats_fwd(const mgdt_view* t, const float* gamma, float* ws, float* scale, int dtype, mgdt_stream s);
+/* mgdt_dwconv7_ln_route: the launch mgdt_dwconv7_ln_fwd / mgdt_dwconv7_ln_train_fwd would make for an n x h x w map of c channels, without launching
+ * anything (no device needed): out[5] = {family, tile side (0: generic), workgroups, dynamic LDS bytes, threads per workgroup}.  Families: the row
+ * kernel with 8x8 or 10x10 tiles (bf16 c <= 100, fp32 c <= 60; 10x10 where 8x8 tiles need another round of workgroups over the chip, or do not fit),
+ * the generic one-pixel-per-thread-row kernel otherwise.  MGDT_BAD_SHAPE for a shape the forward call refuses. */
+enum { MGDT_DW_ROW8 = 0, MGDT_DW_ROW10 = 1, MGDT_DW_GENERIC = 2 };
+int mgdt_dwconv7_ln_route(int n, int h, int w, int c, int dtype, int* out);
 
 /* ---- InjectionMultiSum_Auto_pool tail (nn/modules/block.py:381-399) --------------------------------------
  * up branch  (local >= global size): y = local * bilinear(relu6(ga+3)/6) + bilinear(gf)

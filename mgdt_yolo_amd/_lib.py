@@ -74,6 +74,7 @@ PROTOTYPES = {
     'mgdt_cnx_mlp_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, VP, _i, _vp]),
     'mgdt_cnx_block_supported': (_i, [_i, _i, _i, _i, _i]),
     'mgdt_cnx_block_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'mgdt_cnx_block_geometry': (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
     'mgdt_cnx_block_fwd': (_i, [VP, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, VP, _i, _vp]),
     'mgdt_pw_chain_packed_bytes': (_sz, [_i, _i]),
     'mgdt_pw_chain_pack': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
@@ -112,6 +113,7 @@ PROTOTYPES = {
     'mgdt_dcn_col2im_bwd': (_i, [VP, VP, VP, _vp, VP, _i, _vp]),
     'mgdt_val_match_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     'mgdt_grn_stats_fwd': (_i, [VP, _vp, _vp, _vp, _i, _vp]),
+    'mgdt_dwconv7_ln_route': (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     'mgdt_inject_fwd': (_i, [VP, VP, VP, VP, _i, _vp]),
     'mgdt_detect_decode_fwd': (_i, [VP, _i, _i, _f, _i, _i, _vp, _i, _vp]),
     'mgdt_detect_decode_aug_fwd': (_i, [VP, _i, _i, _f, _i, _i, _vp, _vp, _f, _i, _f, _i, _vp]),

@@ -38,7 +38,7 @@ struct CnxArgs {
   int N, H, W, C, TH, TW, RH, RW, SEGS, tiles_x, tiles, n0;
   FastDiv fd_rw, fd_tw;
   GeluCoef gelu;
-  const char* w3; const float* b3; int act3, C3;         // TAIL: a 1x1 Conv + BN + act on the block's output (IFM's closing conv), panel with K in accumulator order
+  const char* w3; const float* b3; int act3, C3, NB3;       // TAIL: a 1x1 Conv + BN + act on the block's output (IFM's closing conv), panel with K in accumulator order
   unsigned long long* dbg;
 };
 
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(CNX_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   }
   __syncthreads();
   if (TAIL) {                                               // the per-wave sums in T have been read: the closing conv's panel goes there
-    constexpr int W3V = (NB2 / 2) * NB2 * 64;               // 16-byte words: KC3 = NB2 / 2 chunks x NB2 cout blocks
+    const int W3V = (NB2 / 2) * a.NB3 * 64;                 // 16-byte words: KC3 = NB2 / 2 chunks x NB3 = cdiv(C3, 16) cout blocks, as mgdt_conv_pack lays them out
     for (int i = tid; i < W3V; i += CNX_THREADS) ((uint4*)Tb)[i] = ((const uint4*)a.w3)[i];
   }
   if (tid == 0) {
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(CNX_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
       const char* const w3lane = Tb + lane * 16;
       f32x4 acc3[NB3];
 #pragma unroll
-      for (int nb = 0; nb < NB3; ++nb) acc3[nb] = *(const f32x4*)(a.b3 + nb * 16 + 4 * g);
+      for (int nb = 0; nb < NB3; ++nb) acc3[nb] = nb < a.NB3 ? *(const f32x4*)(a.b3 + nb * 16 + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};      // blocks past the panel: never stored
 #pragma unroll
       for (int j3 = 0; j3 < KC3; ++j3) {
         bf16x8 B3;
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(CNX_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
           for (int i = 0; i < 4; ++i) B3[h * 4 + i] = (bf16)(acc2[2 * j3 + h][i] + (float)rb[i]);
         }
 #pragma unroll
-        for (int nb = 0; nb < NB3; ++nb) acc3[nb] = mma(*(const bf16x8*)(w3lane + (j3 * NB3 + nb) * 1024), B3, acc3[nb]);
+        for (int nb = 0; nb < NB3; ++nb) acc3[nb] = mma(*(const bf16x8*)(w3lane + (j3 * a.NB3 + nb) * 1024), B3, acc3[nb]);
       }
 #pragma unroll
       for (int nb = 0; nb < NB3; ++nb) {
@@ -448,6 +448,15 @@ extern "C" int mgdt_cnx_block_supported(int n, int h, int w, int c, int dtype) {
   int th, tw;
   if (!cnx_kc1(c, dtype) || n < 1 || h < 1 || w < 1 || !cnx_pick_tile(h, w, c, &th, &tw)) return 0;
   return cdiv(h, th) * cdiv(w, tw) <= 256;
+}
+
+extern "C" int mgdt_cnx_block_geometry(int h, int w, int c, int* out) {
+  int th, tw;
+  if (!out) MGDT_FAIL(MGDT_BAD_ARG, "cnx_block_geometry: null argument");
+  if (!cnx_kc1(c, MGDT_BF16) || h < 1 || w < 1 || !cnx_pick_tile(h, w, c, &th, &tw)) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_block_geometry: %dx%d c=%d not covered", h, w, c);
+  out[0] = th; out[1] = tw; out[2] = cdiv(tw, CNX_PX); out[3] = cdiv(w, tw); out[4] = cdiv(w, tw) * cdiv(h, th); out[5] = (th * tw + 15) >> 4;
+  out[6] = cnx_lds(c, th, tw).total;
+  return MGDT_OK;
 }
 
 /* workspace: [512 x {arrival counter, generation}, uint32: MUST BE ZERO at first use and never written by anyone else] [n * tiles * 4c floats] */
@@ -509,7 +518,7 @@ extern "C" int mgdt_cnx_block_fwd(const mgdt_view* x, const float* dw_w49c, cons
   a.y = (char*)yp;
   a.dww = dw_w49c; a.dwb = dw_b; a.lnw = ln_w; a.lnb = ln_b; a.eps = eps; a.packed = (const char*)packed; a.gamma = gamma; a.beta = beta;
   a.sync = (unsigned*)ws; a.part = (float*)((char*)ws + 4096);
-  a.w3 = (const char*)tail_w; a.b3 = tail_b; a.act3 = tail_act; a.C3 = y->c;
+  a.w3 = (const char*)tail_w; a.b3 = tail_b; a.act3 = tail_act; a.C3 = y->c; a.NB3 = cdiv(y->c, 16);
   a.N = x->n; a.H = x->h; a.W = x->w; a.C = x->c;
   if (!cnx_pick_tile(a.H, a.W, a.C, &a.TH, &a.TW)) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_block: no tile");
   a.SEGS = cdiv(a.TW, CNX_PX); a.RW = a.SEGS * CNX_PX + 6; a.RH = a.TH + 6;

@@ -1113,111 +1113,8 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const T* __restrict__ x
   }
 }
 
-// LDS-tiled variant: one workgroup = an 8x8 output tile of one image x all channels.  The (8+6)x(8+6) input halo is staged
-// once in LDS (each input pixel is used by up to 49 outputs), a thread owns one channel quad and ~6 pixels, keeps one kernel
-// row of weights (7 x float4) in registers at a time; LayerNorm over the pixel's channels goes through LDS partials.
-#define DW_TH 8
-#define DW_TW 8
-template <typename T, int MAXP>
-__global__ __launch_bounds__(256) void dwconv7_ln_tiled_kernel(const T* __restrict__ x, long xsn, long xsh, long xsw,
-                                                               const float* __restrict__ dw, const float* __restrict__ db,
-                                                               const float* __restrict__ lw, const float* __restrict__ lb, float eps,
-                                                               T* __restrict__ y, long ysn, long ysh, long ysw, int H, int W, int C,
-                                                               T* __restrict__ uo, long usn, long ush, long usw) {
-  extern __shared__ __attribute__((aligned(16))) char smem_dw[];
-  const int Q = C / 4, PL = 256 / Q;                    // channel quads, pixel lanes
-  constexpr int HH = DW_TH + 6, HW_ = DW_TW + 6, NPIX = DW_TH * DW_TW;
-  T* halo = (T*)smem_dw;                                // [HH][HW_][C]
-  float* wl = (float*)(smem_dw + (((size_t)HH * HW_ * C * sizeof(T) + 15) & ~(size_t)15));   // [49][C]
-  float* red = wl + 49 * C;                             // [NPIX][Q] partial sums (reused for mean and variance)
-  const int tiles_x = (W + DW_TW - 1) / DW_TW, tiles_y = (H + DW_TH - 1) / DW_TH;
-  const int n = blockIdx.x / (tiles_x * tiles_y), tr = blockIdx.x % (tiles_x * tiles_y);
-  const int ty0 = (tr / tiles_x) * DW_TH, tx0 = (tr % tiles_x) * DW_TW;
-  const int q = threadIdx.x % Q, pl = threadIdx.x / Q;
-  const bool live = pl < PL;
-  if (live)
-    for (int p = pl; p < HH * HW_; p += PL) {            // stage the halo (zero padding outside the image); q, pl fixed per thread
-      int hy = p / HW_, hx = p % HW_;
-      int iy = ty0 + hy - 3, ix = tx0 + hx - 3;
-      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-      if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = load4<T>(x + n * xsn + iy * xsh + ix * xsw + q * 4);
-      store4<T>(halo + (long)p * C + q * 4, v);
-    }
-  for (int i = threadIdx.x; i < 49 * Q; i += 256) *(f32x4*)(wl + i * 4) = *(const f32x4*)(dw + i * 4);
-  __syncthreads();
-  f32x4 acc[MAXP];                                      // MAXP >= ceil(NPIX / PL) (host-selected instantiation)
-  if (live) {
-    const f32x4 bq = *(const f32x4*)(db + q * 4);
-#pragma unroll
-    for (int k = 0; k < MAXP; ++k) acc[k] = bq;
-    for (int ky = 0; ky < 7; ++ky) {
-      f32x4 wr[7];
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx) wr[kx] = *(const f32x4*)(wl + (ky * 7 + kx) * C + q * 4);
-#pragma unroll
-      for (int k = 0; k < MAXP; ++k) {
-        int p = pl + k * PL;
-        if (p < NPIX) {
-          int py = p / DW_TW, px = p % DW_TW;
-          const T* hp = halo + ((long)(py + ky) * HW_ + px) * C + q * 4;
-#pragma unroll
-          for (int kx = 0; kx < 7; ++kx) {
-            f32x4 v = load4<T>(hp + kx * C);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[k][j] = fmaf(v[j], wr[kx][j], acc[k][j]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < MAXP; ++k) {
-      int p = pl + k * PL;
-      if (p < NPIX) red[p * Q + q] = acc[k][0] + acc[k][1] + acc[k][2] + acc[k][3];
-    }
-  }
-  __syncthreads();
-  float mean[MAXP];
-  if (live) {
-#pragma unroll
-    for (int k = 0; k < MAXP; ++k) {
-      int p = pl + k * PL;
-      mean[k] = 0.f;
-      if (p < NPIX) {
-        for (int j = 0; j < Q; ++j) mean[k] += red[p * Q + j];
-        mean[k] /= (float)C;
-      }
-    }
-  }
-  __syncthreads();
-  if (live) {
-#pragma unroll
-    for (int k = 0; k < MAXP; ++k) {
-      int p = pl + k * PL;
-      if (p < NPIX) {
-        f32x4 d = acc[k] - mean[k];
-        red[p * Q + q] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
-      }
-    }
-  }
-  __syncthreads();
-  if (live) {
-    const f32x4 gq = *(const f32x4*)(lw + q * 4), bq2 = *(const f32x4*)(lb + q * 4);
-#pragma unroll
-    for (int k = 0; k < MAXP; ++k) {
-      int p = pl + k * PL;
-      if (p >= NPIX) continue;
-      int oy = ty0 + p / DW_TW, ox = tx0 + p % DW_TW;
-      if (oy >= H || ox >= W) continue;
-      float var = 0.f;
-      for (int j = 0; j < Q; ++j) var += red[p * Q + j];
-      float rstd = 1.f / sqrtf(var / (float)C + eps);
-      if (uo) store4<T>(uo + n * usn + oy * ush + ox * usw + q * 4, acc[k]);
-      store4<T>(y + n * ysn + oy * ysh + ox * ysw + q * 4, (acc[k] - mean[k]) * rstd * gq + bq2);
-    }
-  }
-}
-
-// Row-sliding variant (C <= 128): a thread owns one channel quad and one ROW of the 8x8 output tile.  Per kernel row it reads the
+// Row-sliding variant (C <= 128): a thread owns one channel quad and one ROW of the TS x TS output tile (TS = 8 or 10); the
+// (TS+6) x (TS+6) input halo is staged once in LDS.  Per kernel row it reads the
 // 14 halo values of its row once and reuses each for up to 7 of its 8 outputs from registers: 4x fewer LDS reads and bf16->fp32
 // conversions than one-pixel-per-iteration, 8 independent accumulators of ILP.  LayerNorm: per-pixel partials -> 64 threads
 // reduce over the quads -> broadcast, twice (mean, then centred variance: the two-pass form F.layer_norm uses).
@@ -1297,10 +1194,10 @@ __global__ __launch_bounds__(256) void dwconv7_ln_row_kernel(const T* __restrict
 #pragma unroll
   for (int k = 0; k < TS; ++k) red[(row * TS + k) * Q + q] = acc[k][0] + acc[k][1] + acc[k][2] + acc[k][3];
   __syncthreads();
-  if (threadIdx.x < NPIX) {
+  for (int p = threadIdx.x; p < NPIX; p += blockDim.x) {     // a workgroup has TS * Q threads: fewer than NPIX when C < 4 * TS
     float m = 0.f;
-    for (int j = 0; j < Q; ++j) m += red[threadIdx.x * Q + j];
-    stat[threadIdx.x] = m / (float)C;
+    for (int j = 0; j < Q; ++j) m += red[p * Q + j];
+    stat[p] = m / (float)C;
   }
   __syncthreads();
   float mean[TS];
@@ -1311,10 +1208,10 @@ __global__ __launch_bounds__(256) void dwconv7_ln_row_kernel(const T* __restrict
     red[(row * TS + k) * Q + q] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
   }
   __syncthreads();
-  if (threadIdx.x < NPIX) {
+  for (int p = threadIdx.x; p < NPIX; p += blockDim.x) {
     float var = 0.f;
-    for (int j = 0; j < Q; ++j) var += red[threadIdx.x * Q + j];
-    stat[threadIdx.x] = 1.f / sqrtf(var / (float)C + eps);
+    for (int j = 0; j < Q; ++j) var += red[p * Q + j];
+    stat[p] = 1.f / sqrtf(var / (float)C + eps);
   }
   __syncthreads();
   if (dbgw) TT[4] = wall_clock64();
@@ -1331,6 +1228,42 @@ __global__ __launch_bounds__(256) void dwconv7_ln_row_kernel(const T* __restrict
     }
   }
   if (dbgw) { TT[5] = wall_clock64(); for (int i = 0; i < 6; ++i) dbg[blockIdx.x * 6 + i] = TT[i]; }
+}
+
+// The launch plan of mgdt_dwconv7_ln_fwd / _train_fwd: decided here, executed by dwconv7_ln_impl, reported by mgdt_dwconv7_ln_route.
+// Row kernel, tile side 8 or 10: whichever needs fewer rounds of workgroups over the chip x pixels per round (a 40x40 map: 25 tiles of 8x8 per
+// image = 800 workgroups = two rounds at 2 per CU; 16 tiles of 10x10 = one round); the generic kernel when neither fits its LDS / thread budget
+// (bf16 c > 100, fp32 c > 60).  An 8x8 LDS-tiled kernel with several pixels per thread used to sit between the two: every shape whose tile fitted its
+// 64 KiB also fitted the row kernel's, so no shape ever reached it (tests/test_cnx_kernels.py restates the census).
+struct DwPlan { int family, ts, nwg, lds, threads; };
+static DwPlan dwconv7_ln_plan(int n, int h, int w, int c, int dtype) {
+  const int Qt = c / 4;
+  auto lds_of = [&](int ts) {
+    const size_t halo_b = ((size_t)(ts + 6) * (ts + 6) * c * dtype_size(dtype) + 15) & ~(size_t)15;
+    return halo_b + (size_t)49 * c * 4 + (size_t)ts * ts * Qt * 4 + (size_t)ts * ts * sizeof(float);
+  };
+  auto cost_of = [&](int ts) -> long {
+    const size_t l = lds_of(ts);
+    if (ts * Qt > 256 || l + 256 > (size_t)(ts == 8 ? 64 : 80) * 1024) return -1;
+    const long nwg = (long)n * cdiv(h, ts) * cdiv(w, ts), per_cu = std::max<long>(1, std::min<long>(160 * 1024 / (long)(l + 256), 2048 / (ts * Qt)));
+    return cdiv(nwg, 256 * per_cu) * ts * ts;
+  };
+  static const int force_ts = getenv("MGDT_DW_TS") ? atoi(getenv("MGDT_DW_TS")) : 0;      // experiment knob: 8 or 10 picks between the two row kernels
+  const long c8 = cost_of(8), c10 = cost_of(10);
+  const int ts = force_ts == 8 || force_ts == 10 ? force_ts : (c10 >= 0 && (c8 < 0 || c10 < c8) ? 10 : 8);
+  if (Qt <= 32 && (ts == 8 ? c8 : c10) >= 0)
+    return DwPlan{ts == 8 ? MGDT_DW_ROW8 : MGDT_DW_ROW10, ts, n * cdiv(h, ts) * cdiv(w, ts), (int)lds_of(ts), ts * Qt};
+  const int PPB = 256 / Qt;
+  return DwPlan{MGDT_DW_GENERIC, 0, (int)cdiv((long)n * h * w, (long)PPB), 0, 256};
+}
+
+extern "C" int mgdt_dwconv7_ln_route(int n, int h, int w, int c, int dtype, int* out) {
+  if (!out) MGDT_FAIL(MGDT_BAD_ARG, "dwconv7_ln_route: null argument");
+  if (n < 1 || h < 1 || w < 1 || c < 4 || c % 4 || c > 1024 || (dtype != MGDT_F32 && dtype != MGDT_BF16) || (long)n * h * w >= 0x7fffffffL)
+    MGDT_FAIL(MGDT_BAD_SHAPE, "dwconv7_ln_route: n=%d %dx%d c=%d dtype=%d not covered (c%%4==0, c<=1024)", n, h, w, c, dtype);
+  const DwPlan p = dwconv7_ln_plan(n, h, w, c, dtype);
+  out[0] = p.family; out[1] = p.ts; out[2] = p.nwg; out[3] = p.lds; out[4] = p.threads;
+  return MGDT_OK;
 }
 
 static int dwconv7_ln_impl(const mgdt_view* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float eps,
@@ -1350,69 +1283,41 @@ static int dwconv7_ln_impl(const mgdt_view* x, const float* dw_w, const float* d
   if (!view_ok(x) || !view_ok(y) || !dw_w || !dw_b || !ln_w || !ln_b) MGDT_FAIL(MGDT_BAD_ARG, "dwconv7_ln: null/empty argument");
   if (!vec4_ok(x, dtype) || !vec4_ok(y, dtype) || x->n != y->n || x->h != y->h || x->w != y->w || x->c != y->c || x->c / 4 > 256)
     MGDT_FAIL(MGDT_BAD_SHAPE, "dwconv7_ln: matching NHWC views, c%%4==0, c<=1024");
-  {   // LDS-tiled fast path: one thread per (channel quad, tile row); tile side 8 or 10: whichever needs fewer rounds of workgroups over the
-      // chip x pixels per round (a 40x40 map: 25 tiles of 8x8 per image = 800 workgroups = two rounds at 2 per CU; 16 tiles of 10x10 = one round)
-    const int Qt = x->c / 4;
-    auto lds_of = [&](int ts) {
-      const size_t halo_b = ((size_t)(ts + 6) * (ts + 6) * x->c * dtype_size(dtype) + 15) & ~(size_t)15;
-      return halo_b + (size_t)49 * x->c * 4 + (size_t)ts * ts * Qt * 4 + (size_t)ts * ts * sizeof(float);
-    };
-    auto cost_of = [&](int ts) -> long {
-      const size_t l = lds_of(ts);
-      if (ts * Qt > 256 || l + 256 > (ts == 8 ? 64 : 80) * 1024) return -1;
-      const long nwg = (long)x->n * cdiv(x->h, ts) * cdiv(x->w, ts), per_cu = std::max<long>(1, std::min<long>(160 * 1024 / (long)(l + 256), 2048 / (ts * Qt)));
-      return cdiv(nwg, 256 * per_cu) * ts * ts;
-    };
-    static const int force_ts = getenv("MGDT_DW_TS") ? atoi(getenv("MGDT_DW_TS")) : 0;      // experiment knob
-    const long c8 = cost_of(8), c10 = cost_of(10);
-    const int ts = force_ts == 8 || force_ts == 10 ? force_ts : (c10 >= 0 && (c8 < 0 || c10 < c8) ? 10 : 8);
-    if (Qt <= 32 && (ts == 8 ? c8 : c10) >= 0) {
-      const int tiles = cdiv(x->h, ts) * cdiv(x->w, ts);
-      const size_t lds_t = lds_of(ts);
-      static unsigned long long* dbgbuf = nullptr;
-      if (getenv("MGDT_DW_DBG") && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, (size_t)x->n * tiles * 6 * 8);
-      static std::atomic<bool> attr10_f32{false}, attr10_bf16{false};
-      if (ts == 10) {
-        MGDT_DISPATCH_DTYPE(dtype, {
-          std::atomic<bool>& fl = sizeof(T) == 2 ? attr10_bf16 : attr10_f32;
-          if (!fl.load()) {
-            (void)hipFuncSetAttribute((const void*)dwconv7_ln_row_kernel<T, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            fl.store(true);
-          }
-          dwconv7_ln_row_kernel<T, 10><<<x->n * tiles, 10 * Qt, lds_t, (hipStream_t)s>>>(
-              (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c,
-              u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0, dbgbuf);
-        });
-      } else {
-        MGDT_DISPATCH_DTYPE(dtype, (dwconv7_ln_row_kernel<T, 8><<<x->n * tiles, 8 * Qt, lds_t, (hipStream_t)s>>>(
-                                       (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c,
-                                       u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0, dbgbuf)));
-      }
-      MGDT_CHECK_LAUNCH("dwconv7_ln_fwd(row)");
-      if (dbgbuf) {
-        const int nwg = x->n * tiles;
-        std::vector<unsigned long long> h((size_t)nwg * 6);
-        (void)hipStreamSynchronize((hipStream_t)s);
-        (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
-        unsigned long long t0 = ~0ull, t5 = 0; double ph[5] = {0, 0, 0, 0, 0};
-        for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, h[i * 6]); t5 = std::max(t5, h[i * 6 + 5]); for (int j = 0; j < 5; ++j) ph[j] += (double)(h[i * 6 + j + 1] - h[i * 6 + j]); }
-        fprintf(stderr, "dwconv row x10ns: span %llu; avg per WG: halo %.0f weights+sync %.0f taps %.0f layernorm %.0f store %.0f\n", t5 - t0, ph[0] / nwg, ph[1] / nwg,
-                ph[2] / nwg, ph[3] / nwg, ph[4] / nwg);
-      }
-      return MGDT_OK;
+  const DwPlan pl = dwconv7_ln_plan(x->n, x->h, x->w, x->c, dtype);
+  if (pl.family != MGDT_DW_GENERIC) {   // row kernel: one thread per (channel quad, tile row)
+    const int Qt = x->c / 4, ts = pl.ts, tiles = cdiv(x->h, ts) * cdiv(x->w, ts);
+    const size_t lds_t = (size_t)pl.lds;
+    static unsigned long long* dbgbuf = nullptr;
+    if (getenv("MGDT_DW_DBG") && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, (size_t)x->n * tiles * 6 * 8);
+    static std::atomic<bool> attr10_f32{false}, attr10_bf16{false};
+    if (ts == 10) {
+      MGDT_DISPATCH_DTYPE(dtype, {
+        std::atomic<bool>& fl = sizeof(T) == 2 ? attr10_bf16 : attr10_f32;
+        if (!fl.load()) {
+          (void)hipFuncSetAttribute((const void*)dwconv7_ln_row_kernel<T, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+          fl.store(true);
+        }
+        dwconv7_ln_row_kernel<T, 10><<<x->n * tiles, 10 * Qt, lds_t, (hipStream_t)s>>>(
+            (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c,
+            u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0, dbgbuf);
+      });
+    } else {
+      MGDT_DISPATCH_DTYPE(dtype, (dwconv7_ln_row_kernel<T, 8><<<x->n * tiles, 8 * Qt, lds_t, (hipStream_t)s>>>(
+                                     (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c,
+                                     u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0, dbgbuf)));
     }
-    const size_t lds_t = (((size_t)(DW_TH + 6) * (DW_TW + 6) * x->c * dtype_size(dtype) + 15) & ~(size_t)15) + (size_t)49 * x->c * 4 + (size_t)DW_TH * DW_TW * Qt * 4;
-    if (Qt <= 64 && lds_t <= 64 * 1024) {
-      const int tiles = cdiv(x->h, DW_TH) * cdiv(x->w, DW_TW);
-      const int need = cdiv(DW_TH * DW_TW, 256 / Qt);      // pixels per thread
-#define DWT_L(MP) MGDT_DISPATCH_DTYPE(dtype, (dwconv7_ln_tiled_kernel<T, MP><<<x->n * tiles, 256, lds_t, (hipStream_t)s>>>( \
-                                     (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c, \
-                                     u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0)))
-      if (need <= 4) DWT_L(4); else if (need <= 7) DWT_L(7); else if (need <= 8) DWT_L(8); else DWT_L(16);
-#undef DWT_L
-      MGDT_CHECK_LAUNCH("dwconv7_ln_fwd(tiled)");
-      return MGDT_OK;
+    MGDT_CHECK_LAUNCH("dwconv7_ln_fwd(row)");
+    if (dbgbuf) {
+      const int nwg = x->n * tiles;
+      std::vector<unsigned long long> h((size_t)nwg * 6);
+      (void)hipStreamSynchronize((hipStream_t)s);
+      (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
+      unsigned long long t0 = ~0ull, t5 = 0; double ph[5] = {0, 0, 0, 0, 0};
+      for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, h[i * 6]); t5 = std::max(t5, h[i * 6 + 5]); for (int j = 0; j < 5; ++j) ph[j] += (double)(h[i * 6 + j + 1] - h[i * 6 + j]); }
+      fprintf(stderr, "dwconv row x10ns: span %llu; avg per WG: halo %.0f weights+sync %.0f taps %.0f layernorm %.0f store %.0f\n", t5 - t0, ph[0] / nwg, ph[1] / nwg,
+              ph[2] / nwg, ph[3] / nwg, ph[4] / nwg);
     }
+    return MGDT_OK;
   }
   int Q = x->c / 4, PPB = 256 / Q;
   long M = (long)x->n * x->h * x->w;

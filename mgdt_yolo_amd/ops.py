@@ -476,6 +476,14 @@ def dwconv7_ln(x, dw_w49c, dw_b, ln_w, ln_b, eps, out=None):
     return out
 
 
+def dwconv7_ln_route(n, h, w, c, dtype):
+    """mgdt_dwconv7_ln_route: the launch dwconv7_ln / dwconv7_ln_train would make, as a dict (family 'row8' / 'row10' / 'generic', ts, nwg, lds_bytes,
+    threads).  Launches nothing and needs no device."""
+    out = (C.c_int * 5)()
+    L.check(L.lib().mgdt_dwconv7_ln_route(int(n), int(h), int(w), int(c), dtype_code(dtype), out), 'dwconv7_ln_route')
+    return dict(family=('row8', 'row10', 'generic')[out[0]], ts=out[1], nwg=out[2], lds_bytes=out[3], threads=out[4])
+
+
 def grn_scale(t, gamma):
     """scale[n,c] = gamma[c]*Nx[n,c] + 1 (fp32) for the GRN-folded pwconv2."""
     b, c = t.shape[:2]
@@ -573,6 +581,14 @@ class lane:
 def cnx_block_supported(x, dtype):
     b, c, h, w = x.shape
     return bool(FUSED_CNX_BLOCK and x.dtype == dtype and is_nhwc(x) and L.lib().mgdt_cnx_block_supported(b, h, w, c, dtype_code(dtype)))
+
+
+def cnx_block_geometry(h, w, c):
+    """mgdt_cnx_block_geometry: the tiling of cnx_block for an h x w map of c channels, as a dict (TH, TW, SEGS, tiles_x, tiles, NWT = 16-pixel groups
+    per tile, lds_bytes).  Launches nothing and needs no device."""
+    out = (C.c_int * 7)()
+    L.check(L.lib().mgdt_cnx_block_geometry(int(h), int(w), int(c), out), 'cnx_block_geometry')
+    return dict(zip(('TH', 'TW', 'SEGS', 'tiles_x', 'tiles', 'NWT', 'lds_bytes'), out))
 
 
 def cnx_block(x, dw_w49c, dw_b, ln_w, ln_b, eps, pk, gamma, beta, out=None, tail=None, tail_act=0):

@@ -1,6 +1,7 @@
 """Shared helpers of the per-route kernel tests (test_reverse_kernels.py, test_forward_kernels.py, test_tood_kernels.py, test_block_kernels.py,
-test_conv_kernels.py): seeded inputs already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds,
-the float64 deformable-conv reference pieces, the restatements of the fused forward block kernels and of the fused convolution.  A plain module, not a
+test_conv_kernels.py, test_cnx_kernels.py): seeded inputs already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds,
+the float64 deformable-conv reference pieces, the restatements of the fused forward block kernels, of the fused convolution and of the ConvNeXtV2
+kernels with their flip allowance.  A plain module, not a
 conftest."""
 import zlib
 
@@ -571,3 +572,165 @@ def ref_sgd(p, g, buf, wd, lr, lr_bias, momentum, nesterov, first, coef):
 def ref_ema(ema, p, d):
     """mgdt_ema_update in float64 (ModelEMA.update, torch_utils.py:342-361), d as the C ABI receives it."""
     return f32r(d) * ema.double() + (1.0 - f32r(d)) * p.double()
+
+
+# ------------------------------------------------------------------------------------------------ ConvNeXtV2 forward (test_cnx_kernels.py)
+# Restatements of mgdt_dwconv7_ln_fwd, mgdt_cnx_mlp_fwd, mgdt_cnx_block_fwd and mgdt_grn_stats_fwd in plain torch on the CPU, stage by stage, so that
+# the flip allowance below can re-enter them behind any of their internal bf16 rounding points.  `dt` is the evaluation dtype as above.
+def ref_dwconv7_ln(x, dw, dwb, lnw, lnb, eps, dt=torch.float64):
+    """mgdt_dwconv7_ln_fwd / _train_fwd: u = depth-wise 7x7 conv (49 taps, zero padding 3) + bias; y = LayerNorm over the channels in the two-pass form
+    (mean, then the centred variance; rstd = 1 / sqrt(var + eps), eps as the fp32 the C ABI receives), computed from the UNROUNDED u.  dw (C, 1, 7, 7).
+    Returns (y, u) before their store rounding."""
+    import torch.nn.functional as F
+    c = x.shape[1]
+    u = F.conv2d(x.to(dt), dw.to(dt), dwb.to(dt), 1, 3, 1, c)
+    d = u - u.mean(1, keepdim=True)
+    var = (d * d).mean(1, keepdim=True)
+    y = d * (1.0 / torch.sqrt(var + f32r(eps))) * lnw.to(dt).view(1, -1, 1, 1) + lnb.to(dt).view(1, -1, 1, 1)
+    return y, u
+
+
+def _erf_gelu(t):
+    return 0.5 * t * (1.0 + torch.erf(t * 0.70710678118654752))
+
+
+def _pw(t, w, b):
+    """Linear over the channels of an NCHW map: w (cout, cin), b (cout)."""
+    return torch.einsum('oc,bchw->bohw', w, t) + b.view(1, -1, 1, 1)
+
+
+def cnx_h_pre(t, w1, b1, dt):
+    """gelu(W1 t + b1) with the exact erf GELU (the kernels' polynomial is held to it by a host-only test), before the bf16 rounding of h."""
+    return _erf_gelu(_pw(t.to(dt), w1.to(dt), b1.to(dt)))
+
+
+def ref_grn_scale(t, gamma, dt=torch.float64):
+    """mgdt_grn_stats_fwd and the GRN prologue of the fused kernels: Gx = sqrt(sum_hw t^2), scale = gamma * Gx / (mean_c Gx + 1e-6) + 1; (B, C)."""
+    gx = torch.sqrt((t.to(dt) ** 2).sum((2, 3)))
+    return gamma.to(dt).view(1, -1) * (gx / (gx.mean(1, keepdim=True) + f32r(1e-6))) + 1.0
+
+
+def cnx_v_pre(h, scale, beta, dt):
+    return h.to(dt) * scale.to(dt)[:, :, None, None] + beta.to(dt).view(1, -1, 1, 1)
+
+
+def ref_cnx_mlp(t, res, w1, b1, w2, b2, gamma, beta, dt=torch.float64, stages=False):
+    """mgdt_cnx_mlp_fwd: h = bf16(gelu(W1 t + b1)); Gx over the ROUNDED h; v = bf16(h * scale + beta); y = W2 v + b2 (+ res).  Weights (4C, C) / (C, 4C)
+    bf16-representable, biases / gamma / beta fp32.  Returns y before its store rounding; with stages=True also a dict of the values before and after
+    the two internal roundings (h_pre, h, scale, v_pre, v)."""
+    h_pre = cnx_h_pre(t, w1, b1, dt)
+    h = _rb(h_pre)
+    scale = ref_grn_scale(h, gamma, dt)
+    v_pre = cnx_v_pre(h, scale, beta, dt)
+    v = _rb(v_pre)
+    y = _pw(v, w2.to(dt), b2.to(dt))
+    if res is not None:
+        y = y + res.to(dt)
+    return (y, dict(h_pre=h_pre, h=h, scale=scale, v_pre=v_pre, v=v)) if stages else y
+
+
+def ref_cnx_block(x, dw, dwb, lnw, lnb, eps, w1, b1, w2, b2, gamma, beta, dt=torch.float64, stages=False):
+    """mgdt_cnx_block_fwd without the closing conv: ref_cnx_mlp(bf16(ref_dwconv7_ln(x).y), x, ...): t is rounded to bf16 where the kernel stores it to
+    LDS as pwconv1's operand.  With stages=True the dict also holds t_pre and t."""
+    t_pre = ref_dwconv7_ln(x, dw, dwb, lnw, lnb, eps, dt)[0]
+    t = _rb(t_pre)
+    out = ref_cnx_mlp(t, x, w1, b1, w2, b2, gamma, beta, dt, stages)
+    if stages:
+        out[1].update(t_pre=t_pre, t=t)
+    return out
+
+
+def ref_cnx_tail(ymap, cp, act, dt=torch.float64):
+    """The closing 1x1 conv of mgdt_cnx_block_fwd on the block's bf16 output map: act(conv1x1_folded(ymap)), cp = ConvP (BN folded by _fold)."""
+    return _ACTS[act](cp(ymap.to(dt), dt))
+
+
+def _bf16_other(pre):
+    """For fp64 values `pre`: (nearest bf16 value, the bf16 neighbour on the other side of pre, distance of pre from the rounding boundary between the
+    two).  Where pre is itself a bf16 value the neighbour is the next one away from zero and the distance half a step."""
+    r = pre.to(BF16)
+    bits = r.view(torch.int16).to(torch.int32)
+    rd = r.double()
+    away = ((pre - rd) * torch.where(rd == 0, pre, rd) >= 0)              # the other neighbour has the larger magnitude
+    mag = (bits & 0x7fff) + torch.where(away, 1, -1)
+    flip_sign = mag < 0                                                  # stepping down from +-0: the smallest value of the other sign
+    mag = torch.where(flip_sign, torch.ones_like(mag), mag)
+    sign = (bits & 0x8000) ^ torch.where(flip_sign, 0x8000, 0)
+    sign = torch.where((rd == 0) & (pre != 0), torch.where(pre < 0, 0x8000, 0) ^ torch.where(flip_sign, 0x8000, 0), sign)
+    ob = (sign | mag)
+    ob = torch.where(ob >= 0x8000, ob - 0x10000, ob).to(torch.int16)
+    other = ob.view(BF16).double()
+    return rd, other, ((rd + other) / 2 - pre).abs()
+
+
+def cnx_deltas(st, w1, b1, gamma, beta, ln=None):
+    """delta_s of the flip allowance for one case, from the restatement alone: 4 x the largest |fp32 - fp64| difference of stage s's pre-rounding value
+    when both evaluations are fed the same (float64-rounded) upstream values, + 1e-6 at h for the kernels' polynomial GELU.  ln = (x, dw, dwb, lnw, lnb,
+    eps) adds the stage t of the whole block.  The device sums in other orders (tap order, MFMA K order, butterflies, per-tile GRN partials) of the
+    same lengths and error magnitudes; the factor 4 covers an ordering-dependent constant."""
+    d = {}
+    if ln is not None:
+        d['t'] = 4 * (ref_dwconv7_ln(*ln, dt=F32)[0].double() - st['t_pre']).abs().max().item()
+    t = st['t']
+    d['h'] = 4 * (cnx_h_pre(t, w1, b1, F32).double() - st['h_pre']).abs().max().item() + 1e-6
+    d['v'] = 4 * (cnx_v_pre(st['h'], ref_grn_scale(st['h'], gamma, F32), beta, F32).double() - st['v_pre']).abs().max().item()
+    return d
+
+
+def cnx_allowance(st, deltas, w1, b1, w2, beta):
+    """The flip allowance of mgdt_cnx_mlp_fwd / mgdt_cnx_block_fwd, computed from the float64 reference alone (st = the stages of ref_cnx_mlp /
+    ref_cnx_block).  An element of an internal rounding point s (t, h, v) is undecided when its pre-rounding value lies within deltas[s] of a bf16
+    rounding boundary: a correct fp32 kernel may round it to the other neighbour.  For every undecided element the stages behind it are evaluated
+    again with that ONE element moved to its other neighbour, the image's GRN scale frozen and the later stages rounded to nearest as usual; |delta y|
+    is added to the allowance of the element's pixel.  Returns (allowance (B, C, H, W), {stage: number of undecided elements})."""
+    B, HD, H, W = st['h'].shape
+    w2a = w2.double().abs()
+    scale = st['scale'][:, :, None, None]
+    bt = beta.double().view(1, -1, 1, 1)
+    count = {}
+    # v: one element of pwconv2's operand moves by one bf16 step
+    _, v_o, v_d = _bf16_other(st['v_pre'])
+    und = v_d < deltas['v']
+    count['v'] = int(und.sum())
+    dv = torch.where(und, (v_o - st['v']).abs(), torch.zeros_like(v_o))
+    # h: the element's v is formed and rounded again from the moved h
+    _, h_o, h_d = _bf16_other(st['h_pre'])
+    und = h_d < deltas['h']
+    count['h'] = int(und.sum())
+    dv = dv + torch.where(und, (_rb(h_o * scale + bt) - st['v']).abs(), torch.zeros_like(h_o))
+    allow = torch.einsum('oc,bchw->bohw', w2a, dv)
+    # t: the whole hidden column of the pixel is evaluated again
+    if 't' in deltas:
+        _, t_o, t_d = _bf16_other(st['t_pre'])
+        und = t_d < deltas['t']
+        count['t'] = int(und.sum())
+        idx = und.nonzero()                                               # (n, 4): b, channel, y, x
+        w1d, b1d, w2d = w1.double(), b1.double(), w2.double()
+        for s0 in range(0, idx.shape[0], 2048):
+            b_, k_, y_, x_ = idx[s0:s0 + 2048].unbind(1)
+            tp = st['t'][b_, :, y_, x_].clone()                           # (n, C)
+            tp[torch.arange(tp.shape[0]), k_] = t_o[b_, k_, y_, x_]
+            h2 = _rb(_erf_gelu(tp @ w1d.t() + b1d))
+            v2 = _rb(h2 * st['scale'][b_] + beta.double())
+            dy = ((v2 - st['v'][b_, :, y_, x_]) @ w2d.t()).abs()          # (n, C)
+            allow.permute(0, 2, 3, 1).index_put_((b_, y_, x_), dy, accumulate=True)
+    return allow, count
+
+
+def _bf16_bound(ref):
+    return 2.0 ** -8 * ref.abs() + 1e-3 * ref.abs().max().item()
+
+
+def _close_allow(got, ref, allow, what=''):
+    """_close for a bf16 output whose elements may also move by their flip allowance: |got - ref| <= the unchanged bf16 bound + allowance.  Prints the
+    largest share of that bound used, and of the plain bound where the allowance is below a tenth of it."""
+    got = got.detach().double().cpu().reshape(ref.shape)
+    assert torch.isfinite(got).all(), (what, 'non-finite output')
+    err, bound = (got - ref).abs(), _bf16_bound(ref)
+    use = (err / (bound + allow)).max().item()
+    quiet = allow < 0.1 * bound
+    plain = (err / bound)[quiet].max().item() if quiet.any() else 0.0
+    print(f'{what}: uses {use:.3f} of bound + allowance, {plain:.3f} of the plain bf16 bound where the allowance is below a tenth of it '
+          f'({100.0 * quiet.float().mean().item():.1f} % of the elements)')
+    assert use <= 1.0, (what, 'worst share of bound + allowance', use, 'elements over', int((err > bound + allow).sum()))
+    return use, plain

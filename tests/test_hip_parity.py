@@ -195,11 +195,12 @@ def test_convnext_block_barrier_words_survive_a_change_of_shape():
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
 @pytest.mark.parametrize('b,c,hw', [(32, 96, (40, 40)), (3, 96, (23, 17)), (2, 64, (13, 9)), (1, 32, (7, 21)), (2, 160, (12, 10))],
-                         ids=['bench-tile10', 'odd-96', 'c64', 'c32', 'c160-tiled'])
+                         ids=['bench-bf16-row10-f32-generic', 'odd-96', 'c64', 'c32', 'c160-generic'])
 def test_dwconv7_layernorm_kernel_vs_torch(b, c, hw, dtype):
     """The ConvNeXt block's first half (convnextv2.py:61-66: 7x7 depth-wise conv, channels-last LayerNorm) in one launch, every tile shape the
-    host picks (10x10 tiles for the bench map: one round of workgroups; 8x8 otherwise; the generic kernels for wide maps), against
-    F.conv2d(groups=C) + F.layer_norm in float64.  The training form also returns the conv output `u`."""
+    host picks (bf16: 10x10 row tiles for the bench map - one round of workgroups - and 8x8 otherwise; fp32 c >= 64 and every c = 160 take the
+    generic kernel: tests/test_cnx_kernels.py asserts each route from mgdt_dwconv7_ln_route), against F.conv2d(groups=C) + F.layer_norm in float64.
+    The training form also returns the conv output `u`."""
     import torch.nn.functional as F
     from mgdt_yolo_amd import ops
     gen = torch.Generator().manual_seed(c + hw[0])
