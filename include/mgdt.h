@@ -156,6 +156,12 @@ int mgdt_stem2_fwd(const mgdt_view* x, int x_dtype, const void* packed0, const f
  * The kernel is persistent: out[0] = tiles (8 x 16 output pixels each), out[1] = workgroups launched (<= tiles, <= out[3] * out[4]; the experiment
  * knob MGDT_STEM_WGS=<n> in the environment caps it), out[2] = LDS bytes per workgroup, out[3] = workgroups per compute unit, out[4] = compute units. */
 int mgdt_stem2_geometry(int n, int h, int w, int cu_count, int* out);
+/* Host-side route query: what mgdt_stem2_fwd would launch for the image view x (x_dtype) and the output view y on a device with cu_count compute units
+ * (<= 0: the current device's), without launching.  The launch and this query run the same planning function, MGDT_STEM_WGS included.  Pointers are only
+ * tested for alignment.  out[7] = {fast loader (1: bf16 image with contiguous, 16-byte aligned rows and W % 8 == 0 - 16-byte loads, next patch
+ * prefetched; 0: the element-wise loader), tiles_x, tiles_y, tiles, workgroups, tiles per XCD range, status}: status is MGDT_OK, or what the launch
+ * fails with before launching anything (the other entries are then 0). */
+int mgdt_stem2_route(const mgdt_view* x, int x_dtype, const mgdt_view* y, int cu_count, int* out);
 
 /* ---- Detect head tail in one launch, bf16 (nn/modules/head.py:150-177): the two final 1x1 convs with bias (box c2 -> 16, cls c3 -> nc), the raw
  * (N, 16+nc, H, W) map and its decode (DFL expectation, dist2bbox, stride, sigmoid) into y[N][4+nc][a_total] at anchor offset a_off.
@@ -263,6 +269,12 @@ int mgdt_conv_pack_direct(const float* w_oihw, const float* conv_bias, const flo
                           float* w_out, float* bias_out, mgdt_stream s);
 int mgdt_conv2d_direct_fwd(const mgdt_view* x, int x_dtype, const float* w_gemm, const float* bias, int k, int stride,
                            int groups, int act, const mgdt_view* y, int dtype, mgdt_stream s);
+/* Host-side route query: what mgdt_conv2d_direct_fwd would launch for these views, without launching and without a device; the launch executes the plan
+ * this reports.  Pointers are only tested for alignment (y's).  out[4] = {family, grid x, grid y, status}.  MGDT_DIRECT_STEM: k = 3, groups = 1,
+ * cin <= 4, cout % 16 == 0, y NHWC with 16-byte aligned pixels (y->p % 16 == 0 and sw, sh, sn multiples of 4 fp32 / 8 bf16 elements), x_dtype fp32 /
+ * uint8, or bf16 with a bf16 y; MGDT_DIRECT_GENERIC: everything else the call accepts; MGDT_DIRECT_REFUSED: status is what the call fails with. */
+enum { MGDT_DIRECT_STEM = 0, MGDT_DIRECT_GENERIC = 1, MGDT_DIRECT_REFUSED = 2 };
+int mgdt_conv2d_direct_route(const mgdt_view* x, int x_dtype, const mgdt_view* y, int dtype, int k, int stride, int groups, int* out);
 
 /* ---- MSPA attention: SPRModule pooling + MLP + softmax over the 4 groups + scale ------------------------
  * nn/modules/spr_module.py:8-31, nn/modules/block.py:268-287.

@@ -40,6 +40,7 @@ class ConvRoute(C.Structure):                 # == mgdt_conv_route
 
 ROUTE_X2, ROUTE_IN_SCALE, ROUTE_IN_SHIFT, ROUTE_R1, ROUTE_R2, ROUTE_FP8 = 1, 2, 4, 8, 16, 32
 ROUTE_IGEMM, ROUTE_LDS3X3 = 0, 1
+DIRECT_STEM, DIRECT_GENERIC, DIRECT_REFUSED = 0, 1, 2
 
 PROTOTYPES = {
     'mgdt_last_error': (C.c_char_p, []),
@@ -58,6 +59,7 @@ PROTOTYPES = {
     'mgdt_conv_pack_dgrad': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'mgdt_conv_pack_direct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp]),
     'mgdt_conv2d_direct_fwd': (_i, [VP, _i, _vp, _vp, _i, _i, _i, _i, VP, _i, _vp]),
+    'mgdt_conv2d_direct_route': (_i, [VP, _i, VP, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     'mgdt_spr_pool_fwd': (_i, [VP, _vp, _i, _vp]),
     'mgdt_spr_attn_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mgdt_scale_channels_fwd': (_i, [VP, _vp, VP, _i, _vp]),
@@ -88,6 +90,7 @@ PROTOTYPES = {
     'mgdt_stem2_pack': (_i, [_vp, _vp, _vp]),
     'mgdt_stem2_fwd': (_i, [VP, _i, _vp, _vp, _vp, _vp, VP, _vp]),
     'mgdt_stem2_geometry': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    'mgdt_stem2_route': (_i, [VP, _i, VP, _i, C.POINTER(C.c_int)]),
     'mgdt_detect_tail_supported': (_i, [_i, _i, _i, _i, _i]),
     'mgdt_detect_tail_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _i, _f, _i, _i, VP, _vp, _vp, _vp, _vp, _vp]),
     'mgdt_detect_tail_aug_fwd': (_i, [VP, VP, _vp, _vp, _vp, _vp, _i, _f, _i, _i, VP, _vp, _vp, _vp, _vp, _f, _i, _f, _vp]),

@@ -168,19 +168,54 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const TX* __restrict__ x
   }
 }
 
-extern "C" int mgdt_conv2d_direct_fwd(const mgdt_view* x, int x_dtype, const float* w, const float* bias, int k, int stride,
-                                      int groups, int act, const mgdt_view* y, int dtype, mgdt_stream s) {
-  if (!view_ok(x) || !view_ok(y) || !w || !bias) MGDT_FAIL(MGDT_BAD_ARG, "conv2d_direct: null/empty argument");
+// What the host decides about one launch of mgdt_conv2d_direct_fwd (reported by mgdt_conv2d_direct_route): the kernel family and its grid.
+struct DirectPlan { int family, gx, gy, Ho, Wo; };
+
+// The one place the decision is taken; the launch executes the plan, the route query reports it.  Looks at sizes, strides, dtypes and the ALIGNMENT of
+// y->p only (nothing is dereferenced).  Returns MGDT_OK or the status the launch fails with.
+static int conv_direct_plan(const mgdt_view* x, int x_dtype, const mgdt_view* y, int dtype, int k, int stride, int groups, DirectPlan* p) {
+  p->family = MGDT_DIRECT_REFUSED; p->gx = p->gy = p->Ho = p->Wo = 0;
   if (k < 1 || k > 7 || !(k & 1) || stride < 1 || groups < 1 || x->c % groups || y->c % groups)
     MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d_direct: k=%d stride=%d groups=%d cin=%d cout=%d", k, stride, groups, x->c, y->c);
   const int pad = k / 2;
   const int Ho = (x->h + 2 * pad - k) / stride + 1, Wo = (x->w + 2 * pad - k) / stride + 1;
   if (y->n != x->n || y->h != Ho || y->w != Wo) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d_direct: y is %dx%dx%d, expected %dx%dx%d", y->n, y->h, y->w, x->n, Ho, Wo);
-  long M = (long)x->n * Ho * Wo;
-  hipStream_t st0 = (hipStream_t)s;
-  if (k == 3 && groups == 1 && x->c <= 4 && y->c % 16 == 0 && y->sc == 1 && y->sw % 4 == 0 && y->sh % 4 == 0 && y->sn % 4 == 0 &&
+  if (dtype != MGDT_F32 && dtype != MGDT_BF16) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d_direct: output dtype %d", dtype);
+  const long M = (long)x->n * Ho * Wo;
+  p->Ho = Ho; p->Wo = Wo;
+  // The stem kernel stores 16 bytes at a time: four fp32, or EIGHT bf16 - so a bf16 view needs pixel, row and image strides that are multiples of 8
+  // elements (a 16-channel slice of a 28-channel buffer has 16-byte aligned even pixels and 8-byte aligned odd ones: it takes the generic kernel).
+  const int va = dtype == MGDT_BF16 ? 8 : 4;
+  if (k == 3 && groups == 1 && x->c <= 4 && y->c % 16 == 0 && y->sc == 1 && y->sw % va == 0 && y->sh % va == 0 && y->sn % va == 0 &&
       (uintptr_t)y->p % 16 == 0 && (x_dtype == MGDT_F32 || x_dtype == MGDT_U8 || (x_dtype == MGDT_BF16 && dtype == MGDT_BF16))) {   // stem fast path
-    dim3 sg(cdiv(M, 256), y->c / 16);
+    p->family = MGDT_DIRECT_STEM; p->gx = cdiv(M, 256); p->gy = y->c / 16;
+    return MGDT_OK;
+  }
+  if (x_dtype == MGDT_U8) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d_direct: uint8 input is taken by the stem path only (k=3, cin<=4, cout%%16==0)");
+  if (x_dtype != MGDT_F32 && x_dtype != MGDT_BF16) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d_direct: dtypes %d -> %d", x_dtype, dtype);
+  p->family = MGDT_DIRECT_GENERIC; p->gx = cdiv(M, 256); p->gy = cdiv(y->c, 16);
+  return MGDT_OK;
+}
+
+static inline bool shape_ok(const mgdt_view* v) { return v && v->n > 0 && v->h > 0 && v->w > 0 && v->c > 0; }
+
+extern "C" int mgdt_conv2d_direct_route(const mgdt_view* x, int x_dtype, const mgdt_view* y, int dtype, int k, int stride, int groups, int* out) {
+  if (!shape_ok(x) || !shape_ok(y) || !out) MGDT_FAIL(MGDT_BAD_ARG, "conv2d_direct_route: null/empty argument");
+  DirectPlan p;
+  const int st = conv_direct_plan(x, x_dtype, y, dtype, k, stride, groups, &p);
+  out[0] = p.family; out[1] = p.gx; out[2] = p.gy; out[3] = st;
+  return MGDT_OK;
+}
+
+extern "C" int mgdt_conv2d_direct_fwd(const mgdt_view* x, int x_dtype, const float* w, const float* bias, int k, int stride,
+                                      int groups, int act, const mgdt_view* y, int dtype, mgdt_stream s) {
+  if (!view_ok(x) || !view_ok(y) || !w || !bias) MGDT_FAIL(MGDT_BAD_ARG, "conv2d_direct: null/empty argument");
+  DirectPlan p;
+  if (int e = conv_direct_plan(x, x_dtype, y, dtype, k, stride, groups, &p)) return e;
+  const int Ho = p.Ho, Wo = p.Wo;
+  hipStream_t st0 = (hipStream_t)s;
+  if (p.family == MGDT_DIRECT_STEM) {
+    dim3 sg(p.gx, p.gy);
 #define STEM(TX, TY) conv_stem_kernel<TX, TY><<<sg, 256, 0, st0>>>((const TX*)x->p, x->sn, x->sh, x->sw, x->sc, w, bias, (TY*)y->p, y->sn, y->sh, y->sw, x->n, \
                                                               x->h, x->w, x->c, Ho, Wo, y->c, stride, act)
     if (x_dtype == MGDT_U8) { if (dtype == MGDT_BF16) STEM(uint8_t, bf16); else STEM(uint8_t, float); }
@@ -191,9 +226,8 @@ extern "C" int mgdt_conv2d_direct_fwd(const mgdt_view* x, int x_dtype, const flo
     MGDT_CHECK_LAUNCH("conv2d_direct_fwd(stem)");
     return MGDT_OK;
   }
-  if (x_dtype == MGDT_U8) MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d_direct: uint8 input is taken by the stem path only (k=3, cin<=4, cout%%16==0)");
   constexpr int COB = 16;
-  dim3 grid(cdiv(M, 256), cdiv(y->c, COB));
+  dim3 grid(p.gx, p.gy);
   hipStream_t st = (hipStream_t)s;
 #define LAUNCH(TX, TY)                                                                                              \
   conv_direct_kernel<TX, TY, COB><<<grid, 256, 0, st>>>((const TX*)x->p, x->sn, x->sh, x->sw, x->sc, w, bias, (TY*)y->p, \
@@ -202,8 +236,7 @@ extern "C" int mgdt_conv2d_direct_fwd(const mgdt_view* x, int x_dtype, const flo
   if (x_dtype == MGDT_F32 && dtype == MGDT_F32) LAUNCH(float, float);
   else if (x_dtype == MGDT_F32 && dtype == MGDT_BF16) LAUNCH(float, bf16);
   else if (x_dtype == MGDT_BF16 && dtype == MGDT_BF16) LAUNCH(bf16, bf16);
-  else if (x_dtype == MGDT_BF16 && dtype == MGDT_F32) LAUNCH(bf16, float);
-  else MGDT_FAIL(MGDT_BAD_DTYPE, "conv2d_direct: dtypes %d -> %d", x_dtype, dtype);
+  else LAUNCH(bf16, float);
 #undef LAUNCH
   MGDT_CHECK_LAUNCH("conv2d_direct_fwd");
   return MGDT_OK;

@@ -338,32 +338,58 @@ extern "C" int mgdt_stem2_geometry(int n, int h, int w, int cu_count, int* out) 
   return MGDT_OK;
 }
 
-/* y = SiLU(conv1(SiLU(conv0(x)))): x = N x 3 x H x W image (NCHW, any strides; x_dtype MGDT_BF16 / MGDT_F32 / MGDT_U8 (u8: / 255 on the fly)),
- * conv0 = 3x3 s2 3 -> 16 (packed0 from mgdt_stem2_pack + bias0[16]), conv1 = 3x3 s2 16 -> 32 (packed1 = mgdt_conv_pack(16, 32, 3, bf16) +
- * bias1[32]); y = N x H1 x W1 x 32 bf16 NHWC view. */
-extern "C" int mgdt_stem2_fwd(const mgdt_view* x, int x_dtype, const void* packed0, const float* bias0, const void* packed1, const float* bias1,
-                              const mgdt_view* y, mgdt_stream s) {
-  if (!view_ok(x) || !view_ok(y) || !packed0 || !bias0 || !packed1 || !bias1) MGDT_FAIL(MGDT_BAD_ARG, "stem2: null/empty argument");
+// Everything mgdt_stem2_fwd decides from the two views (reported by mgdt_stem2_route): the checks the launch makes before it launches, the tile
+// decomposition and the loader.  Pointers are tested for alignment only.
+static int stem2_plan(const mgdt_view* x, int x_dtype, const mgdt_view* y, StemArgs& a) {
+  memset(&a, 0, sizeof(a));
   if (x->c != 3 || y->c != 32 || y->sc != 1 || y->sw % 4 || y->sh % 4 || y->sn % 4 || (uintptr_t)y->p % 8) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: x must have 3 channels, y 32 (NHWC, 8-byte aligned)");
   const int H0 = (x->h - 1) / 2 + 1, W0 = (x->w - 1) / 2 + 1, H1 = (H0 - 1) / 2 + 1, W1 = (W0 - 1) / 2 + 1;
   if (y->n != x->n || y->h != H1 || y->w != W1) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: y is %dx%dx%d, expected %dx%dx%d", y->n, y->h, y->w, x->n, H1, W1);
   const long yext = ((long)(y->n - 1) * y->sn + (long)(y->h - 1) * y->sh + (long)(y->w - 1) * y->sw + y->c) * 2;
   if (yext >= 0x7fffffffL) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: y spans >= 2 GiB");
-  StemArgs a;
-  memset(&a, 0, sizeof(a));
   a.x = x->p; a.xsn = x->sn; a.xsc = x->sc; a.xsh = x->sh; a.xsw = x->sw;
-  a.w0 = (const char*)packed0; a.b0 = bias0; a.w1 = (const char*)packed1; a.b1 = bias1;
   a.y = (char*)y->p; a.ysn = (int)(y->sn * 2); a.ysh = (int)(y->sh * 2); a.ysw = (int)(y->sw * 2); a.y_bytes = (uint32_t)yext;
   a.N = x->n; a.H = x->h; a.W = x->w; a.H0 = H0; a.W0 = W0; a.H1 = H1; a.W1 = W1;
   a.tiles_x = cdiv(W1, ST_TW); a.tiles_y = cdiv(H1, ST_TH);
   a.total = a.N * a.tiles_x * a.tiles_y;
   a.fast = x_dtype == MGDT_BF16 && x->sw == 1 && x->w % 8 == 0 && x->sh % 8 == 0 && x->sc % 8 == 0 && x->sn % 8 == 0 && (uintptr_t)x->p % 16 == 0;
   if (x_dtype != MGDT_BF16 && x_dtype != MGDT_F32 && x_dtype != MGDT_U8) MGDT_FAIL(MGDT_BAD_DTYPE, "stem2: image dtype %d", x_dtype);
-  const int cus = stem2_cu_count();
-  if (cus <= 0) MGDT_FAIL(MGDT_LAUNCH_FAIL, "stem2: cannot read the device's compute-unit count");
+  return MGDT_OK;
+}
+
+// the persistent grid and the XCD ranges of a plan on a device with `cus` compute units
+static int stem2_plan_grid(StemArgs& a, int cus) {
   const char* e = getenv("MGDT_STEM_WGS");           // experiment knob: cap on the grid (not part of the ABI)
   const int grid = stem2_grid(a.total, cus, e ? atoi(e) : 0);
   a.per_xcd = cdiv(a.total, std::min(grid, 8));
+  return grid;
+}
+
+extern "C" int mgdt_stem2_route(const mgdt_view* x, int x_dtype, const mgdt_view* y, int cu_count, int* out) {
+  if (!x || !y || !out || x->n <= 0 || x->h <= 0 || x->w <= 0 || x->c <= 0 || y->n <= 0 || y->h <= 0 || y->w <= 0 || y->c <= 0)
+    MGDT_FAIL(MGDT_BAD_ARG, "stem2_route: null/empty argument");
+  for (int i = 0; i < 7; ++i) out[i] = 0;
+  StemArgs a;
+  if ((out[6] = stem2_plan(x, x_dtype, y, a)) != MGDT_OK) return MGDT_OK;
+  if (cu_count <= 0) cu_count = stem2_cu_count();
+  if (cu_count <= 0) MGDT_FAIL(MGDT_LAUNCH_FAIL, "stem2_route: cannot read the device's compute-unit count");
+  const int grid = stem2_plan_grid(a, cu_count);
+  out[0] = a.fast; out[1] = a.tiles_x; out[2] = a.tiles_y; out[3] = a.total; out[4] = grid; out[5] = a.per_xcd;
+  return MGDT_OK;
+}
+
+/* y = SiLU(conv1(SiLU(conv0(x)))): x = N x 3 x H x W image (NCHW, any strides; x_dtype MGDT_BF16 / MGDT_F32 / MGDT_U8 (u8: / 255 on the fly)),
+ * conv0 = 3x3 s2 3 -> 16 (packed0 from mgdt_stem2_pack + bias0[16]), conv1 = 3x3 s2 16 -> 32 (packed1 = mgdt_conv_pack(16, 32, 3, bf16) +
+ * bias1[32]); y = N x H1 x W1 x 32 bf16 NHWC view. */
+extern "C" int mgdt_stem2_fwd(const mgdt_view* x, int x_dtype, const void* packed0, const float* bias0, const void* packed1, const float* bias1,
+                              const mgdt_view* y, mgdt_stream s) {
+  if (!view_ok(x) || !view_ok(y) || !packed0 || !bias0 || !packed1 || !bias1) MGDT_FAIL(MGDT_BAD_ARG, "stem2: null/empty argument");
+  StemArgs a;
+  if (int e = stem2_plan(x, x_dtype, y, a)) return e;
+  a.w0 = (const char*)packed0; a.b0 = bias0; a.w1 = (const char*)packed1; a.b1 = bias1;
+  const int cus = stem2_cu_count();
+  if (cus <= 0) MGDT_FAIL(MGDT_LAUNCH_FAIL, "stem2: cannot read the device's compute-unit count");
+  const int grid = stem2_plan_grid(a, cus);
   hipStream_t st = (hipStream_t)s;
   static unsigned long long* dbgbuf = nullptr;            // MGDT_STEM_DBG=1: per-workgroup phase sums, printed after the launch (debug only)
   static size_t dbgcap = 0;

@@ -326,6 +326,29 @@ def conv2d_route(x, y, k, stride, dtype=None, act=ACT_SILU, x2=False, in_scale=F
     return out
 
 
+def _route_view(t):
+    """mgdt_view of a tensor for a host-side route query: sizes, strides and a pointer that is never dereferenced, only tested for alignment.  A meta tensor
+    has no address: its byte offset inside its storage stands in (device allocations start on 256-byte boundaries)."""
+    b, c, h, w = t.shape
+    sn, sc, sh, sw = t.stride()
+    p = 4096 + t.storage_offset() * t.element_size() if t.device.type == 'meta' else t.data_ptr()
+    return View(p, b, h, w, c, sn, sh, sw, sc)
+
+
+def _image_code(dt):
+    return dt if isinstance(dt, int) else (U8 if dt == torch.uint8 else dtype_code(dt))
+
+
+def conv2d_direct_route(x, y, k, stride, groups=1, x_dtype=None, dtype=None):
+    """mgdt_conv2d_direct_route: what mgdt_conv2d_direct_fwd would launch for the views x -> y, as a dict: family 'stem' / 'generic' with its grid
+    (gx, gy), or 'refused' with the status the launch would fail with.  Launches nothing and needs no device: x and y may be CPU or meta tensors; only
+    sizes, strides, dtypes and the alignment of y's address count.  x_dtype / dtype override the tensors' dtypes (torch dtypes or C-ABI codes)."""
+    out = (C.c_int * 4)()
+    L.check(L.lib().mgdt_conv2d_direct_route(C.byref(_route_view(x)), _image_code(x.dtype if x_dtype is None else x_dtype), C.byref(_route_view(y)),
+                                             _image_code(y.dtype if dtype is None else dtype), int(k), int(stride), int(groups), out), 'conv2d_direct_route')
+    return dict(family=('stem', 'generic', 'refused')[out[0]], gx=out[1], gy=out[2], status=out[3])
+
+
 # ------------------------------------------------------------------ MSPA attention
 def spr_attention(x, fc1_w, fc1_b, fc2_w, fc2_b, groups, softmax=True):
     """softmax_over_groups(SPR(x_group)) -> attn fp32 [B, C] (softmax=False: the bare sigmoid weights)."""
@@ -391,6 +414,18 @@ def stem2(x, pk0, pk1):
     _launch('stem2_fwd', 'mgdt_stem2_fwd', vp(x), U8 if x.dtype == torch.uint8 else dtype_code(x.dtype), ptr(pk0.blob), ptr(pk0.bias), ptr(pk1.w), ptr(pk1.bias),
             vp(y), stream())
     return y
+
+
+def stem2_route(x, y, cu_count=0, x_dtype=None):
+    """mgdt_stem2_route: what mgdt_stem2_fwd would launch for the image view x and the output view y on a device with cu_count compute units (<= 0: the
+    current device's), as a dict: loader 'fast' (16-byte row loads, next patch prefetched) / 'generic', tiles_x, tiles_y, tiles, grid, per_xcd; or
+    loader 'refused' with the status of the launch.  Launches nothing; with cu_count > 0 it needs no device (CPU or meta tensors)."""
+    out = (C.c_int * 7)()
+    L.check(L.lib().mgdt_stem2_route(C.byref(_route_view(x)), _image_code(x.dtype if x_dtype is None else x_dtype), C.byref(_route_view(y)), int(cu_count), out),
+            'stem2_route')
+    if out[6]:
+        return dict(loader='refused', status=out[6])
+    return dict(loader='fast' if out[0] else 'generic', tiles_x=out[1], tiles_y=out[2], tiles=out[3], grid=out[4], per_xcd=out[5])
 
 
 # ------------------------------------------------------------------ whole CSP block (MSPA_C2f / C2f) in one launch

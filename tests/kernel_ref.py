@@ -1,5 +1,5 @@
 """Shared helpers of the per-route kernel tests (test_reverse_kernels.py, test_forward_kernels.py, test_tood_kernels.py, test_block_kernels.py,
-test_conv_kernels.py, test_cnx_kernels.py): seeded inputs already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds,
+test_conv_kernels.py, test_cnx_kernels.py, test_stem_direct_kernels.py): seeded inputs already representable in a kernel's dtype, NHWC device buffers and channel-slice views, the stated comparison bounds,
 the float64 deformable-conv reference pieces, the restatements of the fused forward block kernels, of the fused convolution and of the ConvNeXtV2
 kernels with their flip allowance.  A plain module, not a
 conftest."""
@@ -734,3 +734,46 @@ def _close_allow(got, ref, allow, what=''):
           f'({100.0 * quiet.float().mean().item():.1f} % of the elements)')
     assert use <= 1.0, (what, 'worst share of bound + allowance', use, 'elements over', int((err > bound + allow).sum()))
     return use, plain
+
+
+# ------------------------------------------------------------------------------------------------ stem and direct convolution (test_stem_direct_kernels.py)
+def u8_unit(v):
+    """A uint8 image as the kernels read it: fp32(v) / fp32(255), one correctly rounded fp32 division (the `lut` entry); fp64 values."""
+    return (v.to(F32) / torch.tensor(255.0, dtype=F32)).double()
+
+
+def ref_stem2(img, cp0, cp1, dt=torch.float64, stages=False):
+    """mgdt_stem2_fwd.  img: the image values as stored (fp64; a uint8 image as u8_unit gives it).  Rounding points read off stem2_kernel: the patch is
+    staged in LDS as bf16 (X = bf16(value): the 16-byte loader copies bf16, the element-wise one rounds fp32 and lut values when it writes them);
+    layer 0 = ConvP(16, 3, 3, BN, no conv bias) folded as PackedStem2 + stem2_pack_kernel do (bf16(w * s), s = gamma / sqrtf(eps + var) in fp32, fp32
+    bias: exactly _fold), y0 = bf16(silu(conv stride 2)) stored to LDS, zero outside the H0 x W0 map (layer 1's padding); layer 1 = the mgdt_conv_pack
+    bf16 panel, y = silu(conv stride 2 + bias).  Returns y BEFORE its final rounding; with stages=True also {y0_pre, y0}
+    (the values before and after the mid-kernel rounding)."""
+    x = _rb(img.to(dt))
+    y0_pre = _silu(cp0(x, dt, 2))
+    y0 = _rb(y0_pre)
+    y = _silu(cp1(y0, dt, 2))
+    return (y, dict(y0_pre=y0_pre, y0=y0)) if stages else y
+
+
+def ref_direct(x, cp, stride, act, groups=1, dt=torch.float64):
+    """mgdt_conv2d_direct_fwd: act(conv(x, w * s, groups) + bias), zero padding k // 2.  cp = ConvP(cout, cin / groups, k, dt=F32): the direct packer keeps
+    the fp32 product w * s and the fp32 bias (_fold(..., dt=F32)); the input is read as stored (a uint8 image as u8_unit gives it, NOT rounded to bf16),
+    products and sums are fp32 FMAs, one rounding at the store.  Returns y BEFORE that rounding."""
+    import torch.nn.functional as F
+    return _ACTS[act](F.conv2d(x.to(dt), cp.wq.to(dt), cp.bq.to(dt), stride, cp.k // 2, 1, groups))
+
+
+def ref_pack_direct(cp):
+    """mgdt_conv_pack_direct in float64 from the unfolded parameters: panel[(tap * cin_g + ci) * cout + co] = w[co][ci][ky][kx] * gamma / sqrt(eps + var),
+    bias = beta - gamma * mean / sqrt(var + eps) (+ s * conv_bias); without BN the weights and the conv bias (or 0).  eps as the fp32 the C ABI receives."""
+    w = cp.w.double()
+    cb = None if cp.cb is None else cp.cb.double()
+    if cp.bn is None:
+        bias = torch.zeros(cp.cout, dtype=torch.float64) if cb is None else cb
+    else:
+        g, b, mu, var, eps = (t.double() if torch.is_tensor(t) else f32r(t) for t in cp.bn)
+        s = g / torch.sqrt(eps + var)
+        w = w * s.view(-1, 1, 1, 1)
+        bias = b - g * mu / torch.sqrt(var + eps) + (0 if cb is None else s * cb)
+    return w.permute(2, 3, 1, 0).reshape(-1), bias
