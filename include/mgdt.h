@@ -653,6 +653,34 @@ int mgdt_cls_loss_fwd(const float* logits, const int64_t* labels, int n, int nc,
 int mgdt_cls_loss_bwd(const float* logits, const int64_t* labels, int n, int nc, float gscale, float* dlogits, mgdt_stream s);
 int mgdt_cls_topk_fwd(const float* probs, int n, int nc, int64_t* topk, const int64_t* targets, int32_t* matrix, mgdt_stream s);
 
+/* ---- ByteTrack (reference tracker/trackers/byte_tracker.py:181-295, tracker/utils/kalman_filter.py KalmanFilterXYAH, tracker/utils/matching.py) ----
+ * One frame of `streams` independent video streams in one launch, one workgroup per stream, no host read (capturable in a hipGraph).
+ * rows [streams][max_det][6] fp32 (x1,y1,x2,y2,conf,cls) + counts[streams] as mgdt_nms_fwd writes them; active: NULL or uint8[streams], 0 = this
+ * stream skips the frame (its state bytes, frame_id included, do not move; 0 rows).  state: mgdt_bytetrack_state_bytes(streams, cap) bytes, zeroed
+ * by mgdt_bytetrack_reset (stream = -1: all).  cap <= 128 slots per stream for tracked + lost + unconfirmed tracks; at most 128 detections per
+ * stream and frame above track_low_thresh.  track_buffer enters as max_time_lost = int(frame_rate / 30 * track_buffer).
+ * tracks [streams][cap][8] fp32 (x1,y1,x2,y2,track_id,score,cls,idx), the activated Tracked tracks in ascending track_id, the box from the filter
+ * mean after this frame's update, rows past ntracks[i] zero; flags[i] = 0, or 1 (too many detections) / 2 (no free slot for a new track): the
+ * stream's state is then unchanged and ntracks[i] = 0.  Ids count from 1 per stream (the reference's counter is one class attribute shared by every
+ * tracker of the process and reset by every constructor; per stream the ids equal those of a reference tracker run alone).
+ * The filter state is fp64 in the decoupled form (four 2x2 blocks; every other covariance entry of the reference is exactly 0); costs are fp32 in
+ * the reference's operation order; the three assignments of a frame are solved exactly (mgdt_track_assign's solver).
+ * mgdt_track_assign: the solver alone. cost [batch][n_max][m_max] fp32, n[batch], m[batch] (n_max, m_max <= 128): the partial matching that
+ *   minimises sum(c_ij - thresh) (lap.lapjv(cost, extend_cost=True, cost_limit=thresh)); pairs with c_ij >= thresh are never matched.
+ *   x [batch][n_max] int32: the column of row i, -1 = unmatched (and for i >= n).
+ * mgdt_bytetrack_export: the live tracks of one stream in ascending id: hdr[3] = {live tracks, frame_id, id counter}; ints [6][cap] = id, state
+ *   (1 Tracked, 2 Lost, 3 Removed: see track.hip), is_activated, frame_id, start_frame, tracklet_len; score_cls [2][cap] fp32; mean [cap][8] fp64;
+ *   cov [cap][8][8] fp64 (the blocks expanded, zeros elsewhere).  Only the first hdr[0] entries of each array are written. */
+size_t mgdt_bytetrack_state_bytes(int streams, int cap);
+int mgdt_bytetrack_reset(void* state, int streams, int cap, int stream, mgdt_stream s);
+int mgdt_bytetrack_update(const float* rows, const int32_t* counts, const uint8_t* active, int streams, int max_det, void* state, int cap,
+                          float track_high_thresh, float track_low_thresh, float new_track_thresh, float match_thresh, int max_time_lost,
+                          float* tracks, int32_t* ntracks, int32_t* flags, mgdt_stream s);
+int mgdt_track_assign(const float* cost, const int32_t* n, const int32_t* m, int batch, int n_max, int m_max, float thresh, int32_t* x,
+                      mgdt_stream s);
+int mgdt_bytetrack_export(const void* state, int streams, int cap, int stream, int32_t* hdr, int32_t* ints, float* score_cls, double* mean,
+                          double* cov, mgdt_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,11 @@ PROTOTYPES = {
     'mgdt_cls_loss_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'mgdt_cls_loss_bwd': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
     'mgdt_cls_topk_fwd': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'mgdt_bytetrack_state_bytes': (_sz, [_i, _i]),
+    'mgdt_bytetrack_reset': (_i, [_vp, _i, _i, _i, _vp]),
+    'mgdt_bytetrack_update': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    'mgdt_track_assign': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    'mgdt_bytetrack_export': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

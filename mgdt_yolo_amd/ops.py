@@ -1904,3 +1904,87 @@ def cls_topk(probs, targets=None, matrix=None):
         targets = _cls_labels(targets, n, nc, probs.device)
     _launch('cls_topk_fwd', 'mgdt_cls_topk_fwd', ptr(probs), n, nc, ptr(out), ptr(targets) if matrix is not None else None, ptr(matrix), stream())
     return out
+
+
+# ---- ByteTrack (mgdt_bytetrack_*, mgdt_track_assign: csrc/track.hip) ----
+TRACK_CAP = 128                    # == TK_CAP: most slots per stream, most detections above track_low_thresh per frame, most rows / columns of an assignment
+TRACK_FLAG_DETS, TRACK_FLAG_TRACKS = 1, 2
+
+
+def _track_cap(cap):
+    if not 1 <= int(cap) <= TRACK_CAP:
+        raise RuntimeError(f'bytetrack: track capacity {cap} is outside 1..{TRACK_CAP}')
+    return int(cap)
+
+
+def bytetrack_state(streams, cap, device):
+    """A zeroed state buffer for `streams` streams of `cap` slots (uint8, mgdt_bytetrack_state_bytes)."""
+    cap = _track_cap(cap)
+    if torch.device(device).type != 'cuda':
+        raise RuntimeError('mgdt_yolo_amd runs on MI355X (HIP) only: the tracker state lives on the device and there is no CPU/PyTorch fallback')
+    return torch.zeros(L.lib().mgdt_bytetrack_state_bytes(int(streams), cap), dtype=torch.uint8, device=device)
+
+
+def bytetrack_reset(state, streams, cap, which=-1):
+    """Zero the state of stream `which` (-1: of every stream) on the current stream."""
+    _need_gpu(state)
+    _launch('bytetrack_reset', 'mgdt_bytetrack_reset', ptr(state), int(streams), _track_cap(cap), int(which), stream())
+
+
+def bytetrack_update(rows, counts, state, cap, high, low, new, match, max_time_lost, active=None, out=None):
+    """One frame of B streams (mgdt_bytetrack_update): rows (B, max_det, 6) fp32 + counts (B,) int32 as `nms` returns them, active (B,) uint8 / bool
+    or None -> (tracks (B, cap, 8) fp32 [x1,y1,x2,y2,track_id,score,cls,idx] in ascending id, ntracks (B,) int32, flags (B,) int32).  No host read."""
+    for t in (rows, counts, state):
+        _need_gpu(t)
+    cap = _track_cap(cap)
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != 6 or not rows.is_contiguous():
+        raise RuntimeError(f'bytetrack_update: rows must be a contiguous float32 (B, max_det, 6) tensor, got {tuple(rows.shape)} {rows.dtype}')
+    b, md, _ = rows.shape
+    counts = _i32(counts, b, 'bytetrack_update: counts')
+    if state.dtype != torch.uint8 or state.numel() != L.lib().mgdt_bytetrack_state_bytes(b, cap) or not state.is_contiguous():
+        raise RuntimeError(f'bytetrack_update: the state buffer does not belong to {b} streams of {cap} slots')
+    if active is not None:
+        _need_gpu(active)
+        if active.dtype == torch.bool:
+            active = active.view(torch.uint8)
+        if active.dtype != torch.uint8 or active.shape != (b,) or not active.is_contiguous():
+            raise RuntimeError('bytetrack_update: active must be a contiguous (B,) bool / uint8 tensor')
+    if out is None:
+        out = (torch.empty(b, cap, 8, dtype=torch.float32, device=rows.device), torch.empty(b, dtype=torch.int32, device=rows.device),
+               torch.empty(b, dtype=torch.int32, device=rows.device))
+    tracks, ntracks, flags = out
+    _launch('bytetrack_update', 'mgdt_bytetrack_update', ptr(rows), ptr(counts), ptr(active), b, md, ptr(state), cap, float(high), float(low), float(new),
+            float(match), int(max_time_lost), ptr(tracks), ptr(ntracks), ptr(flags), stream())
+    return tracks, ntracks, flags
+
+
+def track_assign(cost, n, m, thresh):
+    """The tracker's assignment solver alone (mgdt_track_assign): cost (B, n_max, m_max) fp32, n / m (B,) int32 -> x (B, n_max) int32, -1 = unmatched."""
+    _need_gpu(cost)
+    if cost.dtype != torch.float32 or cost.dim() != 3 or not cost.is_contiguous():
+        raise RuntimeError('track_assign: cost must be a contiguous float32 (B, n_max, m_max) tensor')
+    b, nm, mm = cost.shape
+    if not (1 <= nm <= TRACK_CAP and 1 <= mm <= TRACK_CAP):
+        raise RuntimeError(f'track_assign: {nm} x {mm} is outside 1..{TRACK_CAP}')
+    n, m = _i32(n, b, 'track_assign: n'), _i32(m, b, 'track_assign: m')
+    x = torch.empty(b, nm, dtype=torch.int32, device=cost.device)
+    _launch('track_assign', 'mgdt_track_assign', ptr(cost), ptr(n), ptr(m), b, nm, mm, float(thresh), ptr(x), stream())
+    return x
+
+
+def bytetrack_export(state, streams, cap, which):
+    """The live tracks of one stream in ascending id as host arrays (mgdt_bytetrack_export + one host read)."""
+    _need_gpu(state)
+    cap = _track_cap(cap)
+    dev = state.device
+    hdr = torch.zeros(3, dtype=torch.int32, device=dev)
+    ints = torch.zeros(6, cap, dtype=torch.int32, device=dev)
+    sc = torch.zeros(2, cap, dtype=torch.float32, device=dev)
+    mean = torch.zeros(cap, 8, dtype=torch.float64, device=dev)
+    cov = torch.zeros(cap, 8, 8, dtype=torch.float64, device=dev)
+    _launch('bytetrack_export', 'mgdt_bytetrack_export', ptr(state), int(streams), cap, int(which), ptr(hdr), ptr(ints), ptr(sc), ptr(mean), ptr(cov), stream())
+    n, frame_id, count = hdr.tolist()
+    ints, sc = ints[:, :n].cpu().numpy(), sc[:, :n].cpu().numpy()
+    d = {k: ints[i] for i, k in enumerate(('id', 'state', 'is_activated', 'frame_id', 'start_frame', 'tracklet_len'))}
+    d.update(score=sc[0], cls=sc[1], mean=mean[:n].cpu().numpy(), covariance=cov[:n].cpu().numpy(), tracker_frame_id=frame_id, count=count)
+    return d
