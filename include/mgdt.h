@@ -681,6 +681,41 @@ int mgdt_track_assign(const float* cost, const int32_t* n, const int32_t* m, int
 int mgdt_bytetrack_export(const void* state, int streams, int cap, int stream, int32_t* hdr, int32_t* ints, float* score_cls, double* mean,
                           double* cov, mgdt_stream s);
 
+/* ---- RT-DETR decoder head (reference nn/modules/head.py:275-464 RTDETRDecoder, nn/modules/transformer.py:187-378, vit/rtdetr/predict.py) ----
+ * hd = 256 channels = 8 heads x 32, 4 sampling points, nl <= 4 levels; `shapes` = host int[2 * nl] (h, w) per level, tokens level after level,
+ * row-major.  Every tensor is fp32 except the value tensor of mgdt_msdeform_attn_fwd and x of mgdt_add_layernorm_fwd (dtype: fp32 or bf16).  None of the calls reads back to the host.
+ * mgdt_msdeform_attn_fwd: value[batch][L][ld_value >= 256] (image stride batch_stride_value elements), ref [batch][nq][4] (cx, cy, w, h in [0, 1]),
+ *   offsets [batch][nq][ld_offsets >= 8*nl*4*2] and weights [batch][nq][ld_weights >= 8*nl*4] raw logits in the reference's (head, level, point[, xy])
+ *   order.  loc = ref_xy + off / 4 * ref_wh * 0.5; bilinear at pixel loc * (W, H) - 0.5 with zero padding (grid_sample, align_corners=False);
+ *   softmax over a head's nl*4 weights; out [batch][nq][256] fp32 = the weighted sum, accumulated in fp32.
+ * mgdt_mha_fwd: softmax((q / sqrt(32)) k^T) v per head, no mask; q, k, v [batch][nq][ld >= 256], out [batch][nq][256]; any nq >= 1.
+ * mgdt_add_layernorm_fwd: out[rows][256] = LayerNorm(x [+ res]) * gamma + beta; x in `dtype` (fp32 or bf16), everything else fp32.  fill != NULL (the masked form, rows = batch * L): rows whose
+ *   anchor is invalid (head.py:382) read fill[256], rounded to `dtype`, in place of x.
+ * mgdt_rtdetr_rowmax_fwd: out[rows] = max over x[rows][0..nc).
+ * mgdt_rtdetr_topk_fwd: index[batch][k] int64 = the k best of scores[batch][L], descending, equal scores by ascending index (NaN = -inf); k <= L.
+ * mgdt_rtdetr_gather_fwd: embed[b][q] = feat[b][index[b][q]] (256 channels), enc_scores[b][q] = scores[b][index[b][q]] (nc); an index outside
+ *   [0, L) is clamped.
+ * mgdt_rtdetr_ref_init_fwd: ref[b][q] = sigmoid(delta[b][q] + anchor(index[b][q])); an invalid anchor is +inf (ref = 1).
+ * mgdt_rtdetr_refine_fwd: out = sigmoid(delta + inverse_sigmoid(ref)), eps 1e-5; out may be ref.
+ * mgdt_rtdetr_sigmoid_fwd: out[rows][nc] dense = sigmoid(x[rows][ld]).
+ * mgdt_rtdetr_post_fwd: boxes [batch][nq][4] xywh, scores [batch][nq][nc]; a query is kept when its best score > conf and (keep_class == NULL or
+ *   keep_class[argmax]); rows [batch][nq][6] = (x1, y1, x2, y2) * (w, h, w, h) of wh[batch][2] (NULL: 1), conf, cls in query order, the rest zero;
+ *   counts[batch] int32 - the layout mgdt_nms_fwd leaves. */
+int mgdt_msdeform_attn_fwd(const void* value, long ld_value, long batch_stride_value, const int* shapes, int nl, int batch, int nq, const float* ref,
+                           const float* offsets, long ld_offsets, const float* weights, long ld_weights, float* out, int dtype, mgdt_stream s);
+int mgdt_mha_fwd(const float* q, long ld_q, const float* k, long ld_k, const float* v, long ld_v, int batch, int nq, float* out, mgdt_stream s);
+int mgdt_add_layernorm_fwd(const void* x, int dtype, long ld_x, const float* res, long ld_res, const float* gamma, const float* beta, float eps, long rows,
+                           const float* fill, const int* shapes, int nl, float* out, mgdt_stream s);
+int mgdt_rtdetr_rowmax_fwd(const float* x, long rows, int nc, long ld, float* out, mgdt_stream s);
+int mgdt_rtdetr_topk_fwd(const float* scores, int batch, int L, int k, int64_t* index, mgdt_stream s);
+int mgdt_rtdetr_gather_fwd(const float* feat, const float* scores, long ld_scores, const int64_t* index, int batch, int L, int nq, int nc, float* embed,
+                           float* enc_scores, mgdt_stream s);
+int mgdt_rtdetr_ref_init_fwd(const float* delta, long ld_delta, const int64_t* index, int batch, int nq, const int* shapes, int nl, float* ref, mgdt_stream s);
+int mgdt_rtdetr_refine_fwd(const float* delta, long ld_delta, const float* ref, long rows, float* out, mgdt_stream s);
+int mgdt_rtdetr_sigmoid_fwd(const float* x, long rows, int nc, long ld, float* out, mgdt_stream s);
+int mgdt_rtdetr_post_fwd(const float* boxes, const float* scores, int batch, int nq, int nc, float conf, const uint8_t* keep_class, const float* wh, float* rows,
+                         int32_t* counts, mgdt_stream s);
+
 #ifdef __cplusplus
 }
 #endif

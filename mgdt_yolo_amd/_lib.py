@@ -20,7 +20,7 @@ class View(C.Structure):
 
 
 VP = C.POINTER(View)
-_vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_vp, _i, _f, _sz, _l = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_long
 
 # name -> (restype, argtypes); must list every symbol include/mgdt.h declares (tests check this)
 class PackDesc(C.Structure):                  # == mgdt_pack_desc
@@ -191,6 +191,16 @@ PROTOTYPES = {
     'mgdt_bytetrack_update': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
     'mgdt_track_assign': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     'mgdt_bytetrack_export': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'mgdt_msdeform_attn_fwd': (_i, [_vp, _l, _l, _vp, _i, _i, _i, _vp, _vp, _l, _vp, _l, _vp, _i, _vp]),
+    'mgdt_mha_fwd': (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _vp, _vp]),
+    'mgdt_add_layernorm_fwd': (_i, [_vp, _i, _l, _vp, _l, _vp, _vp, _f, _l, _vp, _vp, _i, _vp, _vp]),
+    'mgdt_rtdetr_rowmax_fwd': (_i, [_vp, _l, _i, _l, _vp, _vp]),
+    'mgdt_rtdetr_topk_fwd': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'mgdt_rtdetr_gather_fwd': (_i, [_vp, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'mgdt_rtdetr_ref_init_fwd': (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    'mgdt_rtdetr_refine_fwd': (_i, [_vp, _l, _vp, _l, _vp, _vp]),
+    'mgdt_rtdetr_sigmoid_fwd': (_i, [_vp, _l, _i, _l, _vp, _vp]),
+    'mgdt_rtdetr_post_fwd': (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -116,9 +116,24 @@ def _cls_cfg(nc):
 CLS_CONFIGS = {'yolov8-cls': lambda nc=1000: _cls_cfg(nc)}
 
 
+def _rtdetr(head):
+    """`head` with its Detect row replaced by RTDETRDecoder [nc] (models/v8/yolov8-rtdetr.yaml:46)."""
+    def build():
+        rows = head()
+        rows[-1] = [rows[-1][0], 1, 'RTDETRDecoder', ['nc']]
+        return rows
+    return build
+
+
+# RT-DETR graph: the reference's models/v8/yolov8-rtdetr.yaml (the yolov8 backbone and PAN neck, then RTDETRDecoder).  Kept apart from CONFIGS: its
+# output is not Detect's (B, 4 + nc, A) map.  The reference's rtdetr-l / rtdetr-x graphs (HGStem, HGBlock, AIFI, RepC3) are not built.
+RTDETR_CONFIGS = {'yolov8-rtdetr': lambda nc=80: _cfg('C2f', _rtdetr(_pan_head), nc)}
+
+
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
-    table = CONFIGS if name in CONFIGS else SEG_CONFIGS if name in SEG_CONFIGS else CLS_CONFIGS if name in CLS_CONFIGS else POSE_CONFIGS
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    table = (CONFIGS if name in CONFIGS else SEG_CONFIGS if name in SEG_CONFIGS else CLS_CONFIGS if name in CLS_CONFIGS else
+             RTDETR_CONFIGS if name in RTDETR_CONFIGS else POSE_CONFIGS)
     d = table[name]() if nc is None else table[name](nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale
     d['yaml_file'] = f'{name}.yaml'

@@ -14,7 +14,7 @@ from ... import ops
 from .block import DFL, Proto
 from .conv import Conv, HipModule
 
-__all__ = ('Detect', 'Segment', 'Pose', 'Classify', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
+__all__ = ('Detect', 'Segment', 'Pose', 'Classify', 'RTDETRDecoder', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
 
 
 class _HeadConv(HipModule):
@@ -765,3 +765,198 @@ class TOODHead(Detect):
         """reference head.py:562-568 (single shared head: the class prior uses stride 16)."""
         self.cv2.bias.data[:] = 1.0
         self.cv3.bias.data[:self.nc] = math.log(5 / self.nc / (640 / 16) ** 2)
+
+
+# ====================================================================================================================
+# RTDETRDecoder (reference nn/modules/head.py:275-464), inference only.
+RTDETR_TRAIN_MSG = ('RT-DETR training is not built: the RT-DETR loss with its Hungarian matcher and the denoising groups (vit/utils/loss.py, vit/utils/ops.py) '
+                    'have no HIP counterpart here; RTDETRDecoder runs in eval() only')
+
+
+class RTDETRDecoder(HipModule):
+    """RT-DETR decoder head.  Submodules and parameters carry the reference's names (`input_proj.{i}.{0,1}`, `decoder.layers.{i}.self_attn.in_proj_weight`,
+    `... .cross_attn.sampling_offsets`, `denoising_class_embed`, `query_pos_head`, `enc_output`, `enc_score_head`, `enc_bbox_head`, `dec_score_head.{i}`,
+    `dec_bbox_head.{i}`); nn.Linear / nn.LayerNorm / nn.MultiheadAttention objects hold parameters only.
+
+    Eval forward of a list of nl feature maps -> (dec_bboxes (1, B, nq, 4) xywh in [0, 1], dec_scores (1, B, nq, nc) after the sigmoid, enc_bboxes
+    (B, nq, 4), enc_scores (B, nq, nc), None), all fp32, no host read.  Launches: nl input projections into one (B, L, 256) token memory; enc_output
+    linear + masked LayerNorm; enc_score_head over all tokens, the per-token class maximum, the selection (`select_queries`: descending score, equal
+    scores by ascending token index); the gather of the nq selected tokens and enc_bbox_head on those rows only; ONE value projection for all `ndl`
+    decoder layers (an ndl*256-column panel over the memory); then per layer the query-position MLP, the q/k and v projections (the position added in the
+    GEMM's input stage), self-attention, out_proj, add + LayerNorm, ONE panel for sampling offsets + attention weights, deformable attention, output_proj,
+    add + LayerNorm, the FFN, add + LayerNorm, the box MLP and the box refinement; the last layer's score head and sigmoid.
+    bf16 compute: the token memory, the enc_output linear's output and the projected values are bf16 in HBM and computed on the bf16 MFMA (everything of
+    size L); the LayerNorm behind enc_output reads bf16 and writes fp32, and from there on (scores, selection, the whole query side) it is fp32.
+    Built for hd = 256, nh = 8, ndp = 4, up to 4 levels; any nq, nc, ndl."""
+
+    def __init__(self, nc=80, ch=(512, 1024, 2048), hd=256, nq=300, ndp=4, nh=8, ndl=6, d_ffn=1024, dropout=0., act=nn.ReLU(), eval_idx=-1,
+                 nd=100, label_noise_ratio=0.5, box_noise_scale=1.0, learnt_init_query=False):
+        super().__init__()
+        from .transformer import MLP, DeformableTransformerDecoder, DeformableTransformerDecoderLayer
+        if hd != 256 or nh != 8 or ndp != 4 or not 1 <= len(ch) <= 4:
+            raise NotImplementedError(f'RTDETRDecoder: the HIP kernels are built for hd = 256, nh = 8, ndp = 4 and 1..4 levels, got hd = {hd}, nh = {nh}, '
+                                      f'ndp = {ndp}, {len(ch)} levels')
+        if learnt_init_query:
+            raise NotImplementedError('RTDETRDecoder: learnt_init_query=True is not built (the queries are the selected encoder tokens)')
+        if d_ffn % 4 or nq < 1 or ndl < 1 or nc < 1:
+            raise ValueError(f'RTDETRDecoder: d_ffn = {d_ffn} (a multiple of 4), nq = {nq}, ndl = {ndl}, nc = {nc}')
+        self.hidden_dim, self.nhead, self.nl, self.nc, self.num_queries, self.num_decoder_layers = hd, nh, len(ch), nc, nq, ndl
+        self.input_proj = nn.ModuleList(nn.Sequential(nn.Conv2d(x, hd, 1, bias=False), nn.BatchNorm2d(hd)) for x in ch)
+        self.decoder = DeformableTransformerDecoder(hd, DeformableTransformerDecoderLayer(hd, nh, d_ffn, dropout, act, self.nl, ndp), ndl, eval_idx)
+        self.denoising_class_embed = nn.Embedding(nc, hd)
+        self.num_denoising, self.label_noise_ratio, self.box_noise_scale = nd, label_noise_ratio, box_noise_scale
+        self.learnt_init_query = learnt_init_query
+        self.query_pos_head = MLP(4, 2 * hd, hd, num_layers=2)
+        self.enc_output = nn.Sequential(nn.Linear(hd, hd), nn.LayerNorm(hd))
+        self.enc_score_head = nn.Linear(hd, nc)
+        self.enc_bbox_head = MLP(hd, hd, 4, num_layers=3)
+        self.dec_score_head = nn.ModuleList([nn.Linear(hd, nc) for _ in range(ndl)])
+        self.dec_bbox_head = nn.ModuleList([MLP(hd, hd, 4, num_layers=3) for _ in range(ndl)])
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        """head.py:443-464: the constants are deterministic, the uniform draws are not pinned to the reference's random stream"""
+        from torch.nn.init import constant_, uniform_, xavier_uniform_
+        bias_cls = float(-math.log((1 - 0.01) / 0.01)) / 80 * self.nc
+        constant_(self.enc_score_head.bias, bias_cls)
+        constant_(self.enc_bbox_head.layers[-1].weight, 0.)
+        constant_(self.enc_bbox_head.layers[-1].bias, 0.)
+        for cls_, reg_ in zip(self.dec_score_head, self.dec_bbox_head):
+            constant_(cls_.bias, bias_cls)
+            constant_(reg_.layers[-1].weight, 0.)
+            constant_(reg_.layers[-1].bias, 0.)
+        lin = self.enc_output[0]
+        bound = 1 / math.sqrt(lin.weight.shape[0])
+        uniform_(lin.bias, -bound, bound)
+        xavier_uniform_(lin.weight)
+        xavier_uniform_(self.query_pos_head.layers[0].weight)
+        xavier_uniform_(self.query_pos_head.layers[1].weight)
+        for layer in self.input_proj:
+            xavier_uniform_(layer[0].weight)
+
+    def q8_site(self, key, x, x2=None):
+        return None                                           # fp8 for the RT-DETR head is not built
+
+    # -- dense linears on the implicit-GEMM convolution: a token matrix (B, N, C) is an NHWC map of height 1 -----------------------
+    VIEW_BYTES = (1 << 31) - 1                                # the convolution addresses one view with 32-bit byte offsets: larger token matrices go in batch chunks
+
+    @staticmethod
+    def _as_map(t):
+        """(B, N, C) -> (B, C, 1, N), channels innermost in memory; the unused stride of the height-1 dimension is one token, not the whole image"""
+        b, n, c = t.shape
+        return t.as_strided((b, c, 1, n), (t.stride(0), 1, t.stride(1), t.stride(1)), t.storage_offset())
+
+    def _linear(self, key, x, cout, weight, bias, act=ops.ACT_NONE, x2=None, tensors=None):
+        """act((x [+ x2]) @ weight^T + bias): x (B, N, cin) -> (B, N, cout), computed and stored in x's dtype (fp32, or bf16 for the token memory's
+        consumers).  `weight` / `bias`: callables that build the (merged) panel's source when the panel is packed, `tensors`: the parameters it
+        depends on."""
+        b, n, cin = x.shape
+        xm = self._as_map(x)
+        dt = x.dtype
+        mfma = cout % 4 == 0 and ops.conv_can_mfma(xm, cin, cout, 1, 1, 1, dt)
+        if not mfma and dt != torch.float32:
+            raise RuntimeError(f'RTDETRDecoder: the bf16 linear {key} ({cin} -> {cout}) is outside the MFMA route')
+        if not mfma and x2 is not None:
+            raise RuntimeError(f'RTDETRDecoder: the linear {key} ({cin} -> {cout}) is outside the MFMA route and cannot add its second input')
+        pk = self._cached((key, mfma, dt), tensors, lambda: ops.PackedConv(weight().reshape(cout, cin, 1, 1), bias(), None, 1, dt, direct=not mfma))
+        out = torch.empty(b, n, cout, dtype=dt, device=x.device)
+        om, x2m = self._as_map(out), None if x2 is None else self._as_map(x2)
+        step = max(1, self.VIEW_BYTES // (n * max(cin, cout, x.stride(1)) * x.element_size()))
+        for b0 in range(0, b, step):
+            ops.conv2d(xm[b0:b0 + step], pk, 1, act, out=om[b0:b0 + step], x2=None if x2m is None else x2m[b0:b0 + step])
+        return out
+
+    def _lin(self, key, x, lin, act=ops.ACT_NONE, x2=None):
+        return self._linear(key, x, lin.out_features, lambda: lin.weight, lambda: lin.bias, act, x2, [lin.weight, lin.bias])
+
+    def _mlp(self, key, x, mlp):
+        for j, lin in enumerate(mlp.layers):
+            x = self._lin((key, j), x, lin, ops.ACT_RELU if j < mlp.num_layers - 1 else ops.ACT_NONE)
+        return x
+
+    # -- encoder side ---------------------------------------------------------------------------------------------------------------
+    def _encode(self, x):
+        """feature maps -> (memory (B, L, 256), shapes, features (B, L, 256) after enc_output, class logits (B, L, nc), score_max (B, L))"""
+        if self.training:
+            raise NotImplementedError(RTDETR_TRAIN_MSG)
+        if not isinstance(x, (list, tuple)) or len(x) != self.nl:
+            raise RuntimeError(f'RTDETRDecoder: expected a list of {self.nl} feature maps')
+        dt = self.out_dtype(x[0])
+        if any(f.dtype != dt for f in x):
+            raise RuntimeError(f'RTDETRDecoder: the feature maps must come in the compute dtype {dt}, got {[str(f.dtype) for f in x]}')
+        b = x[0].shape[0]
+        shapes = [(int(f.shape[2]), int(f.shape[3])) for f in x]
+        L = sum(h * w for h, w in shapes)
+        memory = torch.empty(b, L, self.hidden_dim, dtype=dt, device=x[0].device)
+        off = 0
+        for i, (f, (h, w)) in enumerate(zip(x, shapes)):
+            conv, bn = self.input_proj[i][0], self.input_proj[i][1]
+            self._no_train_bn(bn)
+            if not ops.conv_can_mfma(f, conv.in_channels, self.hidden_dim, 1, 1, 1, dt):
+                raise RuntimeError(f'RTDETRDecoder: input {i} ({tuple(f.shape)}, strides {f.stride()}) is outside the implicit-GEMM route (NHWC, channels % 4 == 0 in fp32, % 8 == 0 in bf16)')
+            pk = self._cached(('proj', i, dt), [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var],
+                              lambda conv=conv, bn=bn: ops.PackedConv(conv.weight, None, (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps), 1, dt))
+            ops.conv2d(f, pk, 1, ops.ACT_NONE, out=memory[:, off:off + h * w].view(b, h, w, self.hidden_dim).permute(0, 3, 1, 2))
+            off += h * w
+        lin, ln = self.enc_output[0], self.enc_output[1]
+        # a token whose anchor is invalid enters enc_output zeroed (head.py:408): its linear is the bias, which the LayerNorm launch substitutes
+        feats = ops.add_layernorm(self._lin('enc_output', memory, lin), None, ln.weight, ln.bias, ln.eps, fill=lin.bias, shapes=shapes)
+        logits = self._lin('enc_score', feats, self.enc_score_head)
+        return memory, shapes, feats, logits, ops.rtdetr_rowmax(logits)
+
+    def select_queries(self, x):
+        """The query selection of head.py:416 as a public step: (index (B, nq) int64, score_max (B, L) fp32), both on the device.  torch.topk leaves
+        the order of equal scores unspecified; here it is descending score, equal scores by ascending token index."""
+        enc = self._encode(x)
+        return ops.rtdetr_topk(enc[4], self.num_queries), enc[4]
+
+    def forward(self, x, batch=None, query_index=None):
+        if self.training or batch is not None:
+            raise NotImplementedError(RTDETR_TRAIN_MSG)
+        if self.__dict__.get('_select_only'):                 # RTDETRDetectionModel.select_queries
+            return self.select_queries(x)
+        if query_index is None:
+            query_index = self.__dict__.get('_query_index')   # RTDETRDetectionModel.predict(query_index=...)
+        memory, shapes, feats, logits, score_max = self._encode(x)
+        b, nq, hd = memory.shape[0], self.num_queries, self.hidden_dim
+        if query_index is None:
+            index = ops.rtdetr_topk(score_max, nq)
+        else:
+            index = query_index
+            if not torch.is_tensor(index) or index.dtype != torch.int64 or tuple(index.shape) != (b, nq) or index.device != memory.device:
+                raise RuntimeError(f'RTDETRDecoder: query_index must be a ({b}, {nq}) int64 tensor on {memory.device}')
+            index = index.contiguous()
+        embed, enc_scores = ops.rtdetr_gather(feats, logits, index)
+        ref = enc_bboxes = ops.rtdetr_ref_init(self._mlp('enc_bbox', embed, self.enc_bbox_head), index, shapes)
+        layers = self.decoder.layers
+        # every layer's value_proj reads the same memory: one GEMM with an ndl*256-column panel
+        vt = [t for l in layers for t in (l.cross_attn.value_proj.weight, l.cross_attn.value_proj.bias)]
+        values = self._linear('values', memory, len(layers) * hd, lambda: torch.cat([l.cross_attn.value_proj.weight for l in layers], 0),
+                              lambda: torch.cat([l.cross_attn.value_proj.bias for l in layers], 0), tensors=vt)
+        no = self.nhead * self.nl * 4 * 2
+        scores = None
+        from .conv import act_code
+        for i, l in enumerate(layers):
+            sa, ca = l.self_attn, l.cross_attn
+            pos = self._mlp(('pos', i), ref, self.query_pos_head)
+            wt = [sa.in_proj_weight, sa.in_proj_bias]
+            qk = self._linear(('qk', i), embed, 2 * hd, lambda: sa.in_proj_weight[:2 * hd], lambda: sa.in_proj_bias[:2 * hd], x2=pos, tensors=wt)
+            v = self._linear(('v', i), embed, hd, lambda: sa.in_proj_weight[2 * hd:], lambda: sa.in_proj_bias[2 * hd:], tensors=wt)
+            t = self._lin(('sa_out', i), ops.mha(qk[..., :hd], qk[..., hd:], v), sa.out_proj)
+            embed = ops.add_layernorm(t, embed, l.norm1.weight, l.norm1.bias, l.norm1.eps)
+            # sampling offsets and attention weights: one panel
+            ow = self._linear(('ow', i), embed, no + no // 2, lambda: torch.cat([ca.sampling_offsets.weight, ca.attention_weights.weight], 0),
+                              lambda: torch.cat([ca.sampling_offsets.bias, ca.attention_weights.bias], 0), x2=pos,
+                              tensors=[ca.sampling_offsets.weight, ca.attention_weights.weight, ca.sampling_offsets.bias, ca.attention_weights.bias])
+            samp = ops.msdeform_attn(values[..., i * hd:(i + 1) * hd], shapes, ref, ow[..., :no], ow[..., no:])
+            t = self._lin(('ca_out', i), samp, ca.output_proj)
+            embed = ops.add_layernorm(t, embed, l.norm2.weight, l.norm2.bias, l.norm2.eps)
+            t = self._lin(('ffn2', i), self._lin(('ffn1', i), embed, l.linear1, act_code(l.act)), l.linear2)
+            embed = ops.add_layernorm(t, embed, l.norm3.weight, l.norm3.bias, l.norm3.eps)
+            ref = ops.rtdetr_refine(self._mlp(('bbox', i), embed, self.dec_bbox_head[i]), ref)
+            if i == self.decoder.eval_idx:
+                scores = ops.rtdetr_sigmoid(self._lin(('score', i), embed, self.dec_score_head[i]))
+                break
+        if scores is None:
+            raise RuntimeError(f'RTDETRDecoder: eval_idx {self.decoder.eval_idx} is outside the {len(layers)} decoder layers')
+        return ref.unsqueeze(0), scores.unsqueeze(0), enc_bboxes, enc_scores, None

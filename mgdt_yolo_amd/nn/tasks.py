@@ -19,11 +19,11 @@ import torch.nn as nn
 from .. import ops
 from ..yolo.utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts, make_divisible
 from .modules import (C2f, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, Detect, DWConv, InjectionMultiSum_Auto_pool,
-                      Pose, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
+                      Pose, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
 
 # names a YAML row may use -> class (the reference resolves them with globals()[m] / getattr(torch.nn, ...), tasks.py:630)
 REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, MSPA_C2f, SPPF, SimFusion_4in, SimFusion_3in, IFM,
-                                    InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose, Classify)}
+                                    InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose, Classify, RTDETRDecoder)}
 REGISTRY['nn.Upsample'] = Upsample
 
 
@@ -634,8 +634,59 @@ class ClassificationModel(BaseModel):
         return super().predict(x, profile=profile, visualize=visualize)
 
 
+class RTDETRDetectionModel(DetectionModel):
+    """RT-DETR detection model (reference tasks.py:409-480), inference only.  Eval forward -> the head's tuple (dec_bboxes (1, B, nq, 4) xywh in [0, 1],
+    dec_scores (1, B, nq, nc), enc_bboxes (B, nq, 4), enc_scores (B, nq, nc), None), fp32, with no host read: the layer loop and the head capture into one
+    graph.  `predict(x, batch=None, query_index=None)`: `query_index` (B, nq) int64 replaces the head's own query selection.  Training (`init_criterion`,
+    `loss`, a train-mode forward) and `augment=True` are not built and raise; `quantize_fp8` leaves the head on bf16."""
+
+    def __init__(self, cfg='yolov8n-rtdetr.yaml', ch=3, nc=None, verbose=True):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        if not isinstance(self.model[-1], RTDETRDecoder):
+            raise ValueError(f'RTDETRDetectionModel: the graph ends in {type(self.model[-1]).__name__}, not RTDETRDecoder')
+
+    def init_criterion(self):
+        from .modules.head import RTDETR_TRAIN_MSG
+        raise NotImplementedError(RTDETR_TRAIN_MSG)
+
+    def loss(self, batch, preds=None):
+        from .modules.head import RTDETR_TRAIN_MSG
+        raise NotImplementedError(RTDETR_TRAIN_MSG)
+
+    def predict(self, x, profile=False, visualize=False, batch=None, augment=False, query_index=None):
+        """tasks.py:455-480: the layers in front of the head, then head(inputs, batch) [with `query_index` in place of its own selection]"""
+        if augment:
+            raise RuntimeError('augment=True is not built for RTDETRDetectionModel: the detection test-time augmentation merges anchor-wise Detect outputs; '
+                               'run the plain single pass')
+        if profile or visualize:
+            raise RuntimeError('profile / visualize are host-side tooling outside the hot path')
+        head = self.model[-1]
+        if self.training or head.training or batch is not None:
+            from .modules.head import RTDETR_TRAIN_MSG
+            raise NotImplementedError(RTDETR_TRAIN_MSG)
+        if query_index is None:
+            return self._predict_once(x)
+        head.__dict__['_query_index'] = query_index
+        try:
+            return self._predict_once(x)
+        finally:
+            head.__dict__.pop('_query_index', None)
+
+    def select_queries(self, x):
+        """(index (B, nq) int64, score_max (B, L) fp32) of the head's query selection for the images x: the one discontinuous step of the model"""
+        head = self.model[-1]
+        head.__dict__['_select_only'] = True
+        try:
+            return self._predict_once(x)
+        finally:
+            head.__dict__.pop('_select_only', None)
+
+
 def model_class_of(cfg):
-    """SegmentationModel / PoseModel / ClassificationModel for a YAML dict whose head ends in Segment / Pose / Classify, DetectionModel otherwise."""
+    """SegmentationModel / PoseModel / ClassificationModel for a YAML dict whose head ends in Segment / Pose / Classify, RTDETRDetectionModel for
+    RTDETRDecoder, DetectionModel otherwise."""
+    if isinstance(cfg, dict) and str(cfg['head'][-1][-2]) == 'RTDETRDecoder':
+        return RTDETRDetectionModel
     return {'segment': SegmentationModel, 'pose': PoseModel, 'classify': ClassificationModel}.get(guess_model_task(cfg), DetectionModel)
 
 
@@ -764,6 +815,9 @@ def parse_model(d, ch, verbose=True):
             if m is Segment:                    # the proto width scales with the model (tasks.py:662-663)
                 args[2] = make_divisible(min(args[2], max_channels) * width, 8)
             r_out = red[f[0]]
+        elif m is RTDETRDecoder:                # the channel list goes in at argument index 1 (tasks.py:666); hd, nq, ndp, nh, ndl pass through
+            args.insert(1, [ch[x] for x in f])
+            r_out = red[f[0]]
         elif m is SimFusion_4in:
             c2 = sum(ch[x] for x in f)
             r_out = red[f[2]]
@@ -793,7 +847,7 @@ def parse_model(d, ch, verbose=True):
         t = f'{m.__module__}.{m.__name__}'
         m.np = sum(x.numel() for x in m_.parameters())
         m_.i, m_.f, m_.type = i, f, t
-        m_.c2 = None if m in (Detect, TOODHead, Segment, Pose) else c2          # output channels (the neck plan sizes the SimFusion buffers from them)
+        m_.c2 = None if m in (Detect, TOODHead, Segment, Pose, RTDETRDecoder) else c2          # output channels (the neck plan sizes the SimFusion buffers from them)
         if verbose:
             print(f'{i:>3}{str(f):>20}{n_:>3}{m.np:10.0f}  {t:<45}{str(args):<30}')
         save.extend(x % i for x in ([f] if isinstance(f, int) else f) if x != -1)
@@ -878,7 +932,7 @@ def yaml_model_load(path):
     """Load a model YAML in the reference's schema; '...yolov8n.yaml' resolves to '...yolov8.yaml' + scale n (tasks.py:702-717).
     Names of the built-in graphs (mgdt_yolo_amd.models.CONFIGS) resolve without a file."""
     import yaml
-    from ..models import CLS_CONFIGS, CONFIGS, POSE_CONFIGS, SEG_CONFIGS, get_config
+    from ..models import CLS_CONFIGS, CONFIGS, POSE_CONFIGS, RTDETR_CONFIGS, SEG_CONFIGS, get_config
     path = Path(path)
     scale = guess_model_scale(path)
     unified = Path(re.sub(r'(\d+)([nslmx])(.+)?$', r'\1\3', str(path)))
@@ -889,7 +943,7 @@ def yaml_model_load(path):
             d['scale'] = scale
             d['yaml_file'] = str(path)
             return d
-    if unified.stem in CONFIGS or unified.stem in SEG_CONFIGS or unified.stem in POSE_CONFIGS or unified.stem in CLS_CONFIGS:
+    if unified.stem in CONFIGS or unified.stem in SEG_CONFIGS or unified.stem in POSE_CONFIGS or unified.stem in CLS_CONFIGS or unified.stem in RTDETR_CONFIGS:
         d = get_config(unified.stem, scale or 'n')
         d['scale'] = scale
         d['yaml_file'] = str(path)

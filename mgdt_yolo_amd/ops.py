@@ -1988,3 +1988,170 @@ def bytetrack_export(state, streams, cap, which):
     d = {k: ints[i] for i, k in enumerate(('id', 'state', 'is_activated', 'frame_id', 'start_frame', 'tracklet_len'))}
     d.update(score=sc[0], cls=sc[1], mean=mean[:n].cpu().numpy(), covariance=cov[:n].cpu().numpy(), tracker_frame_id=frame_id, count=count)
     return d
+
+
+# ------------------------------------------------------------------ RT-DETR decoder head (csrc/rtdetr.hip)
+def _rt_shapes(shapes):
+    """[(h, w)] per level -> (host int array the entry points read during the call, nl, L)"""
+    flat = [int(v) for hw in shapes for v in hw]
+    return (C.c_int * len(flat))(*flat), len(shapes), sum(int(h) * int(w) for h, w in shapes)
+
+
+def _rt_rows(t, name, last=None, dtypes=(torch.float32,)):
+    """a (..., C) fp32 cuda tensor whose rows are dense and evenly strided (a column slice of a contiguous matrix qualifies) -> (rows, row stride)"""
+    _need_gpu(t)
+    if t.dtype not in dtypes:
+        raise RuntimeError(f'{name}: {" or ".join(str(d) for d in dtypes)} expected, got {t.dtype}')
+    if last is not None and t.shape[-1] != last:
+        raise RuntimeError(f'{name}: last dimension {t.shape[-1]}, expected {last}')
+    rows = t.numel() // t.shape[-1]
+    ld = t.stride(-2) if t.dim() > 1 else t.shape[-1]
+    if t.stride(-1) != 1 or (t.dim() > 2 and any(t.stride(i) != t.stride(i + 1) * t.shape[i + 1] for i in range(t.dim() - 2))):
+        raise RuntimeError(f'{name}: rows must be dense and evenly strided, got strides {t.stride()}')
+    return rows, ld
+
+
+def msdeform_attn(value, shapes, ref, offsets, weights):
+    """mgdt_msdeform_attn_fwd.  value (B, L, >= 256 columns; a 256-column slice of a wider matrix is fine) fp32 or bf16, ref (B, nq, 4),
+    offsets (B, nq, 8*nl*4*2) and weights (B, nq, 8*nl*4) logits (column slices of one panel are fine) -> (B, nq, 256) fp32."""
+    _need_gpu(value)
+    arr, nl, L = _rt_shapes(shapes)
+    b, nq = ref.shape[0], ref.shape[1]
+    if value.dim() != 3 or value.shape[0] != b or value.shape[1] != L or value.shape[2] != 256 or value.stride(2) != 1:
+        raise RuntimeError(f'msdeform_attn: value {tuple(value.shape)} strides {value.stride()} for batch {b}, {L} tokens of 256 channels')
+    _rt_rows(ref, 'msdeform_attn: ref', 4)
+    if not ref.is_contiguous():
+        raise RuntimeError('msdeform_attn: ref must be contiguous')
+    _, ldo = _rt_rows(offsets, 'msdeform_attn: offsets', 8 * nl * 4 * 2)
+    _, ldw = _rt_rows(weights, 'msdeform_attn: weights', 8 * nl * 4)
+    if tuple(offsets.shape[:2]) != (b, nq) or tuple(weights.shape[:2]) != (b, nq):
+        raise RuntimeError('msdeform_attn: offsets / weights must be (B, nq, ...) like ref')
+    out = torch.empty(b, nq, 256, dtype=torch.float32, device=value.device)
+    _launch('msdeform_attn_fwd', 'mgdt_msdeform_attn_fwd', ptr(value), value.stride(1), value.stride(0), arr, nl, b, nq, ptr(ref), ptr(offsets), ldo,
+            ptr(weights), ldw, ptr(out), dtype_code(value.dtype), stream())
+    return out
+
+
+def mha(q, k, v):
+    """mgdt_mha_fwd: q, k, v (B, nq, 256) fp32 (column slices of wider matrices are fine) -> (B, nq, 256), 8 heads, no mask."""
+    (_, ldq), (_, ldk), (_, ldv) = _rt_rows(q, 'mha: q', 256), _rt_rows(k, 'mha: k', 256), _rt_rows(v, 'mha: v', 256)
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
+        raise RuntimeError(f'mha: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must be one (B, nq, 256) shape')
+    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    _launch('mha_fwd', 'mgdt_mha_fwd', ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, q.shape[0], q.shape[1], ptr(out), stream())
+    return out
+
+
+def add_layernorm(x, res, gamma, beta, eps=1e-5, fill=None, shapes=None):
+    """mgdt_add_layernorm_fwd: LayerNorm(x [+ res]) over the last dimension (256) -> fp32; x fp32 or bf16, the rest fp32.  `fill` + `shapes`: the
+    masked form over (B, L, 256) tokens."""
+    rows, ldx = _rt_rows(x, 'add_layernorm: x', 256, (torch.float32, torch.bfloat16))
+    ldr = 0
+    if res is not None:
+        rr, ldr = _rt_rows(res, 'add_layernorm: res', 256)
+        if rr != rows:
+            raise RuntimeError('add_layernorm: x and res differ in rows')
+    for t, n in ((gamma, 'gamma'), (beta, 'beta'), (fill, 'fill')):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 256 or not t.is_contiguous()):
+            raise RuntimeError(f'add_layernorm: {n} must be 256 contiguous fp32 values')
+    arr, nl = None, 0
+    if fill is not None:
+        arr, nl, L = _rt_shapes(shapes)
+        if x.dim() != 3 or x.shape[1] != L:
+            raise RuntimeError(f'add_layernorm: the masked form takes (B, {L}, 256) tokens, got {tuple(x.shape)}')
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _launch('add_layernorm_fwd', 'mgdt_add_layernorm_fwd', ptr(x), dtype_code(x.dtype), ldx, ptr(res), ldr, ptr(gamma), ptr(beta), float(eps), rows, ptr(fill), arr, nl, ptr(out), stream())
+    return out
+
+
+def rtdetr_rowmax(x):
+    """mgdt_rtdetr_rowmax_fwd: (..., nc) fp32 -> (...) the maximum over the last dimension"""
+    rows, ld = _rt_rows(x, 'rtdetr_rowmax: x')
+    out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    _launch('rtdetr_rowmax_fwd', 'mgdt_rtdetr_rowmax_fwd', ptr(x), rows, x.shape[-1], ld, ptr(out), stream())
+    return out
+
+
+def rtdetr_topk(scores, k):
+    """mgdt_rtdetr_topk_fwd: (B, L) fp32 -> (B, k) int64, descending score, equal scores by ascending index.  k > L raises, as torch.topk does."""
+    _need_gpu(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise RuntimeError(f'rtdetr_topk: contiguous (B, L) fp32 scores expected, got {tuple(scores.shape)} {scores.dtype}')
+    b, L = scores.shape
+    if not 1 <= k <= L:
+        raise RuntimeError(f'rtdetr_topk: selected index k out of range (k = {k}, L = {L})')
+    out = torch.empty(b, k, dtype=torch.int64, device=scores.device)
+    _launch('rtdetr_topk_fwd', 'mgdt_rtdetr_topk_fwd', ptr(scores), b, L, k, ptr(out), stream())
+    return out
+
+
+def _rt_index(index, b, nq, name):
+    _need_gpu(index)
+    if index.dtype != torch.int64 or tuple(index.shape) != (b, nq) or not index.is_contiguous():
+        raise RuntimeError(f'{name}: index must be a contiguous ({b}, {nq}) int64 tensor, got {tuple(index.shape)} {index.dtype}')
+
+
+def rtdetr_gather(feat, scores, index):
+    """mgdt_rtdetr_gather_fwd: feat (B, L, 256), scores (B, L, nc), index (B, nq) -> (embed (B, nq, 256), enc_scores (B, nq, nc))"""
+    b, L = feat.shape[0], feat.shape[1]
+    nq, nc = index.shape[1], scores.shape[-1]
+    _rt_index(index, b, nq, 'rtdetr_gather')
+    if feat.dtype != torch.float32 or not feat.is_contiguous() or feat.shape[2] != 256:
+        raise RuntimeError('rtdetr_gather: feat must be contiguous (B, L, 256) fp32')
+    rows, lds = _rt_rows(scores, 'rtdetr_gather: scores')
+    if rows != b * L:
+        raise RuntimeError('rtdetr_gather: scores must have one row per token')
+    embed = torch.empty(b, nq, 256, dtype=torch.float32, device=feat.device)
+    enc = torch.empty(b, nq, nc, dtype=torch.float32, device=feat.device)
+    _launch('rtdetr_gather_fwd', 'mgdt_rtdetr_gather_fwd', ptr(feat), ptr(scores), lds, ptr(index), b, L, nq, nc, ptr(embed), ptr(enc), stream())
+    return embed, enc
+
+
+def rtdetr_ref_init(delta, index, shapes):
+    """mgdt_rtdetr_ref_init_fwd: sigmoid(delta (B, nq, 4) + anchor(index)) -> (B, nq, 4)"""
+    rows, ld = _rt_rows(delta, 'rtdetr_ref_init: delta', 4)
+    b, nq = index.shape
+    _rt_index(index, b, nq, 'rtdetr_ref_init')
+    if rows != b * nq:
+        raise RuntimeError('rtdetr_ref_init: delta must have one row per query')
+    arr, nl, _ = _rt_shapes(shapes)
+    out = torch.empty(b, nq, 4, dtype=torch.float32, device=delta.device)
+    _launch('rtdetr_ref_init_fwd', 'mgdt_rtdetr_ref_init_fwd', ptr(delta), ld, ptr(index), b, nq, arr, nl, ptr(out), stream())
+    return out
+
+
+def rtdetr_refine(delta, ref):
+    """mgdt_rtdetr_refine_fwd: sigmoid(delta + inverse_sigmoid(ref)), both (..., 4)"""
+    rows, ld = _rt_rows(delta, 'rtdetr_refine: delta', 4)
+    if ref.dtype != torch.float32 or not ref.is_contiguous() or ref.numel() != rows * 4:
+        raise RuntimeError('rtdetr_refine: ref must be contiguous fp32 with one row of 4 per row of delta')
+    _need_gpu(ref)
+    out = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
+    _launch('rtdetr_refine_fwd', 'mgdt_rtdetr_refine_fwd', ptr(delta), ld, ptr(ref), rows, ptr(out), stream())
+    return out
+
+
+def rtdetr_sigmoid(x):
+    """mgdt_rtdetr_sigmoid_fwd: element-wise sigmoid of (..., nc) fp32 rows into a dense tensor"""
+    rows, ld = _rt_rows(x, 'rtdetr_sigmoid: x')
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _launch('rtdetr_sigmoid_fwd', 'mgdt_rtdetr_sigmoid_fwd', ptr(x), rows, x.shape[-1], ld, ptr(out), stream())
+    return out
+
+
+def rtdetr_post(boxes, scores, conf, keep_class=None, wh=None):
+    """mgdt_rtdetr_post_fwd: boxes (B, nq, 4) xywh, scores (B, nq, nc) -> (rows (B, nq, 6), counts (B,) int32), both on the device.
+    keep_class: None or (nc,) uint8; wh: None or (B, 2) fp32 (w, h) each image's boxes are scaled by."""
+    _need_gpu(boxes)
+    b, nq, nc = scores.shape
+    for t, n, sh in ((boxes, 'boxes', (b, nq, 4)), (scores, 'scores', (b, nq, nc))):
+        if t.dtype != torch.float32 or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda:
+            raise RuntimeError(f'rtdetr_post: {n} must be contiguous {sh} fp32 on the device')
+    if keep_class is not None and (keep_class.dtype != torch.uint8 or keep_class.numel() != nc or not keep_class.is_contiguous() or not keep_class.is_cuda):
+        raise RuntimeError(f'rtdetr_post: keep_class must be {nc} uint8 values on the device')
+    if wh is not None and (wh.dtype != torch.float32 or tuple(wh.shape) != (b, 2) or not wh.is_contiguous() or not wh.is_cuda):
+        raise RuntimeError(f'rtdetr_post: wh must be ({b}, 2) fp32 on the device')
+    rows = torch.empty(b, nq, 6, dtype=torch.float32, device=boxes.device)
+    counts = torch.empty(b, dtype=torch.int32, device=boxes.device)
+    _launch('rtdetr_post_fwd', 'mgdt_rtdetr_post_fwd', ptr(boxes), ptr(scores), b, nq, nc, float(conf), ptr(keep_class), ptr(wh), ptr(rows), ptr(counts), stream())
+    return rows, counts
