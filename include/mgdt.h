@@ -716,6 +716,50 @@ int mgdt_rtdetr_sigmoid_fwd(const float* x, long rows, int nc, long ld, float* o
 int mgdt_rtdetr_post_fwd(const float* boxes, const float* scores, int batch, int nq, int nc, float conf, const uint8_t* keep_class, const float* wh, float* rows,
                          int32_t* counts, mgdt_stream s);
 
+/* ---- training augmentation (reference yolo/data/augment.py:762-790 v8_transforms, detection, stretch=False: Mosaic :117-188 or LetterBox
+ * :538-601, RandomPerspective :289-476 with perspective = 0, RandomHSV :479-501, RandomFlip :504-535, Format :692-746) -----------------------
+ * A batch of B output images in two launches; every random draw is made by the caller.  Nothing reads back to the host.
+ * pool: flat uint8, the images one after another, each h x w x 3 BGR (HWC, packed rows); the image table says where: one mgdt_aug_image per pool
+ *   image = byte offset, h, w (each <= imgsz) and the image's rows label_start .. +label_count of pool_labels [n_labels][5] fp32
+ *   (cls, x, y, w, h normalised to the image).  The table is passed twice: on the device for the kernels, on the host for the checks.
+ * records: one mgdt_aug_record per output image, 56 32-bit words, also passed on the device (read by the kernels) and on the host (checked):
+ *   word 0       nrect   rectangles placed on the canvas, 0..4 (4: a mosaic, 1: a letter-boxed image)
+ *   word 1       canvas  side of the square canvas in pixels (2 * imgsz for a mosaic, imgsz otherwise); it is never stored: 114 wherever no rectangle lies
+ *   word 2       flags   bit 0 flip up-down, bit 1 flip left-right, bit 2 the labels are clipped to the canvas and zero-area boxes dropped (Mosaic._cat_labels)
+ *   word 3       lut     byte offset into `luts` of this image's three 256-entry tables (hue, saturation, value: 768 bytes), a multiple of 4; -1: no HSV step
+ *   words 4..31  rect    [4][7] int32: source id, destination x1 y1 x2 y2 on the canvas (exclusive ends), source x1 y1: canvas[y1:y2, x1:x2] =
+ *                        image[sy1:.., sx1:..]; a later rectangle lies over an earlier one
+ *   words 32..37 inv     fp32: output pixel (x, y) of the unflipped imgsz x imgsz image reads the canvas at (inv0 x + inv1 y + inv2, inv3 x + inv4 y + inv5),
+ *                        pixel centres at integers, bilinear over the four neighbours, each 114 outside the canvas or outside every rectangle;
+ *                        evaluated in fp64 and rounded to the nearest integer
+ *   words 38..43 m       fp32: the first two rows of the forward matrix M (canvas -> output), for the boxes
+ *   word 44      scale   fp32: s of box_candidates (the source box is scaled by it; wh_thr 2, ar_thr 100, area_thr 0.1, eps 1e-16)
+ *   words 45..52 pad     [4][2] fp32: what is added to the de-normalised boxes of rectangle k's source (x, y)
+ *   words 53..55 reserved, 0
+ * mgdt_aug_check: the host-side test both launches run first (callable alone, no GPU): MGDT_BAD_ARG for a null table, a source id outside the pool, a
+ *   LUT offset outside `luts` or a non-finite coefficient; MGDT_BAD_SHAPE for a count, size, image or rectangle out of range.  imgsz % 4 == 0.
+ *   The kernels cut every rectangle to its source image again, so device records that differ from the checked ones read 114, never out of bounds.
+ * mgdt_aug_warp_fwd: out [batch][3][imgsz][imgsz] uint8, planes R, G, B, dense.  8-bit BGR <-> HSV by OpenCV's documented formulas (V = max,
+ *   S = 255 (V - min) / V, H / 2 in 0..179) in exact integer arithmetic, rounded half to even, H rounded before the wrap by 180.
+ * mgdt_aug_labels_fwd: cap = label rows per image, a multiple of 16.  labels [batch][cap][5] = (cls, x, y, w, h) normalised (Format's output), gt
+ *   [batch][cap][5] = (cls, x1, y1, x2, y2) in pixels (what v8DetectionLoss.preprocess makes of them), both in the order source by source, then the source's own;
+ *   rows past nlabels[b] zero.  flags[b] = 1 when more than cap boxes survive: the rows are then the first cap, nlabels[b] = cap. */
+typedef struct { int64_t offset; int32_t h, w, label_start, label_count; } mgdt_aug_image;
+typedef struct {
+  int32_t nrect, canvas, flags, lut;
+  int32_t rect[4][7];
+  float inv[6], m[6], scale, pad[4][2];
+  int32_t reserved[3];
+} mgdt_aug_record;
+int mgdt_aug_check(const mgdt_aug_record* records_host, int batch, const mgdt_aug_image* images_host, int n_pool, size_t pool_bytes, long n_labels,
+                   size_t lut_bytes, int imgsz);
+int mgdt_aug_warp_fwd(const void* pool, size_t pool_bytes, const mgdt_aug_image* images_dev, const mgdt_aug_image* images_host, int n_pool,
+                      const mgdt_aug_record* records_dev, const mgdt_aug_record* records_host, const void* luts, size_t lut_bytes, int batch, int imgsz,
+                      void* out, mgdt_stream s);
+int mgdt_aug_labels_fwd(const float* pool_labels, long n_labels, const mgdt_aug_image* images_dev, const mgdt_aug_image* images_host, int n_pool,
+                        const mgdt_aug_record* records_dev, const mgdt_aug_record* records_host, int batch, int imgsz, int cap, float* gt, float* labels,
+                        int32_t* nlabels, int32_t* flags, mgdt_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ slices `t[:, a:b]` are passed as strided views - the reference's chunk()/split()
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1988,6 +1989,76 @@ def bytetrack_export(state, streams, cap, which):
     d = {k: ints[i] for i, k in enumerate(('id', 'state', 'is_activated', 'frame_id', 'start_frame', 'tracklet_len'))}
     d.update(score=sc[0], cls=sc[1], mean=mean[:n].cpu().numpy(), covariance=cov[:n].cpu().numpy(), tracker_frame_id=frame_id, count=count)
     return d
+
+
+# ---- training augmentation (mgdt_aug_*: csrc/augment.hip) ----
+AUG_IMAGE = np.dtype([('offset', '<i8'), ('h', '<i4'), ('w', '<i4'), ('label_start', '<i4'), ('label_count', '<i4')])      # == mgdt_aug_image
+AUG_RECORD = np.dtype([('nrect', '<i4'), ('canvas', '<i4'), ('flags', '<i4'), ('lut', '<i4'), ('rect', '<i4', (4, 7)), ('inv', '<f4', (6,)),
+                       ('m', '<f4', (6,)), ('scale', '<f4'), ('pad', '<f4', (4, 2)), ('reserved', '<i4', (3,))])                 # == mgdt_aug_record
+assert AUG_IMAGE.itemsize == 24 and AUG_RECORD.itemsize == 224
+
+
+def _aug_host(a, dtype, what):
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or a.ndim != 1 or not a.flags.c_contiguous:
+        raise RuntimeError(f'{what} must be a contiguous 1-D numpy array of the {dtype.itemsize}-byte structure')
+    return C.c_void_p(a.ctypes.data)
+
+
+def aug_check(records, images, pool_bytes, n_labels, lut_bytes, imgsz):
+    """mgdt_aug_check on the host copies of the records and the image table: raises on anything the launches would refuse.  Needs no GPU."""
+    L.check(L.lib().mgdt_aug_check(_aug_host(records, AUG_RECORD, 'aug_check: records'), len(records), _aug_host(images, AUG_IMAGE, 'aug_check: images'),
+                                   len(images), int(pool_bytes), int(n_labels), int(lut_bytes), int(imgsz)), 'aug_check')
+
+
+def _aug_bytes(t, n, what):
+    _need_gpu(t)
+    if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise RuntimeError(f'{what} must be a contiguous uint8 device tensor of {n} bytes, got {tuple(t.shape)} {t.dtype}')
+    return t
+
+
+def aug_warp(pool, images_dev, images, records_dev, records, luts, batch, imgsz, out=None):
+    """mgdt_aug_warp_fwd: placement, affine warp, HSV tables, flips and Format's channel order for `batch` images in one launch -> (B, 3, S, S) uint8
+    RGB.  pool: flat uint8 device tensor; images / records: the host copies (checked), *_dev the same bytes on the device; luts: batch * 768 bytes."""
+    _need_gpu(pool)
+    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
+        raise RuntimeError('aug_warp: pool must be a flat contiguous uint8 tensor')
+    _aug_bytes(images_dev, len(images) * AUG_IMAGE.itemsize, 'aug_warp: images_dev')
+    _aug_bytes(records_dev, batch * AUG_RECORD.itemsize, 'aug_warp: records_dev')
+    _aug_bytes(luts, batch * 768, 'aug_warp: luts')
+    if len(records) != batch:
+        raise RuntimeError(f'aug_warp: {len(records)} records for a batch of {batch}')
+    if out is None:
+        out = torch.empty(batch, 3, imgsz, imgsz, dtype=torch.uint8, device=pool.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (batch, 3, imgsz, imgsz) or not out.is_contiguous():
+        raise RuntimeError(f'aug_warp: out must be a contiguous uint8 ({batch}, 3, {imgsz}, {imgsz}) tensor')
+    _launch('aug_warp_fwd', 'mgdt_aug_warp_fwd', ptr(pool), pool.numel(), ptr(images_dev), _aug_host(images, AUG_IMAGE, 'aug_warp: images'), len(images),
+            ptr(records_dev), _aug_host(records, AUG_RECORD, 'aug_warp: records'), ptr(luts), luts.numel(), int(batch), int(imgsz), ptr(out), stream())
+    return out
+
+
+def aug_labels(pool_labels, n_labels, images_dev, images, records_dev, records, batch, imgsz, cap, out=None):
+    """mgdt_aug_labels_fwd: the boxes of `batch` output images in one launch -> (gt (B, cap, 5) [cls, x1, y1, x2, y2] px, labels (B, cap, 5)
+    [cls, x, y, w, h] normalised, nlabels (B,) int32, flags (B,) int32: 1 = more than cap boxes survived, the rows are the first cap)."""
+    _need_gpu(pool_labels)
+    if pool_labels.dtype != torch.float32 or pool_labels.dim() != 2 or pool_labels.shape[1] != 5 or not pool_labels.is_contiguous() \
+            or pool_labels.shape[0] < n_labels:
+        raise RuntimeError(f'aug_labels: pool_labels must be a contiguous float32 (>= {n_labels}, 5) tensor')
+    _aug_bytes(images_dev, len(images) * AUG_IMAGE.itemsize, 'aug_labels: images_dev')
+    _aug_bytes(records_dev, batch * AUG_RECORD.itemsize, 'aug_labels: records_dev')
+    if len(records) != batch:
+        raise RuntimeError(f'aug_labels: {len(records)} records for a batch of {batch}')
+    if cap < 16 or cap % 16:
+        raise RuntimeError(f'aug_labels: the label capacity {cap} must be a multiple of 16')
+    dev = pool_labels.device
+    if out is None:
+        out = (torch.empty(batch, cap, 5, dtype=torch.float32, device=dev), torch.empty(batch, cap, 5, dtype=torch.float32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev), torch.empty(batch, dtype=torch.int32, device=dev))
+    gt, labels, nlabels, flags = out
+    _launch('aug_labels_fwd', 'mgdt_aug_labels_fwd', ptr(pool_labels), int(n_labels), ptr(images_dev), _aug_host(images, AUG_IMAGE, 'aug_labels: images'),
+            len(images), ptr(records_dev), _aug_host(records, AUG_RECORD, 'aug_labels: records'), int(batch), int(imgsz), int(cap), ptr(gt), ptr(labels),
+            ptr(nlabels), ptr(flags), stream())
+    return gt, labels, nlabels, flags
 
 
 # ------------------------------------------------------------------ RT-DETR decoder head (csrc/rtdetr.hip)

@@ -45,7 +45,14 @@ class v8DetectionLoss:
 
     def preprocess(self, batch, batch_size, imgsz_hw):
         """batch dict -> dense (B, Nmax, 5) [cls, xyxy px] on the device (loss.py:132-148,177-181).  Labels outside [0, nc) are refused here: the
-        assigner kernel indexes the class map with the label as it is (the reference's gather fails on such a label too)."""
+        assigner kernel indexes the class map with the label as it is (the reference's gather fails on such a label too).
+        A batch that already holds the dense labels on the device (batch['gt'], what TrainAugment.apply writes) is taken as it is: no host work, no
+        host read - and so no range check of its classes."""
+        if 'gt' in batch:
+            gt = batch['gt']
+            if not gt.is_cuda or gt.dtype != torch.float32 or gt.dim() != 3 or gt.shape[0] != batch_size or gt.shape[2] != 5 or not gt.is_contiguous():
+                raise ValueError(f"v8DetectionLoss: batch['gt'] must be a contiguous float32 ({batch_size}, N, 5) device tensor, got {tuple(gt.shape)} {gt.dtype}")
+            return gt
         idx = batch['batch_idx'].detach().cpu().numpy().reshape(-1).astype(np.int64)
         cls = batch['cls'].detach().cpu().numpy().reshape(-1, 1).astype(np.float32)
         if cls.size and not (cls.min() >= 0 and cls.max() < self.nc):          # also catches NaN
