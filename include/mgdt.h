@@ -716,6 +716,51 @@ int mgdt_rtdetr_sigmoid_fwd(const float* x, long rows, int nc, long ld, float* o
 int mgdt_rtdetr_post_fwd(const float* boxes, const float* scores, int batch, int nq, int nc, float conf, const uint8_t* keep_class, const float* wh, float* rows,
                          int32_t* counts, mgdt_stream s);
 
+/* ---- RT-DETR criterion and validator rows (reference vit/utils/ops.py:12-111 HungarianMatcher, vit/utils/loss.py DETRLoss / RTDETRDetectionLoss,
+ * yolo/utils/loss.py:16-53, vit/rtdetr/val.py:90-106) ----
+ * boxes [layers][batch][nq][4] xywh in [0, 1], logits [layers][batch][nq][ld_logits >= nc] raw, gt_boxes [G][4] xywh normalised, gt_cls [G] int32 (a
+ * class outside [0, nc) is clamped), gt_off [batch + 1] int32 = the exclusive offsets of the images' ground truths, passed on the device (read by the
+ * kernel) and on the host (checked; G = gt_off_host[batch]).  All fp32 unless said otherwise; no allocation, no host read, capturable.
+ * mgdt_detr_match_fwd: one launch for every (layer, image).  C[q][g] = g_class * cost_class + g_bbox * L1 + g_giou * (1 - GIoU), cost_class the focal
+ *   form of ops.py:86-88 on p = sigmoid(logit[q][gt_cls[g]]), GIoU = bbox_iou(xywh, eps 1e-7), in the reference's fp32 operation order; a cost that
+ *   is not finite becomes 1e18.  Per (layer, image) the assignment that minimises the sum of C over the matchings that give every ground truth of
+ *   the image a distinct query (scipy.optimize.linear_sum_assignment on the nq x ng block): shortest augmenting paths with fp64 potentials, exact for
+ *   the fp32 costs up to fp64 rounding of path sums; with several optima the one found is unspecified.
+ *   assign [layers][batch][nq] int32 = the global ground-truth index (into [G]) of the query, or -1.  cost: NULL or [layers][batch][nq][MGDT_DETR_GCAP],
+ *   only the entries [q][0 .. ng) of an image are written.  layer_of_match = -1: every layer on its own costs; k >= 0: only layer k is solved and its
+ *   assignment (and cost) is written for every layer (use_uni_match).  MGDT_BAD_SHAPE before any launch when an image has more than nq or more than
+ *   MGDT_DETR_GCAP ground truths or nq > MGDT_DETR_MAX_NQ; any nq >= 1, nc >= 1; an image without ground truths gets -1 everywhere.
+ *   workspace: mgdt_detr_match_workspace_bytes(layers, G, nq) bytes (the cost blocks, ground-truth major; contents undefined afterwards).
+ * mgdt_detr_loss_fwd: one launch for every layer.  assign as above (any value outside [0, G) = unmatched; several queries may share a ground truth:
+ *   a denoising pass); num_pairs = matched pairs per layer, known to the host.  gt_score [layers][batch][nq] = IoU (bbox_iou xywh, eps 1e-7) of a
+ *   matched query with its ground truth, 0 otherwise.  out [layers + 1][3] = (class, bbox, giou) per layer, then in row `layers` the sum of the rows 0 .. layers - 2 (the `_aux` entries): class = g_class * sum over (b, q, c) / max(num_pairs, 1)
+ *   of VarifocalLoss (use_vfl and num_pairs > 0: weight 0.75 sigmoid(x)^2 (1 - label) + gt_score label, target gt_score * onehot) or FocalLoss
+ *   (gamma 1.5, alpha 0.25); bbox = g_bbox * sum L1 / num_pairs; giou = g_giou * sum (1 - GIoU) / num_pairs; both 0 when num_pairs == 0.
+ *   d_boxes [layers][batch][nq][4] and d_logits [layers][batch][nq][nc] (dense), both or neither NULL: the gradients of gscale * sum over layers of
+ *   (class + bbox + giou), gt_score held constant, the varifocal weight differentiated; every element is written (0 for an unmatched query's box).
+ *   Box terms in fp64, class terms in fp32, sums in fp64: per-workgroup partials, then one fixed-order reduction by the workgroup that arrives last -
+ *   no floating-point atomics, bit-equal from run to run.  workspace: mgdt_detr_loss_workspace_bytes(layers, batch, nq) bytes, 16-byte aligned; its
+ *   first 16 bytes are zero before the first call and the kernel leaves them zero.
+ * mgdt_rtdetr_val_post_fwd: boxes [batch][nq][4] xywh, scores [batch][nq][nc] -> rows [batch][nq][6] = (x1, y1, x2, y2) * (w, h, w, h) of
+ *   wh[batch][2] (NULL: 1), conf = class maximum, cls (lowest index on ties); ALL nq rows, no threshold, in descending confidence, equal confidences
+ *   by ascending query index, NaN last (the reference's argsort(descending=True) leaves ties unspecified); counts[batch] int32 = nq.
+ *   1 <= nq <= MGDT_RTDETR_VAL_MAX_NQ, one workgroup per image. */
+#define MGDT_DETR_GCAP 256
+#define MGDT_DETR_MAX_NQ 2048
+#define MGDT_RTDETR_VAL_MAX_NQ 4096
+size_t mgdt_detr_match_workspace_bytes(int layers, int G, int nq);
+int mgdt_detr_match_fwd(const float* boxes, const float* logits, long ld_logits, int layers, int batch, int nq, int nc, const float* gt_boxes,
+                        const int32_t* gt_cls, const int32_t* gt_off_dev, const int32_t* gt_off_host, float g_class, float g_bbox, float g_giou,
+                        float alpha, float gamma, int layer_of_match, void* workspace, size_t workspace_bytes, int32_t* assign, float* cost,
+                        mgdt_stream s);
+size_t mgdt_detr_loss_workspace_bytes(int layers, int batch, int nq);
+int mgdt_detr_loss_fwd(const float* boxes, const float* logits, long ld_logits, int layers, int batch, int nq, int nc, const float* gt_boxes,
+                       const int32_t* gt_cls, int G, const int32_t* assign, long num_pairs, float g_class, float g_bbox, float g_giou, int use_vfl,
+                       float gscale, void* workspace, size_t workspace_bytes, float* out, float* gt_score, float* d_boxes, float* d_logits,
+                       mgdt_stream s);
+int mgdt_rtdetr_val_post_fwd(const float* boxes, const float* scores, int batch, int nq, int nc, const float* wh, float* rows, int32_t* counts,
+                             mgdt_stream s);
+
 /* ---- training augmentation (reference yolo/data/augment.py:762-790 v8_transforms, detection, stretch=False: Mosaic :117-188 or LetterBox
  * :538-601, RandomPerspective :289-476 with perspective = 0, RandomHSV :479-501, RandomFlip :504-535, Format :692-746) -----------------------
  * A batch of B output images in two launches; every random draw is made by the caller.  Nothing reads back to the host.

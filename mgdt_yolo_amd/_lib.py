@@ -201,6 +201,11 @@ PROTOTYPES = {
     'mgdt_rtdetr_refine_fwd': (_i, [_vp, _l, _vp, _l, _vp, _vp]),
     'mgdt_rtdetr_sigmoid_fwd': (_i, [_vp, _l, _i, _l, _vp, _vp]),
     'mgdt_rtdetr_post_fwd': (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    'mgdt_detr_match_workspace_bytes': (_sz, [_i, _i, _i]),
+    'mgdt_detr_match_fwd': (_i, [_vp, _vp, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp, _vp, _vp]),
+    'mgdt_detr_loss_workspace_bytes': (_sz, [_i, _i, _i]),
+    'mgdt_detr_loss_fwd': (_i, [_vp, _vp, _l, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _f, _f, _f, _i, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'mgdt_rtdetr_val_post_fwd': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'mgdt_aug_check': (_i, [_vp, _i, _vp, _i, _sz, _l, _sz, _i]),
     'mgdt_aug_warp_fwd': (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp]),
     'mgdt_aug_labels_fwd': (_i, [_vp, _l, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

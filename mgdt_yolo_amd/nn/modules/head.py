@@ -769,8 +769,9 @@ class TOODHead(Detect):
 
 # ====================================================================================================================
 # RTDETRDecoder (reference nn/modules/head.py:275-464), inference only.
-RTDETR_TRAIN_MSG = ('RT-DETR training is not built: the RT-DETR loss with its Hungarian matcher and the denoising groups (vit/utils/loss.py, vit/utils/ops.py) '
-                    'have no HIP counterpart here; RTDETRDecoder runs in eval() only')
+RTDETR_TRAIN_MSG = ('RT-DETR training is not built: the generation of the denoising query groups (vit/utils/ops.py get_cdn_group) and the reverse pass of the '
+                    'decoder have no HIP counterpart here; RTDETRDecoder runs in eval() only.  The criterion exists on its own: RTDETRDetectionModel.detr_criterion(), '
+                    'predict_layers() and loss_from_preds()')
 
 
 class RTDETRDecoder(HipModule):
@@ -917,6 +918,17 @@ class RTDETRDecoder(HipModule):
             return self.select_queries(x)
         if query_index is None:
             query_index = self.__dict__.get('_query_index')   # RTDETRDetectionModel.predict(query_index=...)
+        return self._decode(x, query_index, bool(self.__dict__.get('_all_layers')))
+
+    def forward_layers(self, x, query_index=None):
+        """Eval only: the reference's training-layout tuple without denoising (head.py with self.training set and num_denoising = 0):
+        (dec_bboxes (ndl, B, nq, 4) - the refined boxes after every decoder layer, dec_scores (ndl, B, nq, nc) RAW logits of every layer's score head,
+        enc_bboxes (B, nq, 4), enc_scores (B, nq, nc) raw, None).  The launches are forward()'s, plus the score head on every layer and no sigmoid."""
+        if self.training:
+            raise NotImplementedError(RTDETR_TRAIN_MSG)
+        return self._decode(x, query_index, True)
+
+    def _decode(self, x, query_index, all_layers):
         memory, shapes, feats, logits, score_max = self._encode(x)
         b, nq, hd = memory.shape[0], self.num_queries, self.hidden_dim
         if query_index is None:
@@ -935,6 +947,7 @@ class RTDETRDecoder(HipModule):
                               lambda: torch.cat([l.cross_attn.value_proj.bias for l in layers], 0), tensors=vt)
         no = self.nhead * self.nl * 4 * 2
         scores = None
+        all_boxes, all_scores = [], []
         from .conv import act_code
         for i, l in enumerate(layers):
             sa, ca = l.self_attn, l.cross_attn
@@ -954,9 +967,15 @@ class RTDETRDecoder(HipModule):
             t = self._lin(('ffn2', i), self._lin(('ffn1', i), embed, l.linear1, act_code(l.act)), l.linear2)
             embed = ops.add_layernorm(t, embed, l.norm3.weight, l.norm3.bias, l.norm3.eps)
             ref = ops.rtdetr_refine(self._mlp(('bbox', i), embed, self.dec_bbox_head[i]), ref)
+            if all_layers:
+                all_boxes.append(ref)
+                all_scores.append(self._lin(('score', i), embed, self.dec_score_head[i]))
+                continue
             if i == self.decoder.eval_idx:
                 scores = ops.rtdetr_sigmoid(self._lin(('score', i), embed, self.dec_score_head[i]))
                 break
+        if all_layers:
+            return torch.stack(all_boxes), torch.stack(all_scores), enc_bboxes, enc_scores, None
         if scores is None:
             raise RuntimeError(f'RTDETRDecoder: eval_idx {self.decoder.eval_idx} is outside the {len(layers)} decoder layers')
         return ref.unsqueeze(0), scores.unsqueeze(0), enc_bboxes, enc_scores, None

@@ -637,8 +637,10 @@ class ClassificationModel(BaseModel):
 class RTDETRDetectionModel(DetectionModel):
     """RT-DETR detection model (reference tasks.py:409-480), inference only.  Eval forward -> the head's tuple (dec_bboxes (1, B, nq, 4) xywh in [0, 1],
     dec_scores (1, B, nq, nc), enc_bboxes (B, nq, 4), enc_scores (B, nq, nc), None), fp32, with no host read: the layer loop and the head capture into one
-    graph.  `predict(x, batch=None, query_index=None)`: `query_index` (B, nq) int64 replaces the head's own query selection.  Training (`init_criterion`,
-    `loss`, a train-mode forward) and `augment=True` are not built and raise; `quantize_fp8` leaves the head on bf16."""
+    graph.  `predict(x, batch=None, query_index=None)`: `query_index` (B, nq) int64 replaces the head's own query selection.  `predict_layers` returns every
+    decoder layer's outputs, `detr_criterion()` the RT-DETR loss with its Hungarian matcher, `loss_from_preds(batch, preds)` the reference's `loss` from the
+    predictions on.  Training itself (`init_criterion`, `loss`, a train-mode forward: the denoising groups and the decoder's reverse pass are missing) and
+    `augment=True` are not built and raise; `quantize_fp8` leaves the head on bf16."""
 
     def __init__(self, cfg='yolov8n-rtdetr.yaml', ch=3, nc=None, verbose=True):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
@@ -671,6 +673,51 @@ class RTDETRDetectionModel(DetectionModel):
             return self._predict_once(x)
         finally:
             head.__dict__.pop('_query_index', None)
+
+    def predict_layers(self, x, query_index=None):
+        """Eval only: the head's `forward_layers` tuple for the images x - every decoder layer's boxes and RAW class logits, the layout the reference's
+        head returns in training without denoising: (dec_bboxes (ndl, B, nq, 4), dec_scores (ndl, B, nq, nc), enc_bboxes, enc_scores, None)."""
+        head = self.model[-1]
+        if self.training or head.training:
+            from .modules.head import RTDETR_TRAIN_MSG
+            raise NotImplementedError(RTDETR_TRAIN_MSG)
+        head.__dict__['_all_layers'] = True
+        if query_index is not None:
+            head.__dict__['_query_index'] = query_index
+        try:
+            return self._predict_once(x)
+        finally:
+            head.__dict__.pop('_all_layers', None)
+            head.__dict__.pop('_query_index', None)
+
+    def detr_criterion(self):
+        """tasks.py:414-418: the RT-DETR criterion (what `init_criterion` returns in the reference; here `init_criterion` / `loss` still raise, because a
+        training forward and the decoder's reverse pass do not exist)."""
+        from ..vit.utils.loss import RTDETRDetectionLoss
+        return RTDETRDetectionLoss(nc=getattr(self, 'nc', self.yaml['nc']), use_vfl=True)      # self.nc is the trainer's attribute in the reference
+
+    def loss_from_preds(self, batch, preds):
+        """tasks.py:424-453 from `preds` on: batch = {'batch_idx', 'cls', 'bboxes'} (the labels grouped by image, as the reference's collate leaves them; 'img'
+        or 'batch_size' gives the image count), preds = the training-layout tuple (`predict_layers`) -> (sum of all losses, tensor[loss_giou, loss_class,
+        loss_bbox]).  One host read of batch_idx for gt_groups, as in the reference."""
+        if not hasattr(self, 'criterion'):
+            self.criterion = self.detr_criterion()
+        dec_bboxes, dec_scores, enc_bboxes, enc_scores, dn_meta = preds
+        dev = dec_bboxes.device
+        bs = len(batch['img']) if 'img' in batch else int(batch.get('batch_size', dec_bboxes.shape[1]))
+        batch_idx = batch['batch_idx'].view(-1)
+        gt_groups = torch.bincount(batch_idx.detach().cpu().long(), minlength=bs)[:bs].tolist()
+        targets = {'cls': batch['cls'].to(dev, dtype=torch.long).view(-1), 'bboxes': batch['bboxes'].to(device=dev),
+                   'batch_idx': batch_idx.to(dev, dtype=torch.long), 'gt_groups': gt_groups}
+        if dn_meta is None:
+            dn_bboxes, dn_scores = None, None
+        else:
+            dn_bboxes, dec_bboxes = torch.split(dec_bboxes, dn_meta['dn_num_split'], dim=2)
+            dn_scores, dec_scores = torch.split(dec_scores, dn_meta['dn_num_split'], dim=2)
+        dec_bboxes = torch.cat([enc_bboxes.unsqueeze(0), dec_bboxes])
+        dec_scores = torch.cat([enc_scores.unsqueeze(0), dec_scores])
+        loss = self.criterion((dec_bboxes, dec_scores), targets, dn_bboxes=dn_bboxes, dn_scores=dn_scores, dn_meta=dn_meta)
+        return sum(loss.values()), torch.stack([loss[k].detach() for k in ('loss_giou', 'loss_class', 'loss_bbox')])
 
     def select_queries(self, x):
         """(index (B, nq) int64, score_max (B, L) fp32) of the head's query selection for the images x: the one discontinuous step of the model"""

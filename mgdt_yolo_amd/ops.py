@@ -2226,3 +2226,103 @@ def rtdetr_post(boxes, scores, conf, keep_class=None, wh=None):
     counts = torch.empty(b, dtype=torch.int32, device=boxes.device)
     _launch('rtdetr_post_fwd', 'mgdt_rtdetr_post_fwd', ptr(boxes), ptr(scores), b, nq, nc, float(conf), ptr(keep_class), ptr(wh), ptr(rows), ptr(counts), stream())
     return rows, counts
+
+
+# ------------------------------------------------------------------------------------------------ RT-DETR criterion, validator rows
+DETR_GCAP = 256          # == MGDT_DETR_GCAP: most ground truths of one image, row length of the exported cost
+DETR_MAX_NQ = 2048       # == MGDT_DETR_MAX_NQ
+RTDETR_VAL_MAX_NQ = 4096
+_DETR_WS = {}            # (device, bytes, lane) -> zero-initialised workspace of mgdt_detr_loss_fwd (its arrival counter lives across calls, at rest 0)
+
+
+def _detr_inputs(boxes, logits, name):
+    _need_gpu(boxes)
+    if boxes.dim() != 4 or boxes.shape[-1] != 4 or boxes.dtype != torch.float32 or not boxes.is_contiguous():
+        raise RuntimeError(f'{name}: boxes must be a contiguous (layers, B, nq, 4) fp32 tensor, got {tuple(boxes.shape)} {boxes.dtype}')
+    l, b, nq = boxes.shape[:3]
+    if logits.dim() != 4 or tuple(logits.shape[:3]) != (l, b, nq) or logits.dtype != torch.float32 or not logits.is_contiguous() or not logits.is_cuda:
+        raise RuntimeError(f'{name}: logits must be a contiguous ({l}, {b}, {nq}, nc) fp32 tensor on the device, got {tuple(logits.shape)} {logits.dtype}')
+    return l, b, nq, logits.shape[3]
+
+
+def _detr_gts(gt_boxes, gt_cls, gt_groups, b, name):
+    """gt_groups: the host's per-image counts -> (G, host int32 offsets (B + 1))."""
+    if len(gt_groups) != b:
+        raise RuntimeError(f'{name}: gt_groups has {len(gt_groups)} entries for a batch of {b}')
+    off = np.zeros(b + 1, dtype=np.int32)
+    np.cumsum(np.asarray(gt_groups, dtype=np.int64), out=off[1:])
+    g = int(off[-1])
+    if tuple(gt_boxes.shape) != (g, 4) or gt_boxes.dtype != torch.float32 or not gt_boxes.is_contiguous():
+        raise RuntimeError(f'{name}: gt_boxes must be a contiguous ({g}, 4) fp32 tensor, got {tuple(gt_boxes.shape)} {gt_boxes.dtype}')
+    if gt_cls.numel() != g or gt_cls.dtype != torch.int32 or not gt_cls.is_contiguous():
+        raise RuntimeError(f'{name}: gt_cls must be {g} contiguous int32 values, got {tuple(gt_cls.shape)} {gt_cls.dtype}')
+    if g:
+        _need_gpu(gt_boxes)
+        _need_gpu(gt_cls)
+    return g, off
+
+
+def detr_match(boxes, logits, gt_boxes, gt_cls, gt_groups, gt_off=None, gains=(2.0, 5.0, 2.0), alpha=0.25, gamma=2.0, layer_of_match=-1, want_cost=False):
+    """mgdt_detr_match_fwd: boxes (layers, B, nq, 4), logits (layers, B, nq, nc) raw, gt_boxes (G, 4), gt_cls (G,) int32, gt_groups = the host's per-image
+    counts, gt_off = their (B + 1,) exclusive offsets on the device (made here when None: one small copy, so pass it when capturing).
+    -> assign (layers, B, nq) int32 [, cost (layers, B, nq, DETR_GCAP), zero where no ground truth]."""
+    l, b, nq, nc = _detr_inputs(boxes, logits, 'detr_match')
+    g, off = _detr_gts(gt_boxes, gt_cls, gt_groups, b, 'detr_match')
+    dev = boxes.device
+    if gt_off is None:
+        gt_off = torch.from_numpy(off).to(dev)
+    gt_off = _i32(gt_off, b + 1, 'detr_match: gt_off')
+    nbytes = L.lib().mgdt_detr_match_workspace_bytes(l, g, nq)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    assign = torch.empty(l, b, nq, dtype=torch.int32, device=dev)
+    cost = torch.zeros(l, b, nq, DETR_GCAP, dtype=torch.float32, device=dev) if want_cost else None
+    _launch('detr_match_fwd', 'mgdt_detr_match_fwd', ptr(boxes), ptr(logits), logits.stride(2), l, b, nq, nc, ptr(gt_boxes) if g else None, ptr(gt_cls) if g else None,
+            ptr(gt_off), off.ctypes.data_as(C.c_void_p), float(gains[0]), float(gains[1]), float(gains[2]), float(alpha), float(gamma), int(layer_of_match),
+            ptr(ws), ws.numel(), ptr(assign), ptr(cost), stream())
+    return (assign, cost) if want_cost else assign
+
+
+def detr_loss(boxes, logits, gt_boxes, gt_cls, assign, num_pairs, gains=(1.0, 5.0, 2.0), use_vfl=True, gscale=1.0, want_grads=False):
+    """mgdt_detr_loss_fwd: -> (out (layers + 1, 3) = class / bbox / giou per layer and, in the last row, summed over every layer but the last, gt_score
+    (layers, B, nq), d_boxes, d_logits); the gradients (of gscale * out[:layers].sum()) are None unless want_grads."""
+    l, b, nq, nc = _detr_inputs(boxes, logits, 'detr_loss')
+    g = gt_boxes.shape[0]
+    if tuple(gt_boxes.shape) != (g, 4) or gt_boxes.dtype != torch.float32 or not gt_boxes.is_contiguous() or gt_cls.numel() != g or gt_cls.dtype != torch.int32 or not gt_cls.is_contiguous():
+        raise RuntimeError(f'detr_loss: gt_boxes (G, 4) fp32 and gt_cls (G,) int32 expected, got {tuple(gt_boxes.shape)} {gt_boxes.dtype}, {tuple(gt_cls.shape)} {gt_cls.dtype}')
+    if tuple(assign.shape) != (l, b, nq):
+        raise RuntimeError(f'detr_loss: assign must be ({l}, {b}, {nq}), got {tuple(assign.shape)}')
+    assign = _i32(assign, l * b * nq, 'detr_loss: assign')
+    dev = boxes.device
+    nbytes = L.lib().mgdt_detr_loss_workspace_bytes(l, b, nq)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), nbytes, _LANE[0])
+    ws = _DETR_WS.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('detr_loss: run the criterion once before capturing it into a graph (the kernel\'s arrival counter is allocated and zeroed on first use)')
+        ws = _DETR_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(l + 1, 3, dtype=torch.float32, device=dev)
+    gt_score = torch.empty(l, b, nq, dtype=torch.float32, device=dev)
+    d_boxes = torch.empty(l, b, nq, 4, dtype=torch.float32, device=dev) if want_grads else None
+    d_logits = torch.empty(l, b, nq, nc, dtype=torch.float32, device=dev) if want_grads else None
+    _launch('detr_loss_fwd', 'mgdt_detr_loss_fwd', ptr(boxes), ptr(logits), logits.stride(2), l, b, nq, nc, ptr(gt_boxes) if g else None, ptr(gt_cls) if g else None, g,
+            ptr(assign), int(num_pairs), float(gains[0]), float(gains[1]), float(gains[2]), 1 if use_vfl else 0, float(gscale), ptr(ws), nbytes, ptr(out), ptr(gt_score),
+            ptr(d_boxes), ptr(d_logits), stream())
+    return out, gt_score, d_boxes, d_logits
+
+
+def rtdetr_val_post(boxes, scores, wh=None):
+    """mgdt_rtdetr_val_post_fwd: boxes (B, nq, 4) xywh, scores (B, nq, nc) -> (rows (B, nq, 6) in descending confidence (ties by query index, NaN last),
+    counts (B,) int32 = nq), all nq rows, no threshold.  wh: None or (B, 2) fp32 (w, h) each image's boxes are scaled by."""
+    _need_gpu(boxes)
+    if scores.dim() != 3:
+        raise RuntimeError(f'rtdetr_val_post: scores must be (B, nq, nc), got {tuple(scores.shape)}')
+    b, nq, nc = scores.shape
+    for t, n, sh in ((boxes, 'boxes', (b, nq, 4)), (scores, 'scores', (b, nq, nc))):
+        if t.dtype != torch.float32 or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda:
+            raise RuntimeError(f'rtdetr_val_post: {n} must be contiguous {sh} fp32 on the device')
+    if wh is not None and (wh.dtype != torch.float32 or tuple(wh.shape) != (b, 2) or not wh.is_contiguous() or not wh.is_cuda):
+        raise RuntimeError(f'rtdetr_val_post: wh must be ({b}, 2) fp32 on the device')
+    rows = torch.empty(b, nq, 6, dtype=torch.float32, device=boxes.device)
+    counts = torch.empty(b, dtype=torch.int32, device=boxes.device)
+    _launch('rtdetr_val_post_fwd', 'mgdt_rtdetr_val_post_fwd', ptr(boxes), ptr(scores), b, nq, nc, ptr(wh), ptr(rows), ptr(counts), stream())
+    return rows, counts

@@ -1,4 +1,5 @@
-"""reference: vit/rtdetr - RT-DETR.  The predictor is built; the model wrapper, the trainer and the validator are not."""
+"""reference: vit/rtdetr - RT-DETR.  The predictor and the validator are built; the model wrapper and the trainer are not."""
 from .predict import RTDETRPredictor
+from .val import RTDETRValidator
 
-__all__ = ('RTDETRPredictor',)
+__all__ = ('RTDETRPredictor', 'RTDETRValidator')
