@@ -554,7 +554,9 @@ int mgdt_sgd_step(float* p, const float* g, float* buf, const float* wd, long n,
                   int first, const float* clip2, mgdt_stream s);
 int mgdt_ema_update(float* ema, const float* p, long n, float decay, mgdt_stream s);
 /* SGD + EMA in one launch, scalars from device memory: hyper4 = {lr, lr_bias, momentum, ema_decay}; [0, n_param) parameters, [n_param, n_total)
- * buffers (EMA only; ema may be NULL).  Reference: yolo/engine/trainer.py:317-326 (warm-up values), :462-470, yolo/utils/torch_utils.py:342. */
+ * buffers (EMA only; ema may be NULL); only hyper4[0..3] are read.  Bit-equal to mgdt_sgd_step followed by mgdt_ema_update: all three, like the
+ * families below, are the one streaming kernel described there (SGD: 8 words per parameter; with `first` the old content of buf is not used).
+ * Reference: yolo/engine/trainer.py:317-326 (warm-up values), :462-470, yolo/utils/torch_utils.py:342. */
 int mgdt_sgd_ema_step_dev(float* p, const float* g, float* buf, const float* wd, long n_param, float* ema, long n_total, const float* hyper4,
                           int nesterov, int first, const float* clip2, mgdt_stream s);
 /* Adam / AdamW / RMSProp on the same flat buffers (build_optimizer yolo/engine/trainer.py:651-654; `optimizer: auto` -> AdamW, :635-639), in

@@ -1728,18 +1728,23 @@ def grad_clip_coef(flat_grad, max_norm):
 PARAM_EPOCH = [0]
 
 
-def sgd_step(p, g, buf, wd, lr, momentum, nesterov, first, clip=None, lr_bias=None):
+def _step_stream():
+    """stream() for the launch of an optimizer step: the parameters are about to change, so the epoch moves.  (An argument of the launch and
+    not a wrapper around it: these wrappers are ~10 us of Python per ~10 us kernel, where one more frame with *args shows in tools/optim_bench.py.)"""
     PARAM_EPOCH[0] += 1
+    return stream()
+
+
+def sgd_step(p, g, buf, wd, lr, momentum, nesterov, first, clip=None, lr_bias=None):
     _launch('sgd_step', 'mgdt_sgd_step', ptr(p), ptr(g), ptr(buf), ptr(wd), p.numel(), float(lr), float(lr if lr_bias is None else lr_bias), float(momentum),
-            int(nesterov), int(first), ptr(clip), stream())
+            int(nesterov), int(first), ptr(clip), _step_stream())
 
 
 def sgd_ema_step_dev(p, g, buf, wd, ema, data, hyper, nesterov, first, clip=None):
     """SGD over the parameters `p` (= data[:p.numel()]) and EMA over all of `data`, scalars {lr, lr_bias, momentum, ema_decay} from the device
     tensor `hyper` (fp32[4]): the form a captured training step uses."""
-    PARAM_EPOCH[0] += 1
     _launch('sgd_ema_step_dev', 'mgdt_sgd_ema_step_dev', ptr(p), ptr(g), ptr(buf), ptr(wd), p.numel(), ptr(ema), data.numel(), ptr(hyper),
-            int(nesterov), int(first), ptr(clip), stream())
+            int(nesterov), int(first), ptr(clip), _step_stream())
 
 
 def ema_update(ema, p, decay):
@@ -1762,31 +1767,27 @@ def rmsprop_hyper(lr, lr_bias, momentum, ema_decay):
 
 def adam_step(p, g, m, v, wd, lr, beta1, beta2, eps, step, decoupled, clip=None, lr_bias=None):
     """torch.optim.Adam (decoupled False) / AdamW (True) over the flat buffers; `step` is 1-based."""
-    PARAM_EPOCH[0] += 1
     _launch('adam_step', 'mgdt_adam_step', ptr(p), ptr(g), ptr(m), ptr(v), ptr(wd), p.numel(), float(lr), float(lr if lr_bias is None else lr_bias),
-            float(beta1), float(beta2), float(eps), int(step), int(decoupled), ptr(clip), stream())
+            float(beta1), float(beta2), float(eps), int(step), int(decoupled), ptr(clip), _step_stream())
 
 
 def adam_ema_step_dev(p, g, m, v, wd, ema, data, hyper, beta2, eps, decoupled, clip=None):
     """Adam / AdamW over the parameters `p` (= data[:p.numel()]) and EMA over all of `data`, per-step scalars from the device tensor `hyper`
     (fp32[8], adam_hyper): the form a captured training step uses."""
-    PARAM_EPOCH[0] += 1
     _launch('adam_ema_step_dev', 'mgdt_adam_ema_step_dev', ptr(p), ptr(g), ptr(m), ptr(v), ptr(wd), p.numel(), ptr(ema), data.numel(), ptr(hyper),
-            float(beta2), float(eps), int(decoupled), ptr(clip), stream())
+            float(beta2), float(eps), int(decoupled), ptr(clip), _step_stream())
 
 
 def rmsprop_step(p, g, sq, buf, wd, lr, alpha, eps, momentum, clip=None, lr_bias=None):
     """torch.optim.RMSprop(centered=False) over the flat buffers; `buf` may be None when momentum is 0."""
-    PARAM_EPOCH[0] += 1
     _launch('rmsprop_step', 'mgdt_rmsprop_step', ptr(p), ptr(g), ptr(sq), ptr(buf), ptr(wd), p.numel(), float(lr), float(lr if lr_bias is None else lr_bias),
-            float(alpha), float(eps), float(momentum), ptr(clip), stream())
+            float(alpha), float(eps), float(momentum), ptr(clip), _step_stream())
 
 
 def rmsprop_ema_step_dev(p, g, sq, buf, wd, ema, data, hyper, alpha, eps, with_momentum, clip=None):
     """RMSProp + EMA with {lr, lr_bias, momentum, ema_decay} from the device tensor `hyper` (fp32[8], rmsprop_hyper)."""
-    PARAM_EPOCH[0] += 1
     _launch('rmsprop_ema_step_dev', 'mgdt_rmsprop_ema_step_dev', ptr(p), ptr(g), ptr(sq), ptr(buf), ptr(wd), p.numel(), ptr(ema), data.numel(), ptr(hyper),
-            float(alpha), float(eps), int(with_momentum), ptr(clip), stream())
+            float(alpha), float(eps), int(with_momentum), ptr(clip), _step_stream())
 
 
 # ------------------------------------------------------------------ image classification (csrc/classify.hip)

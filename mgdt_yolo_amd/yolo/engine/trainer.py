@@ -8,6 +8,7 @@ all-reduced in layer-ordered buckets while the earlier layers are still running 
 `accumulate` batches: clip(10) + SGD(Nesterov, the reference's three parameter groups) + EMA on the flat parameter buffer.
 `optimizer=` selects Adam / AdamW / RMSProp instead of SGD, or 'auto' (the reference's default, build_optimizer trainer.py:635-639).
 """
+import collections
 import math
 
 import numpy as np
@@ -49,6 +50,52 @@ def resolve_optimizer(name, nc, iterations, lr0, momentum, warmup_bias_lr):
     if name not in OPTIMIZERS:
         raise NotImplementedError(f"Optimizer '{name}' not found in list of available optimizers [Adam, AdamW, NAdam, RAdam, RMSProp, SGD, auto].")
     return name, lr0, momentum, warmup_bias_lr
+
+
+# One record per optimizer family: everything DetectionTrainer has to know about it.
+#   second_moment   it needs state.second_moment (Adam's exp_avg_sq, RMSProp's square_avg)
+#   warmed          its groups have a 'momentum' key, which the warm-up moves (trainer.py:325); Adam's beta1 never moves
+#   has_step        its state entries carry 'step'; without one a loaded buffer is marked by _loaded_momentum instead
+#   shared_step     the step count enters the update (bias corrections), so a loaded state must hold one count for all parameters
+#   state_keys(mom), torch_cls, torch_kwargs(mom)    the state entries and the torch optimizer of optimizer_state_dict
+#   hyper(tr, d)    the device vector of a captured step as Python floats, d the EMA decay
+#   eager(tr, st, p, clip) / captured(tr, st, p, clip, hyper)    the step kernel on the flat buffers st = tr.state, p the parameters' part of
+#                   st.data: with the scalars of `tr` (ops.ema_update follows), or with those and the EMA decay read from `hyper` at replay
+Family = collections.namedtuple('Family', 'second_moment warmed has_step shared_step state_keys torch_cls torch_kwargs hyper eager captured')
+
+
+def _adam(torch_cls, decoupled):            # every optimizer step is an EMA update, so Adam's 1-based step is st.steps + 1 (+ a loaded count)
+    return Family(
+        second_moment=True, warmed=False, has_step=True, shared_step=True, state_keys=lambda mom: ('exp_avg', 'exp_avg_sq'),
+        torch_cls=torch_cls, torch_kwargs=lambda mom: dict(betas=(mom, ADAM_BETA2), weight_decay=0.0),
+        hyper=lambda tr, d: ops.adam_hyper(tr.lr, tr.lr_bias, tr.mom, ADAM_BETA2, tr.state.steps + tr.opt_step_offset + 1, d),
+        eager=lambda tr, st, p, clip: ops.adam_step(p, st.grad, st.momentum_buf, st.second_moment, st.wd, tr.lr, tr.mom, ADAM_BETA2, OPT_EPS,
+                                                    st.steps + tr.opt_step_offset + 1, decoupled, clip, lr_bias=tr.lr_bias),
+        captured=lambda tr, st, p, clip, hyper: ops.adam_ema_step_dev(p, st.grad, st.momentum_buf, st.second_moment, st.wd, st.ema, st.data, hyper,
+                                                                      ADAM_BETA2, OPT_EPS, decoupled, clip))
+
+
+FAMILIES = {
+    # `first` (the buffer becomes g') on the first step unless a loaded buffer is continued; a captured step is never the first (_graph_ok)
+    'SGD': Family(
+        second_moment=False, warmed=True, has_step=False, shared_step=False, state_keys=lambda mom: ('momentum_buffer',),
+        torch_cls=torch.optim.SGD, torch_kwargs=lambda mom: dict(momentum=mom, nesterov=True),
+        hyper=lambda tr, d: ops.rmsprop_hyper(tr.lr, tr.lr_bias, tr.mom, d),        # SGD reads the first four
+        eager=lambda tr, st, p, clip: ops.sgd_step(p, st.grad, st.momentum_buf, st.wd, tr.lr, tr.mom, True,
+                                                   st.steps == 0 and not tr._loaded_momentum, clip, lr_bias=tr.lr_bias),
+        captured=lambda tr, st, p, clip, hyper: ops.sgd_ema_step_dev(p, st.grad, st.momentum_buf, st.wd, st.ema, st.data, hyper, True, False, clip)),
+    # torch tests momentum > 0 every step; the momentum / no-momentum kernel of a captured step is fixed at capture: see _graph_step
+    'RMSProp': Family(
+        second_moment=True, warmed=True, has_step=True, shared_step=False,
+        state_keys=lambda mom: ('square_avg', 'momentum_buffer') if mom > 0 else ('square_avg',),
+        torch_cls=torch.optim.RMSprop, torch_kwargs=lambda mom: dict(momentum=mom), hyper=lambda tr, d: ops.rmsprop_hyper(tr.lr, tr.lr_bias, tr.mom, d),
+        eager=lambda tr, st, p, clip: ops.rmsprop_step(p, st.grad, st.second_moment, st.momentum_buf, st.wd, tr.lr, RMS_ALPHA, OPT_EPS, tr.mom,
+                                                       clip, lr_bias=tr.lr_bias),
+        captured=lambda tr, st, p, clip, hyper: ops.rmsprop_ema_step_dev(p, st.grad, st.second_moment, st.momentum_buf, st.wd, st.ema, st.data, hyper,
+                                                                         RMS_ALPHA, OPT_EPS, tr.mom > 0, clip)),
+    'Adam': _adam(torch.optim.Adam, False),
+    'AdamW': _adam(torch.optim.AdamW, True),
+}
 
 
 class FlatState:
@@ -150,6 +197,7 @@ class DetectionTrainer:
                  batch_size=None, nb=None, epochs=100, nbs=64, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, overlap=True, amp=False,
                  graph=False, graph_split=None, optimizer='SGD', iterations=None, cos_lr=False):
         self.optimizer, lr0, self.opt_momentum, warmup_bias_lr = resolve_optimizer(optimizer, self._nc(model), iterations, lr0, momentum, warmup_bias_lr)
+        self.family = FAMILIES[self.optimizer]
         self.iterations, self.cos_lr = iterations, bool(cos_lr)
         self.model = model.train()
         # amp: the reference trains under autocast (trainer.py:223,329: fp16 + GradScaler); on this hardware the reduced-precision training path
@@ -168,7 +216,7 @@ class DetectionTrainer:
             wd = weight_decay * batch_size * self.accumulate / nbs                               # trainer.py:251
             self.nw = max(round(warmup_epochs * nb), 100)                                        # trainer.py:284
         self.weight_decay = wd                      # of the decayed group, scaled as trainer.py:251 does
-        self.state = FlatState(model, wd, second_moment=self.optimizer != 'SGD')
+        self.state = FlatState(model, wd, second_moment=self.family.second_moment)
         model._flat_state = self.state
         self.ema_decay, self.ema_tau = ema_decay, ema_tau
         self.ni, self.last_opt_step, self.lr, self.lr_bias, self.mom = 0, -1, lr0, lr0, self.opt_momentum
@@ -210,7 +258,7 @@ class DetectionTrainer:
         base = self.lr0 * self.lf(epoch) if self.batch_size is not None else self.lr0
         self.lr = self.lr_bias = base
         # groups with a 'momentum' key (SGD, RMSProp) are left at the warm-up's target, the constructor's momentum; Adam's beta1 never moves
-        warmed = self.optimizer in ('SGD', 'RMSProp') and self.nw >= 0
+        warmed = self.family.warmed and self.nw >= 0
         self.mom = self.momentum if warmed else self.opt_momentum
         if self.ni <= self.nw:
             xi = [0, self.nw]
@@ -226,23 +274,20 @@ class DetectionTrainer:
         img = batch['img'].to(self.state.data.device, non_blocking=True)
         return img if img.dtype == torch.uint8 else (img.to(torch.bfloat16) if self.amp else img.float())
 
-    def optimizer_step(self):
-        """unscale (no loss scaling: fp32 / bf16) -> clip_grad_norm_(10) -> SGD -> zero_grad (implicit: overwrite) -> EMA (trainer.py:462-470)."""
+    def optimizer_step(self, hyper=None):
+        """unscale (no loss scaling: fp32 / bf16) -> clip_grad_norm_(10) -> the family's step -> zero_grad (implicit: overwrite) -> EMA
+        (trainer.py:462-470) -> re-pack.  With `hyper`, inside a captured step: the scalars are those the device vector holds at replay, the EMA
+        runs in the step's launch and the host side (st.steps) is _graph_step's.  Returns the refreshed panels."""
         st = self.state
         clip = ops.grad_clip_coef(st.grad, 10.0)
         p = st.data[:st.n_param]
-        if self.optimizer == 'SGD':
-            ops.sgd_step(p, st.grad, st.momentum_buf, st.wd, self.lr, self.mom, True, st.steps == 0 and not self._loaded_momentum, clip,
-                         lr_bias=self.lr_bias)
-        elif self.optimizer == 'RMSProp':
-            ops.rmsprop_step(p, st.grad, st.second_moment, st.momentum_buf, st.wd, self.lr, RMS_ALPHA, OPT_EPS, self.mom, clip, lr_bias=self.lr_bias)
-        else:                                       # every optimizer step is an EMA update, so Adam's step count is st.steps
-            ops.adam_step(p, st.grad, st.momentum_buf, st.second_moment, st.wd, self.lr, self.mom, ADAM_BETA2, OPT_EPS,
-                          st.steps + self.opt_step_offset + 1, self.optimizer == 'AdamW', clip, lr_bias=self.lr_bias)
-        st.steps += 1
-        d = self.ema_decay * (1 - math.exp(-st.steps / self.ema_tau))      # torch_utils.py:342
-        ops.ema_update(st.ema, st.data, d)
-        ops.repack_all()                            # the packed panels of this step, refreshed for the next one in a few launches
+        if hyper is None:
+            self.family.eager(self, st, p, clip)
+            st.steps += 1
+            ops.ema_update(st.ema, st.data, self.ema_decay * (1 - math.exp(-st.steps / self.ema_tau)))      # torch_utils.py:342
+        else:
+            self.family.captured(self, st, p, clip, hyper)
+        return ops.repack_all()                     # the packed panels of this step, refreshed for the next one in a few launches
 
     # ---- optimizer state in torch's layout -------------------------------------------------------------------------------------------
     def _reference_groups(self):
@@ -252,25 +297,16 @@ class DetectionTrainer:
         names = [[n for n, g in groups.items() if g == k] for k in (2, 0, 1)]
         return names                               # frozen parameters (dfl.conv.weight) are members too; they never get a state entry
 
-    def _state_keys(self):
-        if self.optimizer in ('Adam', 'AdamW'):
-            return ('exp_avg', 'exp_avg_sq')
-        if self.optimizer == 'RMSProp':
-            return ('square_avg', 'momentum_buffer') if self.mom > 0 else ('square_avg',)
-        return ('momentum_buffer',)
-
     def optimizer_state_dict(self):
         """The optimizer state as torch's Optimizer.state_dict() of the reference's optimizer would hold it (what the reference saves in a
         checkpoint's 'optimizer' entry): per-parameter `step` / `exp_avg` / `exp_avg_sq` (Adam, AdamW), `momentum_buffer` (SGD) or `step` /
         `square_avg` [/ `momentum_buffer`] (RMSProp), indexed through the three groups.  Before the first step the state is empty, as torch's."""
         st, names = self.state, self._reference_groups()
         shapes = {n: p.shape for n, p in self.model.named_parameters()}
-        cls = {'SGD': torch.optim.SGD, 'Adam': torch.optim.Adam, 'AdamW': torch.optim.AdamW, 'RMSProp': torch.optim.RMSprop}[self.optimizer]
-        kw = dict(momentum=self.mom, nesterov=True) if self.optimizer == 'SGD' else dict(momentum=self.mom) if self.optimizer == 'RMSProp' \
-            else dict(betas=(self.mom, ADAM_BETA2), weight_decay=0.0)
         # the hyper-parameter keys of the installed torch, from an optimizer over empty stand-ins
-        opt = cls([{'params': [nn.Parameter(torch.empty(0)) for _ in ns], 'weight_decay': w, 'lr': lr, 'initial_lr': self.lr0}
-                   for ns, w, lr in zip(names, (0.0, self.weight_decay, 0.0), (self.lr_bias, self.lr, self.lr))], lr=self.lr0, **kw)
+        fam = self.family
+        opt = fam.torch_cls([{'params': [nn.Parameter(torch.empty(0)) for _ in ns], 'weight_decay': w, 'lr': lr, 'initial_lr': self.lr0}
+                             for ns, w, lr in zip(names, (0.0, self.weight_decay, 0.0), (self.lr_bias, self.lr, self.lr))], lr=self.lr0, **fam.torch_kwargs(self.mom))
         groups = opt.state_dict()['param_groups']
         state, steps = {}, st.steps + self.opt_step_offset
         if steps > 0 or self._loaded_momentum:
@@ -279,8 +315,8 @@ class DetectionTrainer:
                 if n not in st.offsets:
                     continue
                 off, k = st.offsets[n]
-                e = {} if self.optimizer == 'SGD' else {'step': torch.tensor(float(steps))}
-                e.update({key: bufs[key][off:off + k].view(shapes[n]).clone() for key in self._state_keys()})
+                e = {'step': torch.tensor(float(steps))} if fam.has_step else {}
+                e.update({key: bufs[key][off:off + k].view(shapes[n]).clone() for key in fam.state_keys(self.mom)})
                 state[i] = e
         return {'state': state, 'param_groups': groups}
 
@@ -295,7 +331,7 @@ class DetectionTrainer:
         if [len(g['params']) for g in groups] != [len(ns) for ns in names]:
             raise ValueError(f"optimizer state has groups of {[len(g['params']) for g in groups]} parameters, the model {[len(ns) for ns in names]}")
         idx = [i for g in groups for i in g['params']]
-        state, keys = sd['state'], self._state_keys()
+        state, keys = sd['state'], self.family.state_keys(self.mom)
         known = {'exp_avg', 'exp_avg_sq', 'square_avg', 'momentum_buffer', 'max_exp_avg_sq', 'grad_avg'}
         shapes = {n: p.shape for n, p in self.model.named_parameters()}
         bufs = {'exp_avg': st.momentum_buf, 'momentum_buffer': st.momentum_buf, 'exp_avg_sq': st.second_moment, 'square_avg': st.second_moment}
@@ -316,7 +352,7 @@ class DetectionTrainer:
                     raise ValueError(f'{k} of parameter {i} ({n}) has shape {tuple(e[k].shape)}, the parameter {tuple(shapes[n])}')
             if 'step' in e:
                 steps.add(int(e['step']))
-        if self.optimizer in ('Adam', 'AdamW') and state and len(steps) != 1:
+        if self.family.shared_step and state and len(steps) != 1:
             raise ValueError(f'Adam state needs one step count for all parameters, got {sorted(steps)}')
         st.momentum_buf.zero_()
         if st.second_moment is not None:
@@ -327,8 +363,8 @@ class DetectionTrainer:
                 off, k = st.offsets[n]
                 for key in keys:
                     bufs[key][off:off + k].copy_(e[key].reshape(-1))
-        self._loaded_momentum = bool(state) and self.optimizer == 'SGD'
-        self.opt_step_offset = (max(steps) if steps else 0) - st.steps if self.optimizer != 'SGD' else 0
+        self._loaded_momentum = bool(state) and not self.family.has_step
+        self.opt_step_offset = (max(steps) if steps else 0) - st.steps if self.family.has_step else 0
 
     # ---- captured step -------------------------------------------------------------------------------------------------------------
     def _graph_ok(self):
@@ -337,7 +373,7 @@ class DetectionTrainer:
 
     def _graph_body(self, part=None):
         """part None: the whole step; 'grad': forward + loss + reverse pass; 'update': clip + SGD + EMA + re-pack."""
-        st, S = self.state, self._static
+        S = self._static
         if part != 'update':
             feats = self.model._predict_once(S['img'])
             ls = ops.detect_loss_fwd(list(feats), self.crit.stride_list, self.crit.reg_max, self.crit.nc, S['gt'], 0,
@@ -347,17 +383,7 @@ class DetectionTrainer:
             S['out5'] = ls.out5
             if part == 'grad':
                 return
-        clip = ops.grad_clip_coef(st.grad, 10.0)
-        p = st.data[:st.n_param]
-        if self.optimizer == 'SGD':
-            ops.sgd_ema_step_dev(p, st.grad, st.momentum_buf, st.wd, st.ema, st.data, S['hyper'], True, False, clip)
-        elif self.optimizer == 'RMSProp':           # the momentum / no-momentum kernel is fixed at capture: see _graph_step
-            ops.rmsprop_ema_step_dev(p, st.grad, st.second_moment, st.momentum_buf, st.wd, st.ema, st.data, S['hyper'], RMS_ALPHA, OPT_EPS,
-                                     self.mom > 0, clip)
-        else:
-            ops.adam_ema_step_dev(p, st.grad, st.momentum_buf, st.second_moment, st.wd, st.ema, st.data, S['hyper'], ADAM_BETA2, OPT_EPS,
-                                  self.optimizer == 'AdamW', clip)
-        S['panels'] = ops.repack_all()              # next step's packed weights, all convolutions in a few launches
+        S['panels'] = self.optimizer_step(S['hyper'])      # next step's packed weights, all convolutions in a few launches
 
     def _graph_step(self, batch):
         st = self.state
@@ -376,8 +402,9 @@ class DetectionTrainer:
         # new ones and freeing these), and if anything else moved the weights without refreshing them the graphs are dropped.
         if any(not ops.pack_is_current(o) for _, _, panels in self._graphs.values() for o in panels):
             self._graphs, self._pool = {}, None
-        if self.optimizer == 'RMSProp' and S.setdefault('rms_mom', self.mom > 0) != (self.mom > 0):      # torch tests momentum > 0 every step
-            self._graphs, self._pool, S['rms_mom'] = {}, None, self.mom > 0
+        keys = self.family.state_keys(self.mom)     # the buffers the captured kernel touches: RMSProp's change when momentum > 0 flips
+        if S.setdefault('state_keys', keys) != keys:
+            self._graphs, self._pool, S['state_keys'] = {}, None, keys
         if nmax not in S['gts']:
             S['gts'][nmax] = torch.zeros(b, nmax, 5, dtype=torch.float32, device=img.device)
         S['gt'] = S['gts'][nmax]
@@ -386,10 +413,7 @@ class DetectionTrainer:
         if gt.shape[1]:
             S['gt'][:, :gt.shape[1]].copy_(gt)
         d = self.ema_decay * (1 - math.exp(-(st.steps + 1) / self.ema_tau))      # torch_utils.py:342 with updates = steps + 1
-        if self.optimizer in ('Adam', 'AdamW'):    # bias corrections of optimizer step st.steps + 1, in Python floats as torch computes them
-            hyper = ops.adam_hyper(self.lr, self.lr_bias, self.mom, ADAM_BETA2, st.steps + self.opt_step_offset + 1, d)
-        else:                                       # SGD reads the first four
-            hyper = ops.rmsprop_hyper(self.lr, self.lr_bias, self.mom, d)
+        hyper = self.family.hyper(self, d)
         S['hyper'].copy_(torch.tensor(hyper, dtype=torch.float32), non_blocking=True)
         S['calls'].fill_(int(self.crit.epoch))
         captured = nmax not in self._graphs

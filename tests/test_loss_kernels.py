@@ -36,6 +36,7 @@ import torch
 import inputs as GI
 from kernel_ref import (BF16, DEV, F32, _check, _exact, _gen, _nhwc, _rand, f32r, loss_census, loss_gt_random, loss_maps, loss_margins, loss_reference,
                         ref_clip, ref_ema, ref_sgd)
+from optim_ref import ref_adam, ref_rmsprop
 
 gpu = pytest.mark.gpu
 DTS = [pytest.param(F32, id='f32'), pytest.param(BF16, id='bf16')]
@@ -362,7 +363,7 @@ def test_ema_update(n, decay):
 @pytest.mark.parametrize('with_ema', [True, False], ids=['ema', 'noema'])
 @pytest.mark.parametrize('nesterov', [0, 1])
 @pytest.mark.parametrize('first', [0, 1])
-@pytest.mark.parametrize('n_param', [257, 8192 * 256 + 5])
+@pytest.mark.parametrize('n_param', [257, 259, 8192 * 256 + 5])          # % 4 == 1, 3, 1: the quad that straddles n_param is cut both ways
 def test_sgd_ema_step_dev(n_param, first, nesterov, with_ema):
     """mgdt_sgd_ema_step_dev (the kernel of the captured step) over three steps with `hyper` rewritten on the device between them and the clip
     coefficient present, absent, present: p, buf, ema against float64; the 1000-element tail [n_param, n_total) receives EMA only and keeps its p
@@ -398,3 +399,119 @@ def test_sgd_ema_step_dev(n_param, first, nesterov, with_ema):
         if with_ema:
             _check(d_ema, ema, F32, what + ' ema')
             _exact(d_ema, s_ema.cpu(), what + ' ema vs ema_update')
+
+
+# The flat kernel takes 16-byte accesses only when every array it is given is 16-byte aligned; otherwise every element goes through the scalar
+# path, which evaluates the same element function.  n_param % 4 == 3 and n_total % 4 == 0: a straddling quad and no tail when aligned.
+N_PARAM_Q, N_TOTAL_Q, SENTINEL = 259, 268, 12345.0
+
+
+def _place(t, shifted):
+    """Device copy of the CPU tensor t as a view into a SENTINEL-filled allocation with slack on both sides: 16-byte aligned, or with `shifted`
+    starting one float into it.  Returns (view, allocation, offset of the view)."""
+    big = torch.full((t.numel() + 8,), SENTINEL, dtype=F32, device=DEV)
+    off = 1 if shifted else 4
+    view = big[off:off + t.numel()]
+    view.copy_(t.float())
+    assert view.data_ptr() % 16 == (4 if shifted else 0)
+    return view, big, off
+
+
+def _flat_case(kind, gen):
+    """Inputs of one step of `kind` ('sgd', 'adam', 'rmsprop', 'ema'), |g| >= 0.05 and v a square of such a magnitude so that the float64 bound
+    holds for the divisions; a function that runs the step on placed arrays; which arrays it writes; and the float64 results."""
+    from mgdt_yolo_amd import ops
+    n_param, n_total = N_PARAM_Q, N_TOTAL_Q
+    lr, lrb, mom, dec, coef, beta2, alpha, eps, step = LR, LR_BIAS, 0.9, 0.5, 0.37, 0.999, 0.99, 1e-8, 4
+    a = dict(data=_rand(gen, n_total), ema=_rand(gen, n_total))
+    if kind == 'ema':
+        return a, lambda V: ops.ema_update(V['ema'], V['data'], dec), dict(data=a['data'], ema=ref_ema(a['ema'], a['data'], dec))
+    r = _rand(gen, n_param)
+    a.update(g=(torch.where(r < 0, -1.0, 1.0) * (0.05 + r.abs())).float().double(), m=_rand(gen, n_param, scale=0.3), wd=_wd(n_param).double())
+    p, c, clip = a['data'][:n_param], f32r(coef), _clip2(coef)
+    if kind == 'sgd':
+        hyper = torch.tensor([lr, lrb, mom, dec], dtype=F32, device=DEV)
+        pn, m = ref_sgd(p, a['g'], a['m'], a['wd'], lr, lrb, mom, 1, 0, c)
+        ref = dict(m=m)
+
+        def run(V):
+            ops.sgd_ema_step_dev(V['data'][:n_param], V['g'], V['m'], V['wd'], V['ema'], V['data'], hyper, 1, 0, clip=clip)
+    else:
+        a['v'] = ((0.05 + _rand(gen, n_param).abs()) ** 2).float().double()
+        if kind == 'adam':
+            hyper = torch.tensor(ops.adam_hyper(lr, lrb, mom, beta2, step, dec), dtype=F32, device=DEV)
+            pn, m, v = ref_adam(p, a['g'], a['m'], a['v'], a['wd'], lr, lrb, mom, beta2, eps, step, 1, c)
+
+            def run(V):
+                ops.adam_ema_step_dev(V['data'][:n_param], V['g'], V['m'], V['v'], V['wd'], V['ema'], V['data'], hyper, beta2, eps, 1, clip=clip)
+        else:
+            hyper = torch.tensor(ops.rmsprop_hyper(lr, lrb, mom, dec), dtype=F32, device=DEV)
+            pn, v, m = ref_rmsprop(p, a['g'], a['v'], a['m'], a['wd'], lr, lrb, alpha, eps, mom, c)
+
+            def run(V):
+                ops.rmsprop_ema_step_dev(V['data'][:n_param], V['g'], V['v'], V['m'], V['wd'], V['ema'], V['data'], hyper, alpha, eps, True, clip=clip)
+        ref = dict(m=m, v=v)
+    ref['data'] = torch.cat([pn, a['data'][n_param:]])
+    ref['ema'] = ref_ema(a['ema'], ref['data'], dec)
+    return a, run, ref
+
+
+@gpu
+@pytest.mark.parametrize('kind', ['sgd', 'adam', 'rmsprop', 'ema'])
+def test_unaligned_arrays_take_the_scalar_path(kind):
+    """One step of mgdt_sgd_ema_step_dev / mgdt_adam_ema_step_dev / mgdt_rmsprop_ema_step_dev (with momentum) / mgdt_ema_update from the same
+    values three times: every array 16-byte aligned; one array (wd; p for the EMA) starting one float into its allocation; every array so.  The
+    two scalar-path runs give the bits of the aligned run, all three stay inside the float64 bound, and the slack around every view is left
+    alone."""
+    a, run, ref = _flat_case(kind, _gen('flat-unaligned', kind))
+    one = 'data' if kind == 'ema' else 'wd'
+    aligned = None
+    for shifted in ((), (one,), tuple(a)):
+        placed = {k: _place(t, k in shifted) for k, t in a.items()}
+        run({k: view for k, (view, _, _) in placed.items()})
+        for k, (view, big, off) in placed.items():
+            slack = torch.cat([big[:off], big[off + view.numel():]]).cpu()
+            assert slack.numel() == 8 and (slack == SENTINEL).all(), (kind, shifted, k, 'slack written')
+        got = {k: placed[k][0].cpu() for k in ref}
+        for k in ref:
+            _check(got[k], ref[k], F32, f'{kind} shifted={shifted} {k}')
+            if aligned is not None:
+                _exact(got[k], aligned[k], f'{kind} shifted={shifted} {k} vs aligned')
+        aligned = aligned or got
+    _exact(got['data'][N_PARAM_Q:], a['data'][N_PARAM_Q:], kind + ' tail of p')
+
+
+@gpu
+def test_sgd_ema_step_dev_reads_four_hyper_slots():
+    """`hyper` of mgdt_sgd_ema_step_dev is fp32[4]: with an 8-float vector whose slots 4..7 are NaN the result is the same bit for bit."""
+    a, _, ref = _flat_case('sgd', _gen('sgd-hyper4'))
+    from mgdt_yolo_amd import ops
+    out = []
+    for extra in ([], [float('nan')] * 4):
+        V = {k: _d(t) for k, t in a.items()}
+        hyper = torch.tensor([LR, LR_BIAS, 0.9, 0.5] + extra, dtype=F32, device=DEV)
+        ops.sgd_ema_step_dev(V['data'][:N_PARAM_Q], V['g'], V['m'], V['wd'], V['ema'], V['data'], hyper, 1, 0, clip=_clip2(0.37))
+        out.append({k: V[k].cpu() for k in ref})
+    for k in ref:
+        _check(out[0][k], ref[k], F32, f'hyper4 {k}')
+        _exact(out[1][k], out[0][k], f'hyper8 with NaN in 4..7, {k}')
+
+
+@gpu
+@pytest.mark.parametrize('form', ['eager', 'dev'])
+def test_sgd_first_step_ignores_a_nan_buffer(form):
+    """first = 1: the momentum buffer becomes g' whatever it held - here NaN in every element, vector path and straddling quad alike."""
+    from mgdt_yolo_amd import ops
+    n = N_PARAM_Q
+    gen = _gen('sgd-first-nan', form)
+    p, g, wd = _rand(gen, n), _rand(gen, n), _wd(n)
+    dp, dbuf = _d(p), torch.full((n,), float('nan'), dtype=F32, device=DEV)
+    if form == 'eager':
+        ops.sgd_step(dp, _d(g), dbuf, _d(wd), LR, MOM, 1, 1, clip=_clip2(0.37), lr_bias=LR_BIAS)
+    else:
+        hyper = torch.tensor([LR, LR_BIAS, MOM, 0.5], dtype=F32, device=DEV)
+        ops.sgd_ema_step_dev(dp, _d(g), dbuf, _d(wd), None, dp, hyper, 1, 1, clip=_clip2(0.37))
+    rp, rbuf = ref_sgd(p, g, torch.zeros(n, dtype=torch.float64), wd, LR, LR_BIAS, MOM, 1, 1, f32r(0.37))
+    assert torch.isfinite(dp).all() and torch.isfinite(dbuf).all()
+    _check(dbuf, rbuf, F32, f'first with NaN buffer, {form}: buf')
+    _check(dp, rp, F32, f'first with NaN buffer, {form}: p')
