@@ -52,7 +52,8 @@ int mgdt_conv_pack(const float* w_oihw, const float* conv_bias, const float* bn_
 int mgdt_conv_pack_dgrad(const float* w_oihw, int cin, int cout, int k, int phase, int dtype, void* packed_out, float* bias_out, mgdt_stream s);
 /* Many packs in a few launches (a training step re-packs every convolution after the optimizer moved the weights; the reference has no counterpart:
  * ATen convolutions read nn.Conv2d.weight in place).  One descriptor = the arguments of one mgdt_conv_pack (mode 0) or mgdt_conv_pack_dgrad
- * (mode 1 = stride-1 data gradient, mode 2 + phase = stride-2 phase) call; cin / cout are those of the ORIGINAL convolution. */
+ * (mode 1 = stride-1 data gradient, mode 2 + phase = stride-2 phase) or mgdt_conv_pack_stem6 (mode 5 + cin, k = 3, w = the 6x6 weight) call; cin / cout
+ * are those of the ORIGINAL convolution. */
 typedef struct mgdt_pack_desc {
   const float* w; const float* conv_bias; const float* bn_gamma; const float* bn_beta; const float* bn_mean; const float* bn_var;
   float bn_eps; int32_t cin, cout, k, dtype, mode;
@@ -200,7 +201,10 @@ int mgdt_scale_img_fwd(const mgdt_view* x, int x_dtype, int flip, int hs, int ws
  *   non-NULL; feed it to mgdt_spr_attn_scale_fwd(pool, slots, tiles_x, tiles_y, ...).  mode 0 needs even h, w and picks an even
  *   tile grid (every tile lies inside one adaptive_avg_pool2d(2) bin).
  *   mgdt_csp_block_supported: 1 when covered (bf16; wd in {8,16,32,64}; n in {1,2}; mode 0: cin == 4wd; mode 1: cin == 2wd,
- *   wd >= 16); otherwise callers keep the per-conv launches. */
+ *   wd >= 16); otherwise callers keep the per-conv launches.
+ *   mode 2 (C3, nn/modules/block.py:434-447): x = [a | b] = the output of ONE 1x1 launch over cat(cv1, cv2) (cin == 2wd, wd in {16,32,64}, 16-byte
+ *   aligned pixels), front NULL, mid[2*nbtl] = per bottleneck the 1x1 then the 3x3 panel (wd -> wd), back = cv3 over [m_n(a) | b] (K = 2wd, cout % 4 == 0,
+ *   cout <= 512), pool NULL; halo n, tiles must divide the map (mgdt_csp_block_tiles == 0: none, e.g. a 37-row map). */
 int mgdt_csp_block_supported(int mode, int cin, int cout, int wd, int nbtl, int h, int w, int dtype);
 int mgdt_csp_block_tiles(int mode, int n, int cin, int cout, int wd, int nbtl, int h, int w, int* geom8);
 int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* front, const float* front_bias, const void* const* mid,
@@ -310,6 +314,23 @@ int mgdt_copy_fwd(const mgdt_view* x, int x_dtype, const mgdt_view* y, int y_dty
 /* The 1-3 channel image (any strides; MGDT_U8 is divided by 255: detect/train.py:64) as a 4-channel NHWC map whose remaining channels are zero - the input the
  * stem's weight-gradient kernel reads.  Writes all four channels of y. */
 int mgdt_image_pad4_fwd(const mgdt_view* x, int x_dtype, const mgdt_view* y, int y_dtype, mgdt_stream s); /* cat / layout / cast */
+
+/* ---- the 6x6 / stride 2 / padding 2 stem of the YOLOv5 graphs (models/v5/yolov5.yaml row 0) as space-to-depth + a 3x3 / stride 1 convolution:
+ *   S[b, (dy*2+dx)*C + ci, i, j] = x[b, ci, 2i+dy, 2j+dx],  W3[co, (dy*2+dx)*C + ci, a, b] = W6[co, ci, 2a+dy, 2b+dx],
+ *   conv2d(x, W6, stride 2, pad 2) == conv2d(S, W3, stride 1, pad 1)  (exact).
+ * mgdt_space_to_depth2_fwd: x = N x C x H x W image, C <= 4, H and W even, any strides, x_dtype MGDT_F32 / MGDT_BF16 / MGDT_U8 (u8 divided by 255 like
+ *   the other stem kernels); y = N x H/2 x W/2 x Cp NHWC, y_dtype MGDT_F32 / MGDT_BF16 (a bf16 image goes to bf16 only), 16-byte aligned, with
+ *   Cp = mgdt_space_to_depth2_channels(C, y_dtype) = 4C rounded up to whole 16-byte stores (C = 3: 12 fp32, 16 bf16); channels 4C.. are written zero.
+ * mgdt_stem6_wgrad_unpack: dw6 (fp32 [cout][cin][6][6], overwritten) <- dw3 (fp32 [cout][cp][3][3], cp >= 4 cin): the FINAL sums of the 3x3
+ *   weight-gradient kernel over S, permuted back (rows 4 cin.. of dw3 - the pad channels - are not read).
+ * mgdt_conv_pack_stem6: the panel of that 3x3 convolution (+ folded bias, as mgdt_conv_pack) read straight from the live 6x6 weight w6 fp32 [cout][c6][6][6],
+ *   zero rows for the pad channels; sized by mgdt_conv_packed_bytes(mgdt_space_to_depth2_channels(c6, dtype), cout, 3, dtype); refreshed in place by
+ *   mgdt_conv_pack_batch descriptors of mode 5 + c6. */
+int mgdt_space_to_depth2_channels(int c, int y_dtype);
+int mgdt_conv_pack_stem6(const float* w6, const float* conv_bias, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
+                         float bn_eps, int c6, int cout, int dtype, void* packed_out, float* bias_out, mgdt_stream s);
+int mgdt_space_to_depth2_fwd(const mgdt_view* x, int x_dtype, const mgdt_view* y, int y_dtype, mgdt_stream s);
+int mgdt_stem6_wgrad_unpack(const float* dw3, int cout, int cin, int cp, float* dw6, mgdt_stream s);
 
 /* ---- ConvNeXtV2 block pieces (nn/modules/convnextv2.py:48-77, nn/modules/utils.py:145-182) -------------
  * dwln: y = LayerNorm_c(dwconv7x7(x) + b) * ln_w + ln_b   (eps 1e-6), dw_w is [49][c] fp32.

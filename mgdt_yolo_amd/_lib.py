@@ -69,6 +69,10 @@ PROTOTYPES = {
     'mgdt_nearest_fwd': (_i, [VP, VP, _i, _vp]),
     'mgdt_copy_fwd': (_i, [VP, _i, VP, _i, _vp]),
     'mgdt_image_pad4_fwd': (_i, [VP, _i, VP, _i, _vp]),
+    'mgdt_space_to_depth2_channels': (_i, [_i, _i]),
+    'mgdt_space_to_depth2_fwd': (_i, [VP, _i, VP, _i, _vp]),
+    'mgdt_conv_pack_stem6': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp]),
+    'mgdt_stem6_wgrad_unpack': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'mgdt_dwconv7_ln_fwd': (_i, [VP, _vp, _vp, _vp, _vp, _f, VP, _i, _vp]),
     'mgdt_cnx_mlp_packed_bytes': (_sz, [_i, _i]),
     'mgdt_cnx_mlp_pack': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),

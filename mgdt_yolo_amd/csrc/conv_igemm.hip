@@ -22,6 +22,13 @@
 // The BN fold of fold_kernel runs inline (same expressions, same bits): one launch per convolution instead of two - in training every
 // convolution is re-packed after every optimizer step.  FoldArgs.g == nullptr: no BN (scale 1); bias_out == nullptr: the caller folds.
 struct FoldArgs { const float *cb, *g, *b, *mu, *var; float eps; int cout_real, cpad; float* bias_out; };
+// `dgrad` = 5 + c6 (6..9): the panel of the 3x3 / stride 1 form of a 6x6 / stride 2 / padding 2 stem with c6 <= 4 input channels, read straight from
+// the 6x6 weight w6[cout][c6][6][6]: channel cs = (dy*2+dx)*c6 + ci of the space-to-depth map (stem_s2d.hip), tap (a, b) <- w6[cout][ci][2a+dy][2b+dx];
+// the map's pad channels (cs >= 4 c6) get zero rows.
+__device__ __forceinline__ float stem6_weight(const float* __restrict__ w6, int c6, int cout, int cs, int tap) {
+  const int q = cs / c6, ci = cs - q * c6;
+  return q < 4 ? w6[(((long)cout * c6 + ci) * 6 + 2 * (tap / 3) + (q >> 1)) * 6 + 2 * (tap % 3) + (q & 1)] : 0.f;
+}
 template <typename T>
 __global__ void pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, int Cin, int Cout, int KS,
                             int CP, int nchunks, int NTtot, T* __restrict__ out, int dgrad = 0, FoldArgs fa = FoldArgs{}) {
@@ -51,7 +58,7 @@ __global__ void pack_kernel(const float* __restrict__ w, const float* __restrict
     int r = lane & 15, g = lane >> 4;
     int p = kc * 4 + g;
     int tap = p / CP, cp = p % CP;
-    if (dgrad >= 2) {                                  // compact K: list index -> the phase's tap (rows {1} / {1,2}, columns likewise)
+    if (dgrad >= 2 && dgrad < 6) {                     // compact K: list index -> the phase's tap (rows {1} / {1,2}, columns likewise)
       const int nc_ = 1 + ((dgrad - 2) & 1), nr_ = 1 + ((dgrad - 2) >> 1);
       tap = tap < nr_ * nc_ ? (1 + tap / nc_) * 3 + (1 + tap % nc_) : 99;
     }
@@ -59,6 +66,7 @@ __global__ void pack_kernel(const float* __restrict__ w, const float* __restrict
     float v = 0.f;
     if (tap < KS * KS && cin < Cin && cout < Cout) {
       if (dgrad == 1) v = w[(((long)cin * Cout + cout) * KS + (KS - 1 - tap / KS)) * KS + (KS - 1 - tap % KS)];   // original layout [cin=co][cout=ci][ky][kx]
+      else if (dgrad >= 6) v = stem6_weight(w, dgrad - 5, cout, cin, tap);
       else if (dgrad >= 2) {   // stride-2 phase (py, px) of a 3x3 conv: tap (dy', dx') of the dy grid carries w[ky = py + 1 - 2*dy'][kx = px + 1 - 2*dx'] when that exists
         const int py = (dgrad - 2) >> 1, px = (dgrad - 2) & 1;
         const int ky = py + 1 - 2 * (tap / KS - 1), kx = px + 1 - 2 * (tap % KS - 1);
@@ -135,6 +143,29 @@ extern "C" int mgdt_conv_pack(const float* w, const float* cb, const float* g, c
   const FoldArgs fa{cb, g, b, mu, var, eps, cout, cpad, bias_out};
   MGDT_DISPATCH_DTYPE(dtype, (pack_kernel<T><<<grid, 256, 0, st>>>(w, nullptr, cin, cout, k, CP, nchunks, NTtot, (T*)packed, 0, fa)));
   MGDT_CHECK_LAUNCH("conv_pack");
+  return MGDT_OK;
+}
+
+// channels of the space-to-depth map of a c6-channel image: 4 c6 rounded up to whole 16-byte pieces (== mgdt_space_to_depth2_channels)
+static inline int stem6_channels(int c6, int dtype) { const int pe = piece_elems(dtype); return (4 * c6 + pe - 1) / pe * pe; }
+
+// panel (+ folded bias) of the 3x3 form of the 6x6 / stride 2 / padding 2 stem w6[cout][c6][6][6] (see stem6_weight); used with
+// mgdt_conv2d_fwd(x = the space-to-depth map, k 3, stride 1).  Sized by mgdt_conv_packed_bytes(mgdt_space_to_depth2_channels(c6, dtype), cout, 3, dtype).
+extern "C" int mgdt_conv_pack_stem6(const float* w6, const float* cb, const float* g, const float* b, const float* mu, const float* var, float eps, int c6,
+                                    int cout, int dtype, void* packed, float* bias_out, mgdt_stream s) {
+  if (!w6 || !packed || !bias_out) MGDT_FAIL(MGDT_BAD_ARG, "conv_pack_stem6: null pointer");
+  if ((g != nullptr) != (b != nullptr) || (g != nullptr) != (mu != nullptr) || (g != nullptr) != (var != nullptr))
+    MGDT_FAIL(MGDT_BAD_ARG, "conv_pack_stem6: BN arguments must be all present or all NULL");
+  if (c6 < 1 || c6 > 4 || cout < 1 || (dtype != MGDT_F32 && dtype != MGDT_BF16)) MGDT_FAIL(MGDT_BAD_SHAPE, "conv_pack_stem6: c6 %d cout %d dtype %d", c6, cout, dtype);
+  int CP, nchunks, NTtot;
+  const int cin = stem6_channels(c6, dtype);
+  conv_geometry(cin, cout, 3, dtype, &CP, &nchunks, &NTtot);
+  hipStream_t st = (hipStream_t)s;
+  long total = (long)nchunks * NTtot * 64 * piece_elems(dtype);
+  int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  const FoldArgs fa{cb, g, b, mu, var, eps, cout, NTtot * 16, bias_out};
+  MGDT_DISPATCH_DTYPE(dtype, (pack_kernel<T><<<grid, 256, 0, st>>>(w6, nullptr, cin, cout, 3, CP, nchunks, NTtot, (T*)packed, 5 + c6, fa)));
+  MGDT_CHECK_LAUNCH("conv_pack_stem6");
   return MGDT_OK;
 }
 
@@ -285,7 +316,7 @@ __global__ void pack_batch_kernel(const PackJobs jobs) {
     int r = lane & 15, g = lane >> 4;
     int p = kc * 4 + g;
     int tap = p / CP, cp = p % CP;
-    if (dgrad >= 2) {                                  // compact K: list index -> the phase's tap (rows {1} / {1,2}, columns likewise)
+    if (dgrad >= 2 && dgrad < 6) {                     // compact K: list index -> the phase's tap (rows {1} / {1,2}, columns likewise)
       const int nc_ = 1 + ((dgrad - 2) & 1), nr_ = 1 + ((dgrad - 2) >> 1);
       tap = tap < nr_ * nc_ ? (1 + tap / nc_) * 3 + (1 + tap % nc_) : 99;
     }
@@ -293,6 +324,7 @@ __global__ void pack_batch_kernel(const PackJobs jobs) {
     float v = 0.f;
     if (tap < KS * KS && cin < Cin && cout < Cout) {
       if (dgrad == 1) v = w[(((long)cin * Cout + cout) * KS + (KS - 1 - tap / KS)) * KS + (KS - 1 - tap % KS)];
+      else if (dgrad >= 6) v = stem6_weight(w, dgrad - 5, cout, cin, tap);
       else if (dgrad >= 2) {
         const int py = (dgrad - 2) >> 1, px = (dgrad - 2) & 1;
         const int ky = py + 1 - 2 * (tap / KS - 1), kx = px + 1 - 2 * (tap % KS - 1);
@@ -322,12 +354,14 @@ extern "C" int mgdt_conv_pack_batch(const mgdt_pack_desc* d, int n, mgdt_stream 
       const mgdt_pack_desc& e = d[i];
       if (e.dtype != dtype) continue;
       if (!e.w || !e.packed || !e.bias_out) MGDT_FAIL(MGDT_BAD_ARG, "conv_pack_batch: descriptor %d has a null pointer", i);
-      if (e.mode < 0 || e.mode > 5 || (e.mode >= 2 && e.k != 3)) MGDT_FAIL(MGDT_BAD_SHAPE, "conv_pack_batch: descriptor %d mode %d", i, e.mode);
+      if (e.mode < 0 || e.mode > 9 || (e.mode >= 2 && e.k != 3) || (e.mode >= 6 && e.cin != e.mode - 5))
+        MGDT_FAIL(MGDT_BAD_SHAPE, "conv_pack_batch: descriptor %d mode %d", i, e.mode);
       PackJob& J = jobs.j[m++];
-      const int gi = e.mode == 0 ? e.cin : e.cout, go = e.mode == 0 ? e.cout : e.cin;      // the data-gradient conv maps cout -> cin channels
-      conv_geometry(gi, go, e.k, dtype, &J.CP, &J.nchunks, &J.NTtot, e.mode >= 2 ? phase_ntaps(e.mode) : 0);
+      const bool stem6 = e.mode >= 6, fwd = e.mode == 0 || stem6;                           // stem6 (mode 5 + cin): see mgdt_conv_pack_stem6
+      const int gi = stem6 ? stem6_channels(e.cin, dtype) : fwd ? e.cin : e.cout, go = fwd ? e.cout : e.cin;      // the data-gradient conv maps cout -> cin channels
+      conv_geometry(gi, go, e.k, dtype, &J.CP, &J.nchunks, &J.NTtot, (e.mode >= 2 && !stem6) ? phase_ntaps(e.mode) : 0);
       J.w = e.w; J.Cin = gi; J.Cout = go; J.KS = e.k; J.dgrad = e.mode; J.out = e.packed;
-      J.fa = e.mode == 0 ? FoldArgs{e.conv_bias, e.bn_gamma, e.bn_beta, e.bn_mean, e.bn_var, e.bn_eps, go, J.NTtot * 16, e.bias_out}
+      J.fa = fwd ? FoldArgs{e.conv_bias, e.bn_gamma, e.bn_beta, e.bn_mean, e.bn_var, e.bn_eps, go, J.NTtot * 16, e.bias_out}
                          : FoldArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, go, J.NTtot * 16, e.bias_out};
       if (m == PACK_BATCH) flush();
     }

@@ -533,8 +533,16 @@ static bool csp_geometry(int mode, int H, int W, int wd, int nbtl, int catC, siz
 static int csp_chain_nbk(int wd) { return wd >= 16 ? wd / 16 : 1; }
 static int csp_pool_gst(int cout) { const int nbo = (cout + 15) / 16; return (nbo < CSP_NW && CSP_NW % nbo == 0) ? CSP_NW / nbo : 1; }
 
+// mode 2 (CSP_C3, the C3 block of the YOLOv5 graphs): csp_c3.hip
+int csp_c3_supported(int cin, int cout, int wd, int nbtl, int h, int w, int dtype);
+int csp_c3_tiles(int n, int cin, int cout, int wd, int nbtl, int h, int w, int* geom8);
+int csp_c3_fwd(const mgdt_view* x, const void* const* mid, const float* const* mid_bias, int nbtl, int shortcut, const void* back, const float* back_bias,
+               int wd, const mgdt_view* y, mgdt_stream s);
+
 /* supported configurations of the fused block: bf16, wd in {8,16,32,64}, n in {1,2}; MSPA: even H, W; C2f: Cin % 32 == 0, Cin <= 256 */
 extern "C" int mgdt_csp_block_supported(int mode, int cin, int cout, int wd, int nbtl, int h, int w, int dtype) {
+  if (mode == 2) return csp_c3_supported(cin, cout, wd, nbtl, h, w, dtype);
+  if (mode != 0 && mode != 1) return 0;
   if (dtype != MGDT_BF16 || (wd != 8 && wd != 16 && wd != 32 && wd != 64) || nbtl < 1 || nbtl > 2 || cout % 4) return 0;
   const int catC = (mode == 0 ? 3 : 2) * wd + nbtl * wd;
   if (catC > 256 || catC % 8) return 0;
@@ -583,6 +591,7 @@ static bool csp_pick_tile(int mode, int H, int W, int N, int wd, int nbtl, int c
  * execution order.  back / back_bias: the 1x1 conv over the concat.  pool: NULL or fp32 [N][slots][Cout] per-tile channel sums of y
  * (slots and the tile grid: mgdt_csp_block_tiles). */
 extern "C" int mgdt_csp_block_tiles(int mode, int n, int cin, int cout, int wd, int nbtl, int h, int w, int* geom6) {
+  if (mode == 2) return csp_c3_tiles(n, cin, cout, wd, nbtl, h, w, geom6);
   if (!mgdt_csp_block_supported(mode, cin, cout, wd, nbtl, h, w, MGDT_BF16)) return 0;
   const int catC = (mode == 0 ? 3 : 2) * wd + nbtl * wd;
   const int nbk = csp_chain_nbk(wd);
@@ -606,6 +615,7 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
   if (act != MGDT_ACT_SILU) MGDT_FAIL(MGDT_BAD_ARG, "csp_block: activation %d (only SiLU, the blocks' default, is built)", act);
   for (int j = 0; j < 2 * nbtl; ++j)
     if (!mid[j] || !mid_bias[j]) MGDT_FAIL(MGDT_BAD_ARG, "csp_block: missing conv panel %d", j);
+  if (mode == 2) return csp_c3_fwd(x, mid, mid_bias, nbtl, shortcut, back, back_bias, wd, y, s);
   CspArgs a;
   memset(&a, 0, sizeof(a));
   const long sz = 2;

@@ -1,2 +1,2 @@
-"""Model graph configs (the reference's `models/v8/*.yaml` graphs as Python dict builders)."""
-from .v8 import CLS_CONFIGS, CONFIGS, POSE_CONFIGS, RTDETR_CONFIGS, SEG_CONFIGS, get_config  # noqa: F401
+"""Model graph configs (the reference's `models/v8/*.yaml` and `models/v5/yolov5.yaml` graphs as Python dict builders)."""
+from .v8 import ALL_CONFIGS, CLS_CONFIGS, CONFIGS, POSE_CONFIGS, RTDETR_CONFIGS, SEG_CONFIGS, V5_CONFIGS, get_config  # noqa: F401

@@ -130,11 +130,36 @@ def _rtdetr(head):
 RTDETR_CONFIGS = {'yolov8-rtdetr': lambda nc=80: _cfg('C2f', _rtdetr(_pan_head), nc)}
 
 
+# [depth, width, max_channels] of models/v5/yolov5.yaml: m / l / x keep max_channels 1024 and x is deeper (1.33) than in the v8 files
+V5_SCALES = {'n': [0.33, 0.25, 1024], 's': [0.33, 0.50, 1024], 'm': [0.67, 0.75, 1024], 'l': [1.00, 1.00, 1024], 'x': [1.33, 1.25, 1024]}
+
+
+def _v5_cfg(nc):
+    """models/v5/yolov5.yaml (YOLOv5 v6.0, P3-P5): the 6x6 / stride 2 / padding 2 stem, C3 blocks, SPPF, a PAN head of C3 blocks without shortcuts, Detect."""
+    up = [-1, 1, 'nn.Upsample', ['None', 2, 'nearest']]
+    backbone = [[-1, 1, 'Conv', [64, 6, 2, 2]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'C3', [128]], [-1, 1, 'Conv', [256, 3, 2]], [-1, 6, 'C3', [256]],
+                [-1, 1, 'Conv', [512, 3, 2]], [-1, 9, 'C3', [512]], [-1, 1, 'Conv', [1024, 3, 2]], [-1, 3, 'C3', [1024]], [-1, 1, 'SPPF', [1024, 5]]]
+    head = [[-1, 1, 'Conv', [512, 1, 1]], list(up), [[-1, 6], 1, 'Concat', [1]], [-1, 3, 'C3', [512, False]],
+            [-1, 1, 'Conv', [256, 1, 1]], list(up), [[-1, 4], 1, 'Concat', [1]], [-1, 3, 'C3', [256, False]],
+            [-1, 1, 'Conv', [256, 3, 2]], [[-1, 14], 1, 'Concat', [1]], [-1, 3, 'C3', [512, False]],
+            [-1, 1, 'Conv', [512, 3, 2]], [[-1, 10], 1, 'Concat', [1]], [-1, 3, 'C3', [1024, False]],
+            [[17, 20, 23], 1, 'Detect', ['nc']]]
+    return {'nc': nc, 'scales': deepcopy(V5_SCALES), 'backbone': backbone, 'head': head}
+
+
+# YOLOv5 detection graph: the reference's models/v5/yolov5.yaml.  A table of its own: CONFIGS lists the graphs that have a models/v8/ file.
+# yolov5-p6, YOLOv3 and YOLOv6 are not built.
+V5_CONFIGS = {'yolov5': lambda nc=80: _v5_cfg(nc)}
+
+
+# every built-in graph by name (the tables above stay apart: CONFIGS lists the detection graphs that have a models/v8/ file)
+ALL_CONFIGS = {**CONFIGS, **SEG_CONFIGS, **POSE_CONFIGS, **CLS_CONFIGS, **RTDETR_CONFIGS, **V5_CONFIGS}
+
+
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
-    table = (CONFIGS if name in CONFIGS else SEG_CONFIGS if name in SEG_CONFIGS else CLS_CONFIGS if name in CLS_CONFIGS else
-             RTDETR_CONFIGS if name in RTDETR_CONFIGS else POSE_CONFIGS)
-    d = table[name]() if nc is None else table[name](nc)      # nc=None: the YAML file's own class count
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS / V5_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    build = ALL_CONFIGS[name]
+    d = build() if nc is None else build(nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale
     d['yaml_file'] = f'{name}.yaml'
     return d

@@ -12,7 +12,7 @@ from .conv import Conv, HipModule, act_code
 from .convnextv2 import ConvNeXtV2_Block
 from .spr_module import SPRModule
 
-__all__ = ('DFL', 'SPPF', 'C2f', 'MSPA_C2f', 'Bottleneck', 'SimFusion_4in', 'SimFusion_3in', 'IFM', 'h_sigmoid',
+__all__ = ('DFL', 'SPPF', 'C2f', 'C3', 'MSPA_C2f', 'Bottleneck', 'SimFusion_4in', 'SimFusion_3in', 'IFM', 'h_sigmoid',
            'InjectionMultiSum_Auto_pool', 'Upsample', 'Proto')
 
 
@@ -126,6 +126,82 @@ class C2f(HipModule):
         for j in reversed(range(n)):                                  # bottleneck j: slot 1+j -> slot 2+j
             self.m[j].backward(gcat[:, (2 + j) * c:(3 + j) * c], acc_into=gcat[:, (1 + j) * c:(2 + j) * c])
         return self.cv1.backward(gcat[:, :2 * c])
+
+
+class C3(HipModule):
+    """CSP bottleneck with 3 convolutions (reference block.py:434-447), the block of the YOLOv5 graphs: cv3(cat(m(cv1(x)), cv2(x))).  Composed from the
+    convolution kernels, eval and train, fp32 and bf16, any n and any map: cv2 and the last bottleneck write the two halves of the concat buffer
+    cv3 reads, so no copy is launched; in the reverse pass the shortcut gradients and the sum of the two branches' input gradients ride in the
+    data-gradient convolutions' epilogues.  bf16 inference of a plain block whose (width, n) class ops.C3_FUSED_CLASSES lists runs as two launches instead:
+    [cv1 | cv2] as one 1x1 over the concatenated weights, then mode CSP_C3 of mgdt_csp_block_fwd (bottlenecks and cv3 on LDS-resident tiles);
+    ops.FUSED_CSP_BLOCK = False switches that off.  Which classes are listed is a measurement."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.c = c_
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.cv3 = Conv(2 * c_, c2, 1)
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
+
+    def _plain(self):
+        """what mode CSP_C3 of mgdt_csp_block_fwd computes: 1x1 Conv + BN (or fused bias) + SiLU at both ends, bottlenecks of a dense 1x1 and a dense 3x3
+        with one shortcut setting, nobody watching the inner modules (forward hooks), no fp8 calibration or fp8 sites"""
+        convs = [self.cv1, self.cv2, self.cv3] + [c for m in self.m for c in (m.cv1, m.cv2)]
+        ks = [1, 1, 1] + [1, 3] * len(self.m)
+        if ops.Q8_CALIB is not None or len(self.m) == 0 or any(m._forward_hooks for m in self.modules() if m is not self):
+            return False
+        for c, k in zip(convs, ks):
+            if not (isinstance(c, Conv) and c.plain_affine() and isinstance(c.act, nn.SiLU) and c.conv.kernel_size == (k, k) and c.conv.stride == (1, 1)
+                    and c.conv.groups == 1 and c.conv.dilation == (1, 1) and not c.__dict__.get('_q8')):
+                return False
+        fused = not hasattr(self.cv1, 'bn')
+        if fused != (not hasattr(self.cv2, 'bn')) or (not fused and self.cv1.bn.eps != self.cv2.bn.eps):
+            return False
+        return all(isinstance(m, Bottleneck) and m.add == self.m[0].add and m.cv1.conv.in_channels == m.cv1.conv.out_channels == m.cv2.conv.out_channels == self.c
+                   for m in self.m)
+
+    def _merged_front(self, dt):
+        """PackedConv of cat(cv1, cv2) along cout (BN folded per branch): [a | b] in one launch"""
+        a, b = self.cv1, self.cv2
+        fused = not hasattr(a, 'bn')
+        cat = lambda fn: torch.cat([fn(a).detach().float(), fn(b).detach().float()])
+        zb = lambda m: m.conv.bias if m.conv.bias is not None else torch.zeros(m.conv.out_channels, device=m.conv.weight.device)
+        bn = lambda: None if fused else (cat(lambda m: m.bn.weight), cat(lambda m: m.bn.bias), cat(lambda m: m.bn.running_mean), cat(lambda m: m.bn.running_var), a.bn.eps)
+        return self._cached(('front', dt), [t for m in (a, b) for t in m.affine_tensors()],
+                            lambda: ops.PackedConv(cat(lambda m: m.conv.weight), cat(zb) if fused else None, bn(), 1, dt))
+
+    def forward(self, x):
+        b, _, h, w = x.shape
+        c, n = self.c, len(self.m)
+        train = self.training and hasattr(self.cv1, 'bn')
+        dt0 = self.cv1.out_dtype(x)
+        if (not train and dt0 == torch.bfloat16 and x.dtype == dt0 and ops.c3_fused_route(c, n) and self._plain()
+                and ops.conv_can_mfma(x, x.shape[1], 2 * c, 1, 1, 1, dt0)):
+            ab = ops.new_act(b, 2 * c, h, w, dt0, x.device)
+            if ops.csp_block_supported(ops.CSP_C3, ab, self.cv3.conv.out_channels, c, n, dt0):
+                # two launches: [a | b] = [cv1 | cv2](x) (a wide streaming 1x1 GEMM), then the bottleneck chain on LDS-resident tiles + cv3
+                ops.conv2d(x, self._merged_front(dt0), 1, ops.ACT_SILU, out=ab)
+                mids = [pk for m in self.m for pk in (m.cv1.packed(dt0, False), m.cv2.packed(dt0, False))]
+                return ops.csp_block(ops.CSP_C3, ab, None, None, mids, self.m[0].add, self.cv3.packed(dt0, False), c, ops.ACT_SILU,
+                                     self.cv3.conv.out_channels, False)[0]
+        f = (lambda m: m.train_fwd) if train else (lambda m: m.run)
+        cat = ops.new_act(b, 2 * c, h, w, self.cv1.out_dtype(x), x.device)
+        f(self.cv2)(x, out=cat[:, c:])
+        t = f(self.cv1)(x, out=cat[:, :c] if n == 0 else None)
+        for j, m in enumerate(self.m):
+            t = m.run(t, out=cat[:, :c] if j == n - 1 else None)
+        return f(self.cv3)(cat)
+
+    def backward(self, g):
+        c = self.c
+        gcat = self.cv3.backward(g)                                   # grad of the concat buffer
+        ga = gcat[:, :c]
+        for m in reversed(list(self.m)):                              # each bottleneck's shortcut gradient is the r2 addend of its cv1 data gradient
+            ga = m.backward(ga)
+        dx = self.cv1.backward(ga)
+        return self.cv2.backward(gcat[:, c:], dx_out=dx, acc=True)    # += in the data-gradient convolution's epilogue
 
 
 class MSPA_C2f(HipModule):

@@ -124,17 +124,45 @@ class Conv(HipModule):
         return (one, self.conv.bias.detach().float() if self.conv.bias is not None else zero, zero, one, 0.0)
 
     # -- packed weights ------------------------------------------------------------------------------
+    def _stem6(self):
+        """the 6x6 / stride 2 / padding 2 stem of the YOLOv5 graphs (models/v5/yolov5.yaml row 0): runs as space-to-depth + a 3x3 / stride 1 convolution
+        over the 4 * c1 channel map (ops.space_to_depth2, ops.stem6_w3), an exact identity"""
+        c = self.conv
+        return (c.kernel_size == (6, 6) and c.stride == (2, 2) and c.padding == (2, 2) and c.dilation == (1, 1) and c.groups == 1 and c.in_channels <= 4)
+
     def _geometry(self):
         c = self.conv
+        if self._stem6():
+            return 6, 2
         k, s = c.kernel_size[0], c.stride[0]
         if c.kernel_size[0] != c.kernel_size[1] or c.stride[0] != c.stride[1] or c.dilation != (1, 1) or c.padding != (k // 2, k // 2):
             raise RuntimeError(f'Conv geometry {c} is outside the built kernels (square k, same padding, dilation 1)')
         return k, s
 
+    def _stem6_input(self, x, dt):
+        """the space-to-depth map the 3x3 form of the 6x6 stem reads; sizes it cannot take raise before any launch"""
+        if x.dim() != 4 or x.shape[1] != self.conv.in_channels or x.shape[2] % 2 or x.shape[3] % 2:
+            raise RuntimeError(f'Conv: the 6x6 / stride 2 / padding 2 stem takes a (B, {self.conv.in_channels}, H, W) image with even H and W '
+                               f'(model inputs are multiples of the stride), got {tuple(x.shape)}')
+        return ops.space_to_depth2(x, dt)
+
+    def _stem6_packed(self, dt, direct, raw=False):
+        """panel of the 3x3 form (zero rows for the map's pad channels).  On the MFMA route it is packed straight from the live 6x6 weight
+        (ops.PackedStem6), so it follows ops.PARAM_EPOCH / ops.repack_all() under the trainer like every other panel; the direct kernel's panel is
+        packed from the derived copy ops.stem6_w3 and rebuilt when the weights move or change.  `raw`: the bare convolution of the training forward."""
+        tens = [self.conv.weight] if raw else self.affine_tensors()
+        cb, bn = (None, None) if raw else (self.conv.bias, self.bn_tuple())
+        if not direct:
+            return self._cached(('stem6', raw, dt), tens, lambda: ops.PackedStem6(self.conv.weight, cb, bn, dt))
+        cp = ops.space_to_depth2_channels(self.conv.in_channels, dt)
+        return self._cached(('stem6', raw, dt, 'direct'), tens, lambda: ops.PackedConv(ops.stem6_w3(self.conv.weight, cp), cb, bn, 3, dt, direct=True))
+
     def packed(self, dtype, direct):
         has_bn = hasattr(self, 'bn')
         tens = [self.conv.weight, self.conv.bias] + ([self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var] if has_bn else [])
         k, _ = self._geometry()
+        if k == 6:
+            return self._stem6_packed(dtype, direct)
 
         def build():
             bn = (self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, self.bn.eps) if has_bn else None
@@ -157,6 +185,12 @@ class Conv(HipModule):
             self._no_train_bn(self.bn)
         k, s = self._geometry()
         dt = self.out_dtype(x) if out is None else out.dtype
+        if k == 6:                              # the YOLOv5 stem: space-to-depth, then the 3x3 / stride 1 form on the implicit GEMM (bf16 operands under quantize_fp8 too)
+            if x2 is not None or in_scale is not None or in_shift is not None:
+                raise RuntimeError('Conv: the 6x6 stem reads the image (no fused pre-add or input affine)')
+            sd = self._stem6_input(x, dt)
+            mfma = ops.conv_can_mfma(sd, sd.shape[1], self.conv.out_channels, 3, 1, 1, dt)
+            return ops.conv2d(sd, self._stem6_packed(dt, not mfma), 1, act_code(self.act), out=out, r1=r1, r2=r2)
         mfma = ops.conv_can_mfma(x, self.conv.in_channels, self.conv.out_channels, k, s, self.conv.groups, dt)
         if mfma and dt == torch.bfloat16:
             xq = self.q8_site(None, x, x2)
@@ -175,12 +209,19 @@ class Conv(HipModule):
         """act(bn_batchstats(conv(x [+ x2]))) [+ r1] [+ r2]; keeps (x, x2, raw conv output, mean, rstd) for backward()."""
         k, s = self._geometry()
         dt = self.out_dtype(x) if out is None else out.dtype
-        mfma = ops.conv_can_mfma(x, self.conv.in_channels, self.conv.out_channels, k, s, self.conv.groups, dt)
-        pk = self._cached(('raw', dt, not mfma), [self.conv.weight],
-                          lambda: ops.PackedConv(self.conv.weight, None, None, k, dt, direct=not mfma, groups=self.conv.groups))
-        if x2 is not None and not mfma:
-            raise RuntimeError('Conv.train_fwd: the fused pre-add needs the MFMA path (NHWC input, cin % 4 == 0)')
-        y = ops.conv2d(x, pk, s, ops.ACT_NONE, x2=x2)
+        if k == 6:                              # the YOLOv5 stem: the same route as run(); backward() sees the space-to-depth map as the conv's input
+            if x2 is not None:
+                raise RuntimeError('Conv.train_fwd: the 6x6 stem reads the image (no fused pre-add)')
+            x = self._stem6_input(x, dt)
+            mfma = ops.conv_can_mfma(x, x.shape[1], self.conv.out_channels, 3, 1, 1, dt)
+            y = ops.conv2d(x, self._stem6_packed(dt, not mfma, raw=True), 1, ops.ACT_NONE)
+        else:
+            mfma = ops.conv_can_mfma(x, self.conv.in_channels, self.conv.out_channels, k, s, self.conv.groups, dt)
+            pk = self._cached(('raw', dt, not mfma), [self.conv.weight],
+                              lambda: ops.PackedConv(self.conv.weight, None, None, k, dt, direct=not mfma, groups=self.conv.groups))
+            if x2 is not None and not mfma:
+                raise RuntimeError('Conv.train_fwd: the fused pre-add needs the MFMA path (NHWC input, cin % 4 == 0)')
+            y = ops.conv2d(x, pk, s, ops.ACT_NONE, x2=x2)
         bn = self.bn
         mean, rstd = ops.bn_stats(y, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
         z = ops.bn_act(y, mean, rstd, bn.weight, bn.bias, act_code(self.act), out=out, r1=r1, r2=r2)
@@ -192,6 +233,8 @@ class Conv(HipModule):
         (written into the view `dx_out` when given; `acc`: added to what dx_out holds; `r2`: one more addend, e.g. a shortcut's gradient -
         both fused into the data-gradient convolution's epilogue)."""
         x, x2, y, mean, rstd, k, s = self._ctx.pop()
+        if k == 6:
+            return self._backward_stem6(gz, x, y, mean, rstd, need_dx)
         if self.conv.groups != 1:
             return self._backward_grouped(gz, x, y, mean, rstd, k, s, need_dx, dx_out, acc, r2)
         bn = self.bn
@@ -204,6 +247,21 @@ class Conv(HipModule):
             return None
         dx = dx_out if dx_out is not None else ops.new_act(x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.dtype, dy.device)
         return ops.conv_dgrad(dy, self.conv.weight, k, s, dx, accumulate=bool(acc and dx_out is not None), r2=r2)
+
+    def _backward_stem6(self, gz, sd, y, mean, rstd, need_dx):
+        """the 6x6 stem: the 3x3 weight-gradient kernel over the space-to-depth map `sd`, then the inverse permutation of its final sums into
+        conv.weight.grad's (cout, c1, 6, 6) layout (ops.stem6_wgrad_unpack flushes deferred sums first).  Layer 0 never needs dx."""
+        if need_dx:
+            raise RuntimeError('Conv.backward: the 6x6 stem has no data gradient (it reads the image: call backward(g, need_dx=False))')
+        bn = self.bn
+        dy = ops.bn_act_bwd(gz, y, mean, rstd, bn.weight, bn.bias, act_code(self.act), ops.grad_buf(bn.weight), ops.grad_buf(bn.bias))
+        dw3 = torch.empty((self.conv.out_channels, sd.shape[1], 3, 3), dtype=torch.float32, device=sd.device)      # 9 KB scratch per step (captured: the graph's pool)
+        ops.conv_wgrad(sd, dy, 3, 1, dw3)
+        # stem6_wgrad_unpack flushes ALL pending deferred weight-gradient sums, not only dw3's.  That is always correct (a flush only moves the one
+        # final-sum launch forward) and costs nothing where this geometry occurs: the conv reads the image, so it is layer 0, the last layer of
+        # the reverse pass, and the flush is the one BaseModel.backward would issue right after.  Elsewhere in a graph it would split that launch in two.
+        ops.stem6_wgrad_unpack(dw3, ops.grad_buf(self.conv.weight))
+        return None
 
     def _backward_grouped(self, gz, x, y, mean, rstd, k, s, need_dx, dx_out, acc, r2):
         """DWConv / Conv with g > 1 (conv.py:82-86): the grouped VALU kernels (weight [cout][cin/g][k][k]); not on any target YAML."""

@@ -18,11 +18,11 @@ import torch.nn as nn
 
 from .. import ops
 from ..yolo.utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts, make_divisible
-from .modules import (C2f, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, Detect, DWConv, InjectionMultiSum_Auto_pool,
+from .modules import (C2f, C3, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, Detect, DWConv, InjectionMultiSum_Auto_pool,
                       Pose, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
 
 # names a YAML row may use -> class (the reference resolves them with globals()[m] / getattr(torch.nn, ...), tasks.py:630)
-REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, MSPA_C2f, SPPF, SimFusion_4in, SimFusion_3in, IFM,
+REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, C3, MSPA_C2f, SPPF, SimFusion_4in, SimFusion_3in, IFM,
                                     InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose, Classify, RTDETRDecoder)}
 REGISTRY['nn.Upsample'] = Upsample
 
@@ -415,6 +415,7 @@ class BaseModel(nn.Module):
             self.train(was_training)
         names = {m: n for n, m in self.named_modules()}
         exclude = tuple(exclude) + tuple(n + '.' for n, m in self.named_modules() if isinstance(m, (Segment, Pose, Classify)))     # fp8 for the Segment / Pose / Classify heads is not built
+        exclude += tuple(n + '.' for n, m in self.named_modules() if isinstance(m, C3) or (isinstance(m, Conv) and m._stem6()))      # ... nor for the YOLOv5 graphs' C3 blocks and 6x6 stem
         table = {}
         for (m, key), amax in stats.items():
             if any(e in names.get(m, '?') + '.' for e in exclude):
@@ -840,12 +841,12 @@ def parse_model(d, ch, verbose=True):
                     args[j] = nc if a == 'nc' else kpt_shape if (a == 'kpt_shape' and kpt_shape is not None) else ast.literal_eval(a)
         n = n_ = max(round(n * depth), 1) if n > 1 else n
         r_in = red[f] if isinstance(f, int) else None
-        if m in (Conv, DWConv, Bottleneck, SPPF, C2f, MSPA_C2f):
+        if m in (Conv, DWConv, Bottleneck, SPPF, C2f, C3, MSPA_C2f):
             c1, c2 = ch[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
             args = [c1, c2, *args[1:]]
-            if m in (C2f, MSPA_C2f):
+            if m in (C2f, C3, MSPA_C2f):
                 args.insert(2, n)
                 n = 1
             r_out = r_in * (args[3] if m in (Conv, DWConv) and len(args) > 3 else 1)
@@ -979,7 +980,7 @@ def yaml_model_load(path):
     """Load a model YAML in the reference's schema; '...yolov8n.yaml' resolves to '...yolov8.yaml' + scale n (tasks.py:702-717).
     Names of the built-in graphs (mgdt_yolo_amd.models.CONFIGS) resolve without a file."""
     import yaml
-    from ..models import CLS_CONFIGS, CONFIGS, POSE_CONFIGS, RTDETR_CONFIGS, SEG_CONFIGS, get_config
+    from ..models import ALL_CONFIGS, get_config
     path = Path(path)
     scale = guess_model_scale(path)
     unified = Path(re.sub(r'(\d+)([nslmx])(.+)?$', r'\1\3', str(path)))
@@ -990,7 +991,7 @@ def yaml_model_load(path):
             d['scale'] = scale
             d['yaml_file'] = str(path)
             return d
-    if unified.stem in CONFIGS or unified.stem in SEG_CONFIGS or unified.stem in POSE_CONFIGS or unified.stem in CLS_CONFIGS or unified.stem in RTDETR_CONFIGS:
+    if unified.stem in ALL_CONFIGS:
         d = get_config(unified.stem, scale or 'n')
         d['scale'] = scale
         d['yaml_file'] = str(path)

@@ -429,9 +429,92 @@ def stem2_route(x, y, cu_count=0, x_dtype=None):
     return dict(loader='fast' if out[0] else 'generic', tiles_x=out[1], tiles_y=out[2], tiles=out[3], grid=out[4], per_xcd=out[5])
 
 
+# ------------------------------------------------------------------ the 6x6 / stride 2 / padding 2 stem (YOLOv5) as space-to-depth + 3x3
+def space_to_depth2_channels(c, dtype):
+    """channels of the space-to-depth map of a c-channel image in `dtype`: 4c rounded up to whole 16-byte stores (3 -> 12 fp32, 16 bf16)"""
+    v = 8 if dtype == torch.bfloat16 else 4
+    return (4 * c + v - 1) // v * v
+
+
+def space_to_depth2(x, dtype, out=None):
+    """x (B, C <= 4, H, W) image of any strides (uint8 is divided by 255 / fp32 / bf16), H and W even -> S (B, Cp, H/2, W/2) NHWC in `dtype` with
+    S[b, (dy*2+dx)*C + ci, i, j] = x[b, ci, 2i+dy, 2j+dx] and channels 4C.. zero (mgdt_space_to_depth2_fwd)."""
+    b, c, h, w = x.shape
+    if c > 4 or h % 2 or w % 2:
+        raise RuntimeError(f'space_to_depth2: an image of at most 4 channels with even height and width, got {tuple(x.shape)}')
+    _need_gpu(x)
+    if x.dtype != torch.uint8 and dtype_code(x.dtype) == BF16 and dtype != torch.bfloat16:
+        raise RuntimeError('space_to_depth2: a bf16 image goes to a bf16 map')
+    if out is None:
+        out = new_act(b, space_to_depth2_channels(c, dtype), h // 2, w // 2, dtype, x.device)
+    if _PROF is not None:
+        _META['space_to_depth2_fwd'] = dict(shape=tuple(x.shape), flops=0.0, bytes=float(x.numel() * x.element_size() + out.numel() * out.element_size()))
+    _launch('space_to_depth2_fwd', 'mgdt_space_to_depth2_fwd', vp(x), U8 if x.dtype == torch.uint8 else dtype_code(x.dtype), vp(out), dtype_code(out.dtype), stream())
+    return out
+
+
+class PackedStem6(PackedConv):
+    """Panel of the 3x3 / stride 1 form of the 6x6 / stride 2 / padding 2 stem over the space-to-depth map (BN folded, zero rows for the map's pad
+    channels), packed straight from the live 6x6 weight (mgdt_conv_pack_stem6): repack_all() refreshes it in place like every other panel."""
+    __slots__ = ()
+
+    def __init__(self, weight6, conv_bias, bn, dtype):
+        """weight6: (cout, c6 <= 4, 6, 6) fp32 cuda; bn: None or (gamma, beta, mean, var, eps)."""
+        lib = L.lib()
+        weight = weight6.detach().float().contiguous()
+        _need_gpu(weight)
+        cout, c6 = weight.shape[0], weight.shape[1]
+        if tuple(weight.shape[2:]) != (6, 6) or c6 > 4:
+            raise RuntimeError(f'PackedStem6: a (cout, <= 4, 6, 6) weight, got {tuple(weight.shape)}')
+        g, b, mu, var, eps = (None, None, None, None, 0.0) if bn is None else bn
+        f = lambda t: None if t is None else t.detach().float().contiguous()
+        g, b, mu, var, cb = f(g), f(b), f(mu), f(var), f(conv_bias)
+        code = dtype_code(dtype)
+        cp = space_to_depth2_channels(c6, dtype)
+        self.k, self.cin, self.cout, self.dtype, self.direct, self.groups = 3, cp, cout, dtype, False, 1
+        self.w = torch.empty(lib.mgdt_conv_packed_bytes(cp, cout, 3, code), dtype=torch.uint8, device=weight.device)
+        self.bias = torch.empty((cout + 15) // 16 * 16, dtype=torch.float32, device=weight.device)
+        _launch('conv_pack', 'mgdt_conv_pack_stem6', ptr(weight), ptr(cb), ptr(g), ptr(b), ptr(mu), ptr(var), eps, c6, cout, code, ptr(self.w), ptr(self.bias), stream())
+        _register_pack(self, (weight, cb, g, b, mu, var, float(eps), c6, cout, 3, code, 5 + c6))
+
+
+def stem6_w3(w6, cp=None):
+    """The 3x3 weight over the space-to-depth map that equals the 6x6 / stride 2 / padding 2 weight w6 (cout, C, 6, 6):
+    W3[co, (dy*2+dx)*C + ci, a, b] = W6[co, ci, 2a+dy, 2b+dx]; rows 4C..cp zero.  A derived copy (plain tensor indexing, any device)."""
+    co, c = w6.shape[0], w6.shape[1]
+    w3 = w6.detach().reshape(co, c, 3, 2, 3, 2).permute(0, 3, 5, 1, 2, 4).reshape(co, 4 * c, 3, 3)
+    if cp is not None and cp > 4 * c:
+        w3 = torch.cat([w3, w3.new_zeros(co, cp - 4 * c, 3, 3)], 1)
+    return w3.contiguous()
+
+
+def stem6_w6(w3, c):
+    """Inverse of stem6_w3 on the first 4c rows: (cout, >= 4c, 3, 3) -> (cout, c, 6, 6)."""
+    co = w3.shape[0]
+    return w3[:, :4 * c].reshape(co, 2, 2, c, 3, 3).permute(0, 3, 4, 1, 5, 2).reshape(co, c, 6, 6).contiguous()
+
+
+def stem6_wgrad_unpack(dw3, dw6):
+    """dw6 (cout, C, 6, 6) fp32 <- the final sums dw3 (cout, cp, 3, 3) fp32 of the 3x3 weight gradient over the space-to-depth map (mgdt_stem6_wgrad_unpack).
+    Pending deferred weight-gradient sums are flushed first: the permutation reads final sums, never partials."""
+    flush_wgrad()
+    if not (dw3.is_contiguous() and dw6.is_contiguous() and dw3.dtype == dw6.dtype == torch.float32 and dw3.shape[0] == dw6.shape[0]
+            and tuple(dw3.shape[2:]) == (3, 3) and tuple(dw6.shape[2:]) == (6, 6) and dw3.shape[1] >= 4 * dw6.shape[1]):
+        raise RuntimeError(f'stem6_wgrad_unpack: contiguous fp32 (cout, cp, 3, 3) -> (cout, c, 6, 6), got {tuple(dw3.shape)} -> {tuple(dw6.shape)}')
+    _launch('stem6_wgrad_unpack', 'mgdt_stem6_wgrad_unpack', ptr(dw3), dw6.shape[0], dw6.shape[1], dw3.shape[1], ptr(dw6), stream())
+    return dw6
+
+
 # ------------------------------------------------------------------ whole CSP block (MSPA_C2f / C2f) in one launch
 FUSED_CSP_BLOCK = True   # tests flip this to compare against the per-conv launch chain
-CSP_MSPA, CSP_C2F = 0, 1
+CSP_MSPA, CSP_C2F, CSP_C3 = 0, 1, 2
+# C3 blocks (mode CSP_C3): the (wd, n) classes that take the one-launch route.  Decided by measurement (tools/c3_bench.py, DESIGN section 5): a class is
+# listed only where its median beat the composed route's by more than the run-to-run spread of the two.  None: every class the kernel covers (tests, the tool).
+C3_FUSED_CLASSES = ((16, 1), (32, 1), (32, 2), (64, 1))      # the yolov5n blocks at B = 32, 640 x 640; (16, 2) and (64, 2) are covered by the kernel but unmeasured: composed
+
+
+def c3_fused_route(wd, nbtl):
+    return FUSED_CSP_BLOCK and (C3_FUSED_CLASSES is None or (int(wd), int(nbtl)) in C3_FUSED_CLASSES)
 
 
 def csp_block_supported(mode, x, cout, wd, nbtl, dtype):
@@ -460,8 +543,8 @@ def csp_block(mode, x, front, front_bias, mids, shortcut, back, wd, act, cout, w
     barr = (C.c_void_p * len(mids))(*[m.bias.data_ptr() for m in mids])
     if _PROF is not None:
         es = x.element_size()
-        catc = (3 if mode == CSP_MSPA else 2) * wd + nb * wd
-        fl = 2.0 * b * h * w * ((3 * wd * wd if mode == CSP_MSPA else 0) + 2 * nb * 9 * wd * wd + catc * cout)
+        catc = 2 * wd if mode == CSP_C3 else (3 if mode == CSP_MSPA else 2) * wd + nb * wd
+        fl = 2.0 * b * h * w * ((3 * wd * wd if mode == CSP_MSPA else 0) + (10 if mode == CSP_C3 else 18) * nb * wd * wd + catc * cout)
         _META['csp_block_fwd'] = dict(shape=(b, cin, h, w, cout, wd, nb), flops=fl, bytes=float(b * h * w * (cin + cout) * es))
     _launch('csp_block_fwd', 'mgdt_csp_block_fwd', mode, vp(x), ptr(front), ptr(front_bias), marr, barr, nb, int(bool(shortcut)), ptr(back.w), ptr(back.bias),
             int(wd), act, vp(y), ptr(pool), dtype_code(x.dtype), stream())
