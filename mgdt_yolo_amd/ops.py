@@ -1639,6 +1639,10 @@ def conv_wgrad(x, dy, k, stride, dw, dbias=None, x2=None, accumulate=False):
         return
     if is_nhwc(x) and x.shape[1] % 4 == 0 and dy.shape[1] % 4 == 0:
         _same(x, dy, x2)
+    elif x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and x2 is None and is_nhwc(x) and x.shape[1] % 4 == 0:
+        # a bf16 NHWC feature map in front of a convolution whose cout is no multiple of 4 (Detect's class branch with nc = 1 or 2 under amp): the
+        # generic kernel reads fp32, so the map is widened first (one cast launch over a head-sized map; the values are the same)
+        x = copy(x, new_act(x.shape[0], x.shape[1], x.shape[2], x.shape[3], torch.float32, x.device))
     elif x.dtype != torch.float32 or dy.dtype not in (torch.float32, torch.bfloat16):
         # the generic kernel (any layout, any channel count) reads x as fp32 whatever dy is: any other dtype would be an out-of-range read
         raise RuntimeError(f'conv_wgrad: the generic (non-NHWC / channels % 4 != 0) path takes an fp32 input, got {x.dtype} (dy {dy.dtype})')
