@@ -243,7 +243,9 @@ int mgdt_conv1x1_inject_conv_fwd(const mgdt_view* x, const void* packed_w, const
                                  const void* packed_w2, const float* bias2, int act2, const mgdt_view* y2, int dtype, mgdt_stream s);
 
 /* ---- TOODHead (nn/modules/head.py:466-572; parity unpinned: mmcv's ModulatedDeformConv2d is not shipped with the reference) --------
- * GroupNorm + activation (Conv_GN head.py:67-81, DyDCNv2's norm block.py:427-431): y = act(group_norm(x, groups, gamma, beta, eps)). */
+ * GroupNorm + activation (Conv_GN head.py:67-81, DyDCNv2's norm block.py:427-431): y = act(group_norm(x, groups, gamma, beta, eps)).
+ * ws: mgdt_groupnorm_workspace_bytes(n, c) bytes, 8-byte aligned (it holds the double partial sums; MGDT_BAD_ARG otherwise); x, y: 4-aligned NHWC views,
+ * c <= 4096, h*w < 2^31 - 2^16 (MGDT_BAD_SHAPE otherwise). */
 size_t mgdt_groupnorm_workspace_bytes(int n, int c);
 int mgdt_groupnorm_fwd(const mgdt_view* x, const float* gamma, const float* beta, int groups, float eps, int act, void* ws, const mgdt_view* y,
                        int dtype, mgdt_stream s);
@@ -626,10 +628,15 @@ int mgdt_ap_per_class(const void* tp, const float* conf, const int32_t* seg, con
 
 /* ---- TOODHead training (reference nn/modules/head.py:466-572 under autograd; mmcv ModulatedDeformConv2d backward) -----------------------
  * GroupNorm(16)+act backward of Conv_GN / DyDCNv2.norm (head.py:67-81, block.py:401-432), composed with mgdt_nc_reduce:
- *   gn_affine:          Sy = sum_hw y, Syy = sum_hw y*y  ->  mean / rstd per (image, group), A = gamma*rstd, B = beta - mean*rstd*gamma  (u = y*A + B)
+ *   gn_affine:          sum_hw y, sum_hw y*y in double (the forward kernel's partial sums)  ->  mean / rstd per (image, group), A = gamma*rstd,
+ *                       B = beta - mean*rstd*gamma  (u = y*A + B); y: 4-aligned NHWC view, c <= 4096; ws: mgdt_gn_affine_workspace_bytes, 8-byte aligned, whose
+ *                       last n*groups*2 doubles (offset mgdt_gn_affine_workspace_bytes - n*groups*16) keep (mean, rstd) in double for gn_bwd_coef
  *   nc_affine_act_bwd:  gu = g * act'(y*A + B)        (A = B = NULL: u = y, i.e. with act = ReLU and y the layer output the ReLU mask)
- *   gn_bwd_coef:        S1 = sum_hw gu, S2 = sum_hw gu*y  ->  P, Q, R with dy = gu*P + y*Q + R, and dgamma / dbeta (written or accumulated: the head is
- *                       shared by all levels); ws: mgdt_gn_bwd_workspace_bytes
+ *   gn_act_grad:        GroupNorm's gu = g * act'((y - mean)*rstd*gamma + beta), u formed in double from stats_ng = gn_affine's double (mean, rstd) and
+ *                       rounded once to fp32 (u = y*A + B with fp32 A, B is off by (|mean|/std) of 2^-24); matching 4-aligned NHWC views
+ *   gn_bwd_coef:        S1 = sum_hw gu, S2 = sum_hw gu*y summed in double from the views, centred in double with stats_ng = gn_affine's double (mean, rstd)
+ *                       ->  P, Q, R with dy = gu*P + y*Q + R, and dgamma / dbeta (written or accumulated: the head is shared by all levels);
+ *                       ws: mgdt_gn_bwd_workspace_bytes, 8-byte aligned
  *   nc_axpby:           out = a*sa[n][c] (+ b*sb[n][c]) (+ shift[n][c])     (sa NULL: 1)
  * pixel_gate_bwd: adjoint of mgdt_pixel_gate_fwd (cls_feat * sigmoid(prob logit), head.py:530-537): gx = g*s, glogit = s(1-s) * sum_c g*x.
  * tood_layer_attn_bwd: adjoint of mgdt_tood_layer_attn_fwd (TaskDecomposition.forward head.py:107-116): dscale [n][c] -> dsums [n][c] (gradient
@@ -638,12 +645,15 @@ int mgdt_ap_per_class(const void* tp, const float* conf, const int32_t* seg, con
  *   1x1 convolution of col with weight.view(cout, cin*9), so its weight / column gradients are mgdt_conv_wgrad / dgrad.
  * dcn_col2im_bwd: column gradient -> gx_f32 (dense fp32 NHWC, ZERO on entry; float atomics, the order-dependent scatter of mmcv's col2im) and
  *   gom (offset gradients 0..17, mask-LOGIT gradients 18..26, further channels zeroed) (mmcv modulated_deformable_col2im / col2im_coord). */
-int mgdt_gn_affine(const float* Sy, const float* Syy, int n, int c, int hw, const float* gamma, const float* beta, int groups, float eps,
-                   float* mean_ng, float* rstd_ng, float* A, float* B, mgdt_stream s);
+size_t mgdt_gn_affine_workspace_bytes(int n, int c, int groups);
+int mgdt_gn_affine(const mgdt_view* y, const float* gamma, const float* beta, int groups, float eps, float* mean_ng, float* rstd_ng, float* A, float* B,
+                   void* ws, int dtype, mgdt_stream s);
 int mgdt_nc_affine_act_bwd(const mgdt_view* g, const mgdt_view* y, const float* A, const float* B, int act, const mgdt_view* gu, int dtype, mgdt_stream s);
+int mgdt_gn_act_grad(const mgdt_view* g, const mgdt_view* y, const double* stats_ng, const float* gamma, const float* beta, int groups, int act,
+                     const mgdt_view* gu, int dtype, mgdt_stream s);
 size_t mgdt_gn_bwd_workspace_bytes(int n, int c);
-int mgdt_gn_bwd_coef(const float* S1, const float* S2, const float* mean_ng, const float* rstd_ng, const float* gamma, int n, int c, int hw, int groups,
-                     float* P, float* Q, float* R, float* dgamma, float* dbeta, int accumulate, void* ws, mgdt_stream s);
+int mgdt_gn_bwd_coef(const mgdt_view* gu, const mgdt_view* y, const double* stats_ng, const float* gamma, int groups, float* P, float* Q, float* R,
+                     float* dgamma, float* dbeta, int accumulate, void* ws, int dtype, mgdt_stream s);
 int mgdt_nc_axpby(const mgdt_view* a, const float* sa, const mgdt_view* b, const float* sb, const float* shift, const mgdt_view* out, int dtype,
                   mgdt_stream s);
 int mgdt_pixel_gate_bwd(const mgdt_view* g, const mgdt_view* x, const mgdt_view* logit, const mgdt_view* gx, const mgdt_view* glogit, int dtype, mgdt_stream s);

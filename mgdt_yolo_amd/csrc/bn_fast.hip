@@ -1,5 +1,6 @@
 // Vectorised training-mode BatchNorm kernels (statistics, normalise + activation, backward sums, backward apply) for pixel-linear NHWC
-// views: 4 channels (8 / 16 bytes) per thread, per-thread fp32 partial sums widened to fp64 only when threads are combined, the activation a
+// views: 4 channels (8 / 16 bytes) per thread, per-thread partial sums (fp64 for the statistics, fp32 widened to fp64 when threads are combined for the
+// centred backward sums), the activation a
 // template constant (a run-time switch inside the element loop serialises four exp -> rcp chains).  Same math and the same partial-sum
 // format as the scalar kernels in train.hip, which stay as the fallback for spatially strided views.
 // Reference: nn.BatchNorm2d in training mode + the activation of Conv (nn/modules/conv.py:25-42) and their autograd.
@@ -62,21 +63,23 @@ template <int V> __device__ __forceinline__ void ldp(const float* p, float (&o)[
   for (int j = 0; j < V; j += 4) { const f32x4 t = *(const f32x4*)(p + j); o[j] = t[0]; o[j + 1] = t[1]; o[j + 2] = t[2]; o[j + 3] = t[3]; }
 }
 
-// per-channel partial sums of (f0, f1) over this workgroup's pixel range -> partial[split][c][2] (double); F: (pixel, c0) -> two float[V]
-template <int V, typename F>
+// per-channel partial sums of (f0, f1) over this workgroup's pixel range -> partial[split][c][2] (double); F: (pixel, c0) -> two ACC[V].
+// ACC = float: per-thread fp32 sums, widened when the threads are combined (the backward sums: g and g * xhat are centred).  ACC = double: the
+// statistics pass, whose sum of squares must not round before mean^2 is subtracted from it - see bnf_stats_kernel.
+template <int V, typename ACC, typename F>
 __device__ __forceinline__ void bnf_reduce(long npix, int C, double* partial, F f) {
   const int Q = C / V;
   const int PL = 256 / (Q < 256 ? Q : 256);                      // pixel lanes per pass (Q <= 256)
   const int q = threadIdx.x % Q, pl = threadIdx.x / Q;
   const int split = blockIdx.x;
   const long p0 = split * npix / gridDim.x, p1 = (split + 1) * npix / gridDim.x;     // gridDim.x = number of pixel splits (a multiple of 16, <= BNF_SPLITS)
-  float s0[V], s1[V];
+  ACC s0[V], s1[V];
 #pragma unroll
-  for (int j = 0; j < V; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+  for (int j = 0; j < V; ++j) { s0[j] = 0; s1[j] = 0; }
   if (pl < PL) {
     long p = p0 + pl;
     for (; p + 3 * PL < p1; p += 4 * PL) {
-      float a[4][V], b[4][V];
+      ACC a[4][V], b[4][V];
 #pragma unroll
       for (int u = 0; u < 4; ++u) f(p + u * PL, q * V, a[u], b[u]);
 #pragma unroll
@@ -85,13 +88,13 @@ __device__ __forceinline__ void bnf_reduce(long npix, int C, double* partial, F 
         for (int j = 0; j < V; ++j) { s0[j] += a[u][j]; s1[j] += b[u][j]; }
     }
     for (; p < p1; p += PL) {
-      float a[V], b[V];
+      ACC a[V], b[V];
       f(p, q * V, a, b);
 #pragma unroll
       for (int j = 0; j < V; ++j) { s0[j] += a[j]; s1[j] += b[j]; }
     }
   }
-  __shared__ float red[2][V][256];
+  __shared__ ACC red[2][V][256];
 #pragma unroll
   for (int j = 0; j < V; ++j) { red[0][j][threadIdx.x] = s0[j]; red[1][j][threadIdx.x] = s1[j]; }
   __syncthreads();
@@ -104,12 +107,15 @@ __device__ __forceinline__ void bnf_reduce(long npix, int C, double* partial, F 
   }
 }
 
+// sum y and sum y^2 in double from the first addition on: y * y of an fp32 (or bf16) value is exact in double, so var = E[y^2] - mean^2 in the final
+// kernel loses (mean/std)^2 of 2^-53.  With fp32 per-thread sums it lost (mean/std)^2 of 2^-24: rstd off by 1e-3 at mean = 512 std.
 template <typename T, int V>
 __global__ __launch_bounds__(256) void bnf_stats_kernel(BnfView y, long npix, int C, double* partial) {
-  bnf_reduce<V>(npix, C, partial, [&](long p, int c0, float (&a)[V], float (&b)[V]) {
-    ldv<T, V>((const T*)y.p + p * y.pix + c0, a);
+  bnf_reduce<V, double>(npix, C, partial, [&](long p, int c0, double (&a)[V], double (&b)[V]) {
+    float v[V];
+    ldv<T, V>((const T*)y.p + p * y.pix + c0, v);
 #pragma unroll
-    for (int j = 0; j < V; ++j) b[j] = a[j] * a[j];
+    for (int j = 0; j < V; ++j) { a[j] = (double)v[j]; b[j] = a[j] * a[j]; }
   });
 }
 
@@ -160,7 +166,7 @@ __global__ __launch_bounds__(256) void bnf_bwd_partial_kernel(BnfView gz, BnfVie
     ga[j] = mean ? gamma[cq + j] : 0.f; be[j] = beta ? beta[cq + j] : 0.f;
   }
   const bool bn = mean != nullptr;
-  bnf_reduce<V>(npix, C, partial, [&](long p, int c0, float (&a)[V], float (&b)[V]) {
+  bnf_reduce<V, float>(npix, C, partial, [&](long p, int c0, float (&a)[V], float (&b)[V]) {
     float v[V], gv[V];
     ldv<T, V>((const T*)y.p + p * y.pix + c0, v);
     ldv<T, V>((const T*)gz.p + p * gz.pix + c0, gv);

@@ -34,6 +34,11 @@ static inline bool view_nhwc(const mgdt_view* v) { return v->sc == 1; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t dtype_size(int dt) { return dt == MGDT_BF16 ? 2 : 4; }
 
+// GroupNorm's double partial sums partial[n][GN_SPLITS][c][2] (tood.hip), which the forward, mgdt_gn_affine and mgdt_gn_bwd_coef (tood_train.hip) share
+#define GN_SPLITS 16
+size_t mgdt_gn_partial_bytes(int n, int c);
+bool mgdt_gn_partial_sums(const mgdt_view* a, const mgdt_view* b, double* partial, int dtype, hipStream_t st);
+
 // What the host decided about one launch of the LDS-staged 3x3 kernel (mgdt_conv3x3_lds_plan in conv3x3_lds.hip; reported by mgdt_conv2d_route)
 struct C3Plan { int NBW, MT, waves, ncg, nwg, tiles_x, tiles_per_img, ntiles, XP; size_t lds; long extx, exty; };
 

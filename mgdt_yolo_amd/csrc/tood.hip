@@ -13,85 +13,135 @@ static inline bool nhwc4(const mgdt_view* v, int dtype) {
 }
 
 // ------------------------------------------------------------------------------------------------ GroupNorm (+ activation)
-#define GN_SPLITS 16
-// partial[n][split][c][2] = {sum, sum of squares} over a band of rows (fixed order -> deterministic)
-template <typename T>
-__global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, long sn, long sh, long sw, int H, int W, int C, float* __restrict__ partial) {
+// (GN_SPLITS and the two shared prototypes: common.h)
+// partial[n][split][c][2] (double) = {sum a, sum a*b} over a band of rows (fixed order -> deterministic); PAIR = false: b = a, the statistics
+// {sum x, sum x^2}; PAIR = true: the backward sums {sum g, sum g*y}.  The sums are kept in double from the first addition on: the product of two
+// fp32 values is exact in double, so E[x^2] - mean^2 formed from them in the finalise kernels loses (mean/std)^2 of 2^-53, not of 2^-24.
+// one thread's share of a band: the pixels p = first, first + step, ... < npix of the rows from r0 on, four loads in flight, the terms added in the
+// order of p (32-bit pixel arithmetic: the host refuses maps of 2^31 pixels).  x / x2 point at the thread's channel quad of image n.
+template <typename T, bool PAIR>
+__device__ __forceinline__ void gn_band_sums(const T* __restrict__ x, long sh, long sw, const T* __restrict__ x2, long sh2, long sw2, int r0, int W, int first,
+                                             int step, int npix, double (&s1)[4], double (&s2)[4]) {
+  auto at = [&](int p, f32x4& v, f32x4& u) __attribute__((always_inline)) {
+    const int dy = p / W, yy = r0 + dy, xx = p - dy * W;
+    v = load4<T>(x + yy * sh + xx * sw);
+    u = PAIR ? load4<T>(x2 + yy * sh2 + xx * sw2) : v;
+  };
+  auto add = [&](const f32x4& v, const f32x4& u) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s1[j] += (double)v[j]; s2[j] = fma((double)v[j], (double)u[j], s2[j]); }
+  };
+  int p = first;
+  for (; p + 3 * step < npix; p += 4 * step) {
+    f32x4 v[4], u[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) at(p + k * step, v[k], u[k]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) add(v[k], u[k]);
+  }
+  for (; p < npix; p += step) { f32x4 v, u; at(p, v, u); add(v, u); }
+}
+
+template <typename T, bool PAIR>
+__global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, long sn, long sh, long sw, const T* __restrict__ x2, long sn2, long sh2, long sw2,
+                                                         int H, int W, int C, double* __restrict__ partial) {
   const int n = blockIdx.x, split = blockIdx.y;
   const int Q = C / 4;
   const int r0 = (int)((long)split * H / GN_SPLITS), r1 = (int)((long)(split + 1) * H / GN_SPLITS);
-  const long npix = (long)(r1 - r0) * W;
+  const int npix = (r1 - r0) * W;
   for (int q = threadIdx.x; q < Q; q += 256) {        // (channel quads are few: C <= 1024 in the heads)
-    f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
-    for (long p = 0; p < npix; ++p) {
-      const int yy = r0 + (int)(p / W), xx = (int)(p % W);
-      const f32x4 v = load4<T>(x + n * sn + yy * sh + xx * sw + q * 4);
-      s1 += v; s2 += v * v;
-    }
-    float* o = partial + (((long)n * GN_SPLITS + split) * C + q * 4) * 2;
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    gn_band_sums<T, PAIR>(x + n * sn + q * 4, sh, sw, PAIR ? x2 + n * sn2 + q * 4 : nullptr, sh2, sw2, r0, W, 0, 1, npix, s1, s2);
+    double* o = partial + (((long)n * GN_SPLITS + split) * C + q * 4) * 2;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { o[2 * j] = s1[j]; o[2 * j + 1] = s2[j]; }
   }
 }
 
 // the same reduction with pixels spread over the threads of a block (used when there are many pixels per band)
-template <typename T>
-__global__ __launch_bounds__(256) void gn_partial_wide_kernel(const T* __restrict__ x, long sn, long sh, long sw, int H, int W, int C,
-                                                              float* __restrict__ partial) {
+template <typename T, bool PAIR>
+__global__ __launch_bounds__(256) void gn_partial_wide_kernel(const T* __restrict__ x, long sn, long sh, long sw, const T* __restrict__ x2, long sn2, long sh2,
+                                                              long sw2, int H, int W, int C, double* __restrict__ partial) {
   const int n = blockIdx.x, split = blockIdx.y;
   const int Q = C / 4, PR = 256 / Q;                    // Q <= 64: PR >= 4 pixel lanes
   const int q = threadIdx.x % Q, pl = threadIdx.x / Q;
   const int r0 = (int)((long)split * H / GN_SPLITS), r1 = (int)((long)(split + 1) * H / GN_SPLITS);
-  const long npix = (long)(r1 - r0) * W;
-  f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
-  if (pl < PR)
-    for (long p = pl; p < npix; p += PR) {
-      const int yy = r0 + (int)(p / W), xx = (int)(p % W);
-      const f32x4 v = load4<T>(x + n * sn + yy * sh + xx * sw + q * 4);
-      s1 += v; s2 += v * v;
-    }
-  __shared__ float red[2][4][256];
+  const int npix = (r1 - r0) * W;
+  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+  if (pl < PR) gn_band_sums<T, PAIR>(x + n * sn + q * 4, sh, sw, PAIR ? x2 + n * sn2 + q * 4 : nullptr, sh2, sw2, r0, W, pl, PR, npix, s1, s2);
+  __shared__ double red[2][4][256];
 #pragma unroll
   for (int j = 0; j < 4; ++j) { red[0][j][threadIdx.x] = s1[j]; red[1][j][threadIdx.x] = s2[j]; }
   __syncthreads();
   if (threadIdx.x < Q * 4) {
     const int qq = threadIdx.x / 4, j = threadIdx.x % 4;
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int r = 0; r < PR; ++r) { a += red[0][j][r * Q + qq]; b += red[1][j][r * Q + qq]; }
-    float* o = partial + (((long)n * GN_SPLITS + split) * C + qq * 4 + j) * 2;
+    double* o = partial + (((long)n * GN_SPLITS + split) * C + qq * 4 + j) * 2;
     o[0] = a; o[1] = b;
   }
 }
 
-// A[n][c] = gamma[c] * rstd(group), B[n][c] = beta[c] - mean(group) * A  (biased variance, eps inside the sqrt: nn.GroupNorm)
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          int C, int G, float count, float eps, float* __restrict__ AB) {
-  extern __shared__ float sm[];   // [C][2] channel sums, then [G][2] mean / rstd
-  float* cs = sm;
-  float* gs = sm + 2 * C;
+// {sum a, sum a*b} (b = NULL: a*a) of 4-aligned NHWC views -> partial[n][GN_SPLITS][c][2] (double).  Shared with tood_train.hip.
+size_t mgdt_gn_partial_bytes(int n, int c) { return (size_t)n * GN_SPLITS * c * 2 * sizeof(double); }
+bool mgdt_gn_partial_sums(const mgdt_view* a, const mgdt_view* b, double* partial, int dtype, hipStream_t st) {
+  if (!nhwc4(a, dtype) || a->c > 4096 || (long)a->h * a->w >= 0x7fff0000L || (b && (!nhwc4(b, dtype) || b->n != a->n || b->h != a->h || b->w != a->w || b->c != a->c))) return false;
+  const dim3 grid(a->n, GN_SPLITS);
+  const bool wide = a->c / 4 <= 64;
+#define GN_PARTIAL(K, PAIR)                                                                                                              \
+  MGDT_DISPATCH_DTYPE(dtype, (K<T, PAIR><<<grid, 256, 0, st>>>((const T*)a->p, a->sn, a->sh, a->sw, PAIR ? (const T*)b->p : nullptr, PAIR ? b->sn : 0, \
+                                                               PAIR ? b->sh : 0, PAIR ? b->sw : 0, a->h, a->w, a->c, partial)))
+  if (b) { if (wide) GN_PARTIAL(gn_partial_wide_kernel, true); else GN_PARTIAL(gn_partial_kernel, true); }
+  else { if (wide) GN_PARTIAL(gn_partial_wide_kernel, false); else GN_PARTIAL(gn_partial_kernel, false); }
+#undef GN_PARTIAL
+  return true;
+}
+
+// A[n][c] = gamma[c] * rstd(group), B[n][c] = beta[c] - mean(group) * A  (biased variance, eps inside the sqrt: nn.GroupNorm).  Everything up to
+// the two results is double.  AB: the pairs [n][c][2] of the forward kernel; or A, B apart with the fp32 mean / rstd per (image, group) and the
+// same two in double (stats[n][G][2]) for the backward coefficients.
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ partial, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          int C, int G, double count, float eps, float* __restrict__ AB, float* __restrict__ A,
+                                                          float* __restrict__ B, float* __restrict__ mean, float* __restrict__ rstd,
+                                                          double* __restrict__ stats) {
+  extern __shared__ double smd[];   // [C][2] channel sums, then [G][2] mean / rstd
+  double* cs = smd;
+  double* gs = smd + 2 * C;
   const int n = blockIdx.x, cg = C / G;
   for (int c = threadIdx.x; c < C; c += 256) {
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int sp = 0; sp < GN_SPLITS; ++sp) {
-      const float* p = partial + (((long)n * GN_SPLITS + sp) * C + c) * 2;
+      const double* p = partial + (((long)n * GN_SPLITS + sp) * C + c) * 2;
       a += p[0]; b += p[1];
     }
     cs[2 * c] = a; cs[2 * c + 1] = b;
   }
   __syncthreads();
   for (int g = threadIdx.x; g < G; g += 256) {
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int c = g * cg; c < (g + 1) * cg; ++c) { a += cs[2 * c]; b += cs[2 * c + 1]; }
-    const float mean = a / (count * cg), var = fmaxf(b / (count * cg) - mean * mean, 0.f);
-    gs[2 * g] = mean; gs[2 * g + 1] = 1.f / sqrtf(var + eps);
+    const double m = a / (count * cg), var = fmax(b / (count * cg) - m * m, 0.0), r = 1.0 / sqrt(var + (double)eps);
+    gs[2 * g] = m; gs[2 * g + 1] = r;
+    if (mean) { mean[(long)n * G + g] = (float)m; rstd[(long)n * G + g] = (float)r; }
+    if (stats) { stats[((long)n * G + g) * 2] = m; stats[((long)n * G + g) * 2 + 1] = r; }
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {
     const int g = c / cg;
-    const float a = gamma[c] * gs[2 * g + 1];
-    AB[((long)n * C + c) * 2] = a;
-    AB[((long)n * C + c) * 2 + 1] = beta[c] - gs[2 * g] * a;
+    const double a = (double)gamma[c] * gs[2 * g + 1];
+    const float bb = (float)((double)beta[c] - gs[2 * g] * a);
+    if (AB) { AB[((long)n * C + c) * 2] = (float)a; AB[((long)n * C + c) * 2 + 1] = bb; }
+    else { A[(long)n * C + c] = (float)a; B[(long)n * C + c] = bb; }
   }
+}
+
+// launches gn_finalize_kernel; C > 4064 needs more than 64 KiB of dynamic LDS (the opt-in is idempotent, same value from every caller)
+static bool gn_finalize(const double* partial, const float* gamma, const float* beta, int n, int C, int G, double count, float eps, float* AB, float* A, float* B,
+                        float* mean, float* rstd, double* stats, hipStream_t st) {
+  const size_t lds = (size_t)(2 * C + 2 * G) * sizeof(double);
+  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)gn_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+  gn_finalize_kernel<<<n, 256, lds, st>>>(partial, gamma, beta, C, G, count, eps, AB, A, B, mean, rstd, stats);
+  return true;
 }
 
 template <typename T>
@@ -110,25 +160,43 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, long xsn, long xsh, lon
   }
 }
 
-extern "C" size_t mgdt_groupnorm_workspace_bytes(int n, int c) { return ((size_t)n * GN_SPLITS * c * 2 + (size_t)n * c * 2) * sizeof(float); }
+extern "C" size_t mgdt_groupnorm_workspace_bytes(int n, int c) { return mgdt_gn_partial_bytes(n, c) + (size_t)n * c * 2 * sizeof(float); }
 
 extern "C" int mgdt_groupnorm_fwd(const mgdt_view* x, const float* gamma, const float* beta, int groups, float eps, int act, void* ws, const mgdt_view* y,
                                   int dtype, mgdt_stream s) {
   if (!view_ok(x) || !view_ok(y) || !gamma || !beta || !ws) MGDT_FAIL(MGDT_BAD_ARG, "groupnorm: null/empty argument");
   if (!nhwc4(x, dtype) || !nhwc4(y, dtype) || x->n != y->n || x->h != y->h || x->w != y->w || x->c != y->c || groups < 1 || x->c % groups || x->c > 4096)
     MGDT_FAIL(MGDT_BAD_SHAPE, "groupnorm: matching NHWC views, c%%4==0, c%%groups==0");
+  if ((uintptr_t)ws % sizeof(double)) MGDT_FAIL(MGDT_BAD_ARG, "groupnorm: workspace not 8-byte aligned");
   hipStream_t st = (hipStream_t)s;
-  float* partial = (float*)ws;
-  float* AB = partial + (size_t)x->n * GN_SPLITS * x->c * 2;
+  double* partial = (double*)ws;
+  float* AB = (float*)((char*)ws + mgdt_gn_partial_bytes(x->n, x->c));
   const int Q = x->c / 4;
-  if (Q <= 64) MGDT_DISPATCH_DTYPE(dtype, (gn_partial_wide_kernel<T><<<dim3(x->n, GN_SPLITS), 256, 0, st>>>((const T*)x->p, x->sn, x->sh, x->sw, x->h, x->w, x->c, partial)));
-  else MGDT_DISPATCH_DTYPE(dtype, (gn_partial_kernel<T><<<dim3(x->n, GN_SPLITS), 256, 0, st>>>((const T*)x->p, x->sn, x->sh, x->sw, x->h, x->w, x->c, partial)));
-  gn_finalize_kernel<<<x->n, 256, (size_t)(2 * x->c + 2 * groups) * sizeof(float), st>>>(partial, gamma, beta, x->c, groups, (float)x->h * x->w, eps, AB);
+  if (!mgdt_gn_partial_sums(x, nullptr, partial, dtype, st)) MGDT_FAIL(MGDT_BAD_SHAPE, "groupnorm: 4-aligned NHWC view, c <= 4096, h*w < 2^31 - 2^16");
+  if (!gn_finalize(partial, gamma, beta, x->n, x->c, groups, (double)x->h * x->w, eps, AB, nullptr, nullptr, nullptr, nullptr, nullptr, st))
+    MGDT_FAIL(MGDT_LAUNCH_FAIL, "groupnorm: hipFuncSetAttribute");
   const long total = (long)x->n * x->h * x->w * Q;
   const int grid = (int)std::min<long>((total + 255) / 256, 8192);
   MGDT_DISPATCH_DTYPE(dtype, (gn_apply_kernel<T><<<grid, 256, 0, st>>>((const T*)x->p, x->sn, x->sh, x->sw, AB, act, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w,
                                                                         x->c, total)));
   MGDT_CHECK_LAUNCH("groupnorm_fwd");
+  return MGDT_OK;
+}
+
+// GroupNorm of the conv output y as the per-(image, channel) affine u = y*A + B (the training path): the forward's statistics, with mean / rstd kept.
+// ws: mgdt_gn_affine_workspace_bytes; its LAST n*groups*2 doubles hold (mean, rstd) per (image, group) in double for mgdt_gn_bwd_coef.
+extern "C" size_t mgdt_gn_affine_workspace_bytes(int n, int c, int groups) { return mgdt_gn_partial_bytes(n, c) + (size_t)n * groups * 2 * sizeof(double); }
+extern "C" int mgdt_gn_affine(const mgdt_view* y, const float* gamma, const float* beta, int groups, float eps, float* mean_ng, float* rstd_ng, float* A, float* B,
+                              void* ws, int dtype, mgdt_stream s) {
+  if (!view_ok(y) || !gamma || !beta || !mean_ng || !rstd_ng || !A || !B || !ws || (uintptr_t)ws % sizeof(double)) MGDT_FAIL(MGDT_BAD_ARG, "gn_affine: null pointer");
+  if (groups < 1 || groups > 256 || y->c % groups) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_affine: c=%d groups=%d", y->c, groups);
+  hipStream_t st = (hipStream_t)s;
+  double* partial = (double*)ws;
+  double* stats = (double*)((char*)ws + mgdt_gn_partial_bytes(y->n, y->c));
+  if (!mgdt_gn_partial_sums(y, nullptr, partial, dtype, st)) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_affine: 4-aligned NHWC view, c <= 4096");
+  if (!gn_finalize(partial, gamma, beta, y->n, y->c, groups, (double)y->h * y->w, eps, nullptr, A, B, mean_ng, rstd_ng, stats, st))
+    MGDT_FAIL(MGDT_LAUNCH_FAIL, "gn_affine: hipFuncSetAttribute");
+  MGDT_CHECK_LAUNCH("gn_affine");
   return MGDT_OK;
 }
 

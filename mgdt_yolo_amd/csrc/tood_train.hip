@@ -1,7 +1,7 @@
 // Training side of the TOODHead (reference nn/modules/head.py:466-572, block.py:401-432, mmcv ModulatedDeformConv2d): the adjoints that the
 // conv / reduction kernels of train.hip do not already cover.
 //   GroupNorm(16) + act backward   : GN is a per-(image, channel) affine u = y*A + B of the conv output; the backward needs the sums
-//                                    S1 = sum_hw g_u, S2 = sum_hw g_u*y (mgdt_nc_reduce) and then dy = g_u*P + y*Q + R with per-(image, channel)
+//                                    S1 = sum_hw g_u, S2 = sum_hw g_u*y (double sums) and then dy = g_u*P + y*Q + R with per-(image, channel)
 //                                    coefficients (mgdt_gn_affine, mgdt_nc_affine_act_bwd, mgdt_gn_bwd_coef, mgdt_nc_axpby)
 //   layer attention backward       : the tiny GAP -> 1x1 -> ReLU -> 1x1 -> sigmoid chain per image (mgdt_tood_layer_attn_bwd)
 //   probability gate backward      : d(x * sigmoid(l)) (mgdt_pixel_gate_bwd)
@@ -26,37 +26,8 @@ __device__ __forceinline__ float tt_act_grad(float u, int act) {
 }
 
 // ------------------------------------------------------------------------------------------------ GroupNorm as a per-(image, channel) affine
-// Sy = sum_hw y, Syy = sum_hw y^2 (fp32 [n][c]).  mean / rstd per (image, group) (biased variance E[y^2] - mean^2, the forward kernel's form);
-// A = gamma * rstd, B = beta - mean * rstd * gamma.
-__global__ __launch_bounds__(256) void gn_affine_kernel(const float* __restrict__ Sy, const float* __restrict__ Syy, int C, int hw, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, int G, float eps, float* __restrict__ mean, float* __restrict__ rstd,
-                                                        float* __restrict__ A, float* __restrict__ B) {
-  __shared__ float sm[2][256];
-  const int n = blockIdx.x, cpg = C / G;
-  for (int g = threadIdx.x; g < G; g += 256) {
-    double s = 0.0, ss = 0.0;
-    for (int j = 0; j < cpg; ++j) { s += Sy[(long)n * C + g * cpg + j]; ss += Syy[(long)n * C + g * cpg + j]; }
-    const double cnt = (double)cpg * hw, m = s / cnt;
-    double var = ss / cnt - m * m;
-    if (var < 0.0) var = 0.0;
-    sm[0][g] = (float)m; sm[1][g] = (float)(1.0 / sqrt(var + (double)eps));
-    mean[(long)n * G + g] = sm[0][g]; rstd[(long)n * G + g] = sm[1][g];
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float m = sm[0][c / cpg], r = sm[1][c / cpg];
-    A[(long)n * C + c] = gamma[c] * r;
-    B[(long)n * C + c] = beta[c] - m * r * gamma[c];
-  }
-}
-extern "C" int mgdt_gn_affine(const float* Sy, const float* Syy, int n, int c, int hw, const float* gamma, const float* beta, int groups, float eps,
-                              float* mean_ng, float* rstd_ng, float* A, float* B, mgdt_stream s) {
-  if (!Sy || !Syy || !gamma || !beta || !mean_ng || !rstd_ng || !A || !B) MGDT_FAIL(MGDT_BAD_ARG, "gn_affine: null pointer");
-  if (n < 1 || c < 1 || hw < 1 || groups < 1 || groups > 256 || c % groups) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_affine: c=%d groups=%d", c, groups);
-  gn_affine_kernel<<<n, 256, 0, (hipStream_t)s>>>(Sy, Syy, c, hw, gamma, beta, groups, eps, mean_ng, rstd_ng, A, B);
-  MGDT_CHECK_LAUNCH("gn_affine");
-  return MGDT_OK;
-}
+// mgdt_gn_affine (mean / rstd per (image, group), A = gamma * rstd, B = beta - mean * rstd * gamma) lives in tood.hip beside the forward kernel whose
+// double-precision statistics it shares; the backward sums below use the same partial-sum kernels (mgdt_gn_partial_sums, GN_SPLITS: common.h).
 
 // gu = g * act'(y * A[n][c] + B[n][c])   (A, B NULL: u = y - with act = ReLU and y the layer's OUTPUT this is the ReLU mask)
 template <typename T>
@@ -90,37 +61,84 @@ extern "C" int mgdt_nc_affine_act_bwd(const mgdt_view* g, const mgdt_view* y, co
   return MGDT_OK;
 }
 
-// S1 = sum_hw g_u, S2 = sum_hw g_u * y.  With xhat = (y - mean) * rstd:  sum_hw g_u*xhat = rstd * (S2 - mean*S1).
+// GroupNorm's gu = g * act'(u) with u = (y - mean) * (rstd * gamma) + beta evaluated in double from mgdt_gn_affine's double (mean, rstd) and rounded
+// once to fp32: u = y*A + B with fp32 A, B is off by (|mean|/std) of 2^-24 - at mean 1, std 2^-10 by 2e-5 - which decides the bf16 rounding of
+// the stored gu the other way on one element in some hundreds, and each such element moves its dy by gamma * rstd times one bf16 step.
+template <typename T>
+__global__ __launch_bounds__(256) void gn_act_grad_kernel(const mgdt_view g, const mgdt_view y, const double* __restrict__ stats, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, int G, int act, const mgdt_view gu) {
+  const int Q = y.c >> 2, cpg = y.c / G;
+  const long total = (long)y.n * y.h * y.w * Q;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int c = (int)(i % Q) * 4;
+    long t = i / Q;
+    const int w = (int)(t % y.w);
+    t /= y.w;
+    const int h = (int)(t % y.h);
+    const long n = t / y.h;
+    const f32x4 gv = load4<T>(TT_AT(const T, g, n, h, w, c)), yv = load4<T>(TT_AT(const T, y, n, h, w, c));
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double* st = stats + (n * G + (c + j) / cpg) * 2;
+      const float u = (float)fma((double)yv[j] - st[0], st[1] * (double)gamma[c + j], (double)beta[c + j]);
+      o[j] = gv[j] * tt_act_grad(u, act);
+    }
+    store4<T>(TT_AT(T, gu, n, h, w, c), o);
+  }
+}
+extern "C" int mgdt_gn_act_grad(const mgdt_view* g, const mgdt_view* y, const double* stats_ng, const float* gamma, const float* beta, int groups, int act,
+                                const mgdt_view* gu, int dtype, mgdt_stream s) {
+  if (!view_ok(g) || !view_ok(y) || !view_ok(gu) || !stats_ng || !gamma || !beta) MGDT_FAIL(MGDT_BAD_ARG, "gn_act_grad: null/empty argument");
+  if (!tt_v4(g, dtype) || !tt_v4(y, dtype) || !tt_v4(gu, dtype) || !tt_same(g, y) || !tt_same(gu, y) || groups < 1 || y->c % groups)
+    MGDT_FAIL(MGDT_BAD_SHAPE, "gn_act_grad: matching 4-aligned NHWC views, c%%groups==0");
+  const long nq = (long)y->n * y->h * y->w * (y->c / 4);
+  MGDT_DISPATCH_DTYPE(dtype, (gn_act_grad_kernel<T><<<tt_grid(nq), 256, 0, (hipStream_t)s>>>(*g, *y, stats_ng, gamma, beta, groups, act, *gu)));
+  MGDT_CHECK_LAUNCH("gn_act_grad");
+  return MGDT_OK;
+}
+
+// S1 = sum_hw g_u, S2 = sum_hw g_u * y, both summed in double (partial[n][GN_SPLITS][c][2]).  With xhat = (y - mean) * rstd:
+//   sum_hw g_u*xhat = rstd * (S2 - mean*S1), the difference formed in double with the double mean of mgdt_gn_affine (stats[n][G][2] = mean, rstd): it
+//   cancels (mean/std) of 2^-53, where fp32 sums and an fp32 mean lost (mean/std) of 2^-24.
 //   dgamma[c] = sum_n rstd*(S2 - mean*S1),  dbeta[c] = sum_n S1
 //   M1[n,g] = mean over the group of g_u*gamma,  M2[n,g] = mean over the group of g_u*gamma*xhat
 //   dy = g_u * P + y * Q + R,  P = gamma*rstd,  Q = -rstd^2 * M2,  R = -rstd*M1 + mean*rstd^2*M2
-__global__ __launch_bounds__(256) void gn_bwd_coef_kernel(const float* __restrict__ S1, const float* __restrict__ S2, const float* __restrict__ mean,
-                                                          const float* __restrict__ rstd, const float* __restrict__ gamma, int C, int hw, int G,
-                                                          float* __restrict__ P, float* __restrict__ Q, float* __restrict__ R, float* __restrict__ pimg) {
-  __shared__ float sm[2][256];
+__global__ __launch_bounds__(256) void gn_bwd_coef_kernel(const double* __restrict__ partial, const double* __restrict__ stats, const float* __restrict__ gamma, int C,
+                                                          int hw, int G, float* __restrict__ P, float* __restrict__ Q, float* __restrict__ R,
+                                                          float* __restrict__ pimg) {
+  __shared__ double sm[2][256];
   const int n = blockIdx.x, cpg = C / G;
+  // per channel: S1 and the centred sum rstd * (S2 - mean*S1) -> pimg (this block's rows), which the group means below read back
+  for (int c = threadIdx.x; c < C; c += 256) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int sp = 0; sp < GN_SPLITS; ++sp) {
+      const double* p = partial + (((long)n * GN_SPLITS + sp) * C + c) * 2;
+      s1 += p[0]; s2 += p[1];
+    }
+    const double m = stats[((long)n * G + c / cpg) * 2], r = stats[((long)n * G + c / cpg) * 2 + 1];
+    const double cen = r * (s2 - m * s1);
+    pimg[((long)n * 2) * C + c] = (float)cen;
+    pimg[((long)n * 2 + 1) * C + c] = (float)s1;
+  }
+  __syncthreads();
   for (int g = threadIdx.x; g < G; g += 256) {
-    const float m = mean[(long)n * G + g], r = rstd[(long)n * G + g];
     double a = 0.0, b = 0.0;
     for (int j = 0; j < cpg; ++j) {
       const int c = g * cpg + j;
-      const float s1 = S1[(long)n * C + c], s2 = S2[(long)n * C + c];
-      a += (double)(gamma[c] * s1);
-      b += (double)(gamma[c] * r * (s2 - m * s1));
+      a += (double)gamma[c] * (double)pimg[((long)n * 2 + 1) * C + c];
+      b += (double)gamma[c] * (double)pimg[((long)n * 2) * C + c];
     }
     const double cnt = (double)cpg * hw;
-    sm[0][g] = (float)(a / cnt); sm[1][g] = (float)(b / cnt);
+    sm[0][g] = a / cnt; sm[1][g] = b / cnt;
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {
     const int g = c / cpg;
-    const float m = mean[(long)n * G + g], r = rstd[(long)n * G + g], M1 = sm[0][g], M2 = sm[1][g];
-    const float s1 = S1[(long)n * C + c], s2 = S2[(long)n * C + c];
-    P[(long)n * C + c] = gamma[c] * r;
-    Q[(long)n * C + c] = -r * r * M2;
-    R[(long)n * C + c] = -r * M1 + m * r * r * M2;
-    pimg[((long)n * 2) * C + c] = r * (s2 - m * s1);
-    pimg[((long)n * 2 + 1) * C + c] = s1;
+    const double m = stats[((long)n * G + g) * 2], r = stats[((long)n * G + g) * 2 + 1], M1 = sm[0][g], M2 = sm[1][g];
+    P[(long)n * C + c] = (float)((double)gamma[c] * r);
+    Q[(long)n * C + c] = (float)(-r * r * M2);
+    R[(long)n * C + c] = (float)(-r * M1 + m * r * r * M2);
   }
 }
 // out[i] (+)= sum_n pimg[n * stride + i], i < count
@@ -131,16 +149,22 @@ __global__ void tt_sum_rows_kernel(const float* __restrict__ pimg, int N, long s
   for (int n = 0; n < N; ++n) s += pimg[(long)n * stride + i];
   out[i] = accumulate ? out[i] + s : s;
 }
-extern "C" size_t mgdt_gn_bwd_workspace_bytes(int n, int c) { return (size_t)n * 2 * c * sizeof(float); }
-extern "C" int mgdt_gn_bwd_coef(const float* S1, const float* S2, const float* mean_ng, const float* rstd_ng, const float* gamma, int n, int c, int hw, int groups,
-                                float* P, float* Q, float* R, float* dgamma, float* dbeta, int accumulate, void* ws, mgdt_stream s) {
-  if (!S1 || !S2 || !mean_ng || !rstd_ng || !gamma || !P || !Q || !R || !dgamma || !dbeta || !ws) MGDT_FAIL(MGDT_BAD_ARG, "gn_bwd_coef: null pointer");
-  if (n < 1 || c < 1 || hw < 1 || groups < 1 || groups > 256 || c % groups) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_bwd_coef: c=%d groups=%d", c, groups);
+// ws: the double partial sums, then pimg [n][2][c] fp32
+extern "C" size_t mgdt_gn_bwd_workspace_bytes(int n, int c) { return mgdt_gn_partial_bytes(n, c) + (size_t)n * 2 * c * sizeof(float); }
+extern "C" int mgdt_gn_bwd_coef(const mgdt_view* gu, const mgdt_view* y, const double* stats_ng, const float* gamma, int groups, float* P, float* Q, float* R,
+                                float* dgamma, float* dbeta, int accumulate, void* ws, int dtype, mgdt_stream s) {
+  if (!view_ok(gu) || !view_ok(y) || !stats_ng || !gamma || !P || !Q || !R || !dgamma || !dbeta || !ws || (uintptr_t)ws % sizeof(double))
+    MGDT_FAIL(MGDT_BAD_ARG, "gn_bwd_coef: null pointer");
+  const int n = y->n, c = y->c, hw = y->h * y->w;
+  if (groups < 1 || groups > 256 || c % groups) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_bwd_coef: c=%d groups=%d", c, groups);
   hipStream_t st = (hipStream_t)s;
-  gn_bwd_coef_kernel<<<n, 256, 0, st>>>(S1, S2, mean_ng, rstd_ng, gamma, c, hw, groups, P, Q, R, (float*)ws);
+  double* partial = (double*)ws;
+  float* pimg = (float*)((char*)ws + mgdt_gn_partial_bytes(n, c));
+  if (!mgdt_gn_partial_sums(gu, y, partial, dtype, st)) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_bwd_coef: matching 4-aligned NHWC views, c <= 4096");
+  gn_bwd_coef_kernel<<<n, 256, 0, st>>>(partial, stats_ng, gamma, c, hw, groups, P, Q, R, pimg);
   // pimg rows are [n][2][c]: sum over n of the two halves; the halves are contiguous per image, so treat each image's row as 2c values
-  tt_sum_rows_kernel<<<cdiv(c, 256), 256, 0, st>>>((const float*)ws, n, 2L * c, c, dgamma, accumulate);          // first c entries of every row
-  tt_sum_rows_kernel<<<cdiv(c, 256), 256, 0, st>>>((const float*)ws + c, n, 2L * c, c, dbeta, accumulate);       // second c entries
+  tt_sum_rows_kernel<<<cdiv(c, 256), 256, 0, st>>>(pimg, n, 2L * c, c, dgamma, accumulate);          // first c entries of every row
+  tt_sum_rows_kernel<<<cdiv(c, 256), 256, 0, st>>>(pimg + c, n, 2L * c, c, dbeta, accumulate);       // second c entries
   MGDT_CHECK_LAUNCH("gn_bwd_coef");
   return MGDT_OK;
 }

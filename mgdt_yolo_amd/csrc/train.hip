@@ -44,7 +44,8 @@ __device__ __forceinline__ float act_grad(float u, int act) {
 
 // ------------------------------------------------------------------------------------------------ per-channel reductions
 // partial[split][c][2] (double) = sum over the split's pixels of (f0, f1); pixel ranges are fixed -> deterministic.
-template <typename T, typename F>
+// A = the type f hands its two terms over in: float, or double where a term must not round before it is summed (the statistics' y * y).
+template <typename T, typename A = float, typename F>
 __device__ __forceinline__ void channel_reduce(const mgdt_view v, double* partial, F f) {
   // grid: (cdiv(C, CW), RED_SPLITS); block 256 = CW channel lanes x 256/CW pixel lanes; four pixels per thread are read before they are
   // accumulated (in order) so that a thread keeps several requests in flight
@@ -56,20 +57,20 @@ __device__ __forceinline__ void channel_reduce(const mgdt_view v, double* partia
   double s0 = 0.0, s1 = 0.0;
   if (c < v.c) {
     const int HW = v.h * v.w;
-    auto at = [&](int p, float& a0, float& a1) __attribute__((always_inline)) {
+    auto at = [&](int p, A& a0, A& a1) __attribute__((always_inline)) {
       const int n = p / HW, rem = p - n * HW;
       const int yy = rem / v.w, xx = rem - yy * v.w;
       f((long)n * v.sn + (long)yy * v.sh + (long)xx * v.sw + c, (long)n, (long)yy, (long)xx, c, a0, a1);
     };
     int p = p0 + pl;
     for (; p + 3 * PL < p1; p += 4 * PL) {
-      float a0[4], a1[4];
+      A a0[4], a1[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) at(p + u * PL, a0[u], a1[u]);
 #pragma unroll
       for (int u = 0; u < 4; ++u) { s0 += a0[u]; s1 += a1[u]; }
     }
-    for (; p < p1; p += PL) { float a0, a1; at(p, a0, a1); s0 += a0; s1 += a1; }
+    for (; p < p1; p += PL) { A a0, a1; at(p, a0, a1); s0 += a0; s1 += a1; }
   }
   __shared__ double red[2][256];
   red[0][threadIdx.x] = s0;
@@ -86,7 +87,8 @@ __device__ __forceinline__ void channel_reduce(const mgdt_view v, double* partia
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const mgdt_view y, double* partial) {
   const T* p = (const T*)y.p;
-  channel_reduce<T>(y, partial, [&](long off, long, long, long, int, float& a0, float& a1) { float v = (float)p[off]; a0 = v; a1 = v * v; });
+  // y * y in double is exact: the fp32 product rounded away (mean/std)^2 of 2^-24 of the variance before mean^2 was subtracted
+  channel_reduce<T, double>(y, partial, [&](long off, long, long, long, int, double& a0, double& a1) { const double v = (double)(float)p[off]; a0 = v; a1 = v * v; });
 }
 
 // sum of the RED_SPLITS partial rows of 16 channels per workgroup: 16 threads per channel each add 32 rows (loads independent, in flight

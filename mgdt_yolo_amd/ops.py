@@ -825,15 +825,21 @@ def pixel_gate(x, gate, out=None):
 
 
 # ---- TOODHead training (tood_train.hip) ----
-def gn_affine(y, gamma, beta, groups, eps):
-    """GroupNorm of the conv output y as the per-(image, channel) affine u = y*A + B; returns (A, B, mean, rstd) fp32."""
+def _gn_affine(y, gamma, beta, groups, eps):
+    """gn_affine plus the (b, groups, 2) double (mean, rstd) view of its workspace, which gn_bwd_coef centres its sums with."""
     b, c, h, w = y.shape
-    sy, syy = nc_reduce(y), nc_reduce(y, y)
     dev = y.device
     A, B = torch.empty(b, c, dtype=torch.float32, device=dev), torch.empty(b, c, dtype=torch.float32, device=dev)
     mean, rstd = torch.empty(b, groups, dtype=torch.float32, device=dev), torch.empty(b, groups, dtype=torch.float32, device=dev)
-    _launch('gn_affine', 'mgdt_gn_affine', ptr(sy), ptr(syy), b, c, h * w, ptr(gamma), ptr(beta), groups, float(eps), ptr(mean), ptr(rstd), ptr(A), ptr(B), stream())
-    return A, B, mean, rstd
+    ws = torch.empty(L.lib().mgdt_gn_affine_workspace_bytes(b, c, groups), dtype=torch.uint8, device=dev)
+    _launch('gn_affine', 'mgdt_gn_affine', vp(y), ptr(gamma), ptr(beta), groups, float(eps), ptr(mean), ptr(rstd), ptr(A), ptr(B), ptr(ws), dtype_code(y.dtype), stream())
+    return A, B, mean, rstd, ws[ws.numel() - b * groups * 16:].view(torch.float64).view(b, groups, 2)
+
+
+def gn_affine(y, gamma, beta, groups, eps):
+    """GroupNorm of the conv output y as the per-(image, channel) affine u = y*A + B; returns (A, B, mean, rstd) fp32.  The sums of y and y*y are
+    kept in double (mgdt_gn_affine), as in the forward kernel."""
+    return _gn_affine(y, gamma, beta, groups, eps)[:4]
 
 
 def nc_affine_act_bwd(g, y, A, B, act, out=None):
@@ -858,13 +864,14 @@ def nc_axpby(a, sa, b=None, sb=None, shift=None, out=None):
 def gn_act_bwd(g, y, gamma, beta, groups, eps, act, dgamma, dbeta, accumulate=False):
     """Backward of z = act(GroupNorm(y)): returns dy; dgamma / dbeta written or accumulated."""
     b, c, h, w = y.shape
-    A, B, mean, rstd = gn_affine(y, gamma, beta, groups, eps)
-    gu = nc_affine_act_bwd(g, y, A, B, act)
-    s1, s2 = nc_reduce(gu), nc_reduce(gu, y)
+    stats = _gn_affine(y, gamma, beta, groups, eps)[4]
+    gu = like(y)
+    _same(g, y)
+    _launch('gn_act_grad', 'mgdt_gn_act_grad', vp(g), vp(y), ptr(stats), ptr(gamma), ptr(beta), groups, act, vp(gu), dtype_code(y.dtype), stream())
     P, Q, R = (torch.empty(b, c, dtype=torch.float32, device=y.device) for _ in range(3))
     ws = torch.empty(L.lib().mgdt_gn_bwd_workspace_bytes(b, c), dtype=torch.uint8, device=y.device)
-    _launch('gn_bwd_coef', 'mgdt_gn_bwd_coef', ptr(s1), ptr(s2), ptr(mean), ptr(rstd), ptr(gamma), b, c, h * w, groups, ptr(P), ptr(Q), ptr(R), ptr(dgamma), ptr(dbeta),
-            int(accumulate), ptr(ws), stream())
+    _launch('gn_bwd_coef', 'mgdt_gn_bwd_coef', vp(gu), vp(y), ptr(stats), ptr(gamma), groups, ptr(P), ptr(Q), ptr(R), ptr(dgamma), ptr(dbeta), int(accumulate), ptr(ws),
+            dtype_code(y.dtype), stream())
     return nc_axpby(gu, P, y, Q, R, out=gu)
 
 

@@ -777,3 +777,45 @@ def ref_pack_direct(cp):
         w = w * s.view(-1, 1, 1, 1)
         bias = b - g * mu / torch.sqrt(var + eps) + (0 if cb is None else s * cb)
     return w.permute(2, 3, 1, 0).reshape(-1), bias
+
+
+# ------------------------------------------------------------------------------------------------ conditioning ladder (test_conditioning.py)
+# Inputs whose normalisation sets have |mean| / std = R, and the bound that comes from the reference alone: the distance of the same torch functional
+# run in float32 on the CPU to its float64 run (the rule of tests/test_train_modules.py and tests/test_rtdetr.py:fp32_bound).
+def ladder_map(key, shape, R, dt, std=1.0):
+    """(B, C, H, W) fp64 values representable in dt, N(R * std, std) with ONE mean and ONE std for the whole map, so that every channel, every
+    (image, group) and every pixel has |mean| / std = R (negative R: a negative mean).  R = 'const': the near-constant rung, mean 1 and std 2^-10
+    (variance below every eps in use: the clamp at zero and eps are what is exercised).  Every rung of a case shifts and scales the same draw."""
+    gen = _gen('ladder', *key, shape)                      # the same N(0, 1) draw on every rung and in both dtypes
+    if R == 'const':
+        return _q(torch.randn(*shape, generator=gen, dtype=torch.float64) * 2.0 ** -10 + 1.0, dt)
+    return _q(torch.randn(*shape, generator=gen, dtype=torch.float64) * std + R * std, dt)
+
+
+def cond_bounds(r64, r32):
+    """(relative L2 bound, largest-element bound) of an fp32 output: max(2e-5, 8 x d32) and max(1e-4 x max|ref|, 8 x d32_max), d32 / d32_max the
+    relative L2 / largest-element distance of the float32 CPU run r32 to the float64 run r64.  With d32 = 0 this is _close's fp32 bound."""
+    r64, r32 = r64.detach().double(), r32.detach().double().reshape(r64.shape)
+    d = (r32 - r64).abs()
+    return max(2e-5, 8 * d.norm().item() / max(r64.norm().item(), 1e-300)), max(1e-4 * r64.abs().max().item(), 8 * d.max().item())
+
+
+def cond_use(got, r64, r32):
+    """Largest fraction of cond_bounds that got uses (1.0 = at the bound)."""
+    got, r64 = got.detach().double().cpu().reshape(r64.shape), r64.detach().double()
+    rel_b, max_b = cond_bounds(r64, r32)
+    err = (got - r64).abs()
+    return max(err.norm().item() / max(r64.norm().item(), 1e-300) / rel_b, err.max().item() / max(max_b, 1e-300))
+
+
+def cond_check(got, r64, r32, dt, what=''):
+    """fp32 outputs (dt = F32; every fp32 statistic and parameter gradient of a bf16 run included): within cond_bounds.  bf16 outputs: _close's bf16
+    bound unchanged.  Prints the fraction of the bound used first."""
+    if dt != F32:
+        return _check(got, r64, dt, what)
+    g = got.detach().double().cpu().reshape(r64.shape)
+    assert torch.isfinite(g).all(), (what, 'non-finite output')
+    use = cond_use(g, r64, r32)
+    rel_b, max_b = cond_bounds(r64, r32)
+    print(f'{what}: uses {use:.3f} of the fp32 ladder bound (rel L2 <= {rel_b:.2e}, max <= {max_b:.2e})')
+    assert use <= 1.0 or (g == r64.double()).all(), (what, 'share of the bound', use, 'rel L2 bound', rel_b, 'max bound', max_b)
