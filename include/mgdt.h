@@ -52,8 +52,9 @@ int mgdt_conv_pack(const float* w_oihw, const float* conv_bias, const float* bn_
 int mgdt_conv_pack_dgrad(const float* w_oihw, int cin, int cout, int k, int phase, int dtype, void* packed_out, float* bias_out, mgdt_stream s);
 /* Many packs in a few launches (a training step re-packs every convolution after the optimizer moved the weights; the reference has no counterpart:
  * ATen convolutions read nn.Conv2d.weight in place).  One descriptor = the arguments of one mgdt_conv_pack (mode 0) or mgdt_conv_pack_dgrad
- * (mode 1 = stride-1 data gradient, mode 2 + phase = stride-2 phase) or mgdt_conv_pack_stem6 (mode 5 + cin, k = 3, w = the 6x6 weight) call; cin / cout
- * are those of the ORIGINAL convolution. */
+ * (mode 1 = stride-1 data gradient, mode 2 + phase = stride-2 phase) or mgdt_conv_pack_stem6 (mode 5 + cin, k = 3, w = the 6x6 weight) or
+ * mgdt_conv_pack_deconv2x2 (mode 10 + phase, k = 1, w = the (cin, cout, 2, 2) weight, conv_bias = its bias) or mgdt_conv_pack_deconv2x2_dgrad (mode 14 + phase) call; cin / cout are those of the ORIGINAL
+ * convolution. */
 typedef struct mgdt_pack_desc {
   const float* w; const float* conv_bias; const float* bn_gamma; const float* bn_beta; const float* bn_mean; const float* bn_var;
   float bn_eps; int32_t cin, cout, k, dtype, mode;
@@ -403,6 +404,26 @@ int mgdt_nms_masks_fwd(const float* pred, int n, int nc, int nm, int a, float co
  *   no_skip: compute every (detection, tile) pair even when its crop box misses the tile (tests: the skip changes no byte).
  *   mgdt_seg_mask_geometry: geom4 = {tile_h, tile_w, tiles_y, tiles_x} of that launch; 0 when the resampling ratio is not covered. */
 int mgdt_deconv2x2_fwd(const mgdt_view* x, const void* const* packed4, const float* bias, const mgdt_view* y, int dtype, mgdt_stream s);
+/* nn.ConvTranspose2d(cin, cout, 2, 2, 0) as a layer that trains (models/v6/yolov6.yaml rows 11, 16), weight w fp32 [cin][cout][2][2] in place:
+ * mgdt_conv_pack_deconv2x2: panel `phase` = 2*ky + kx of mgdt_deconv2x2_fwd (+ bias_out = the bias, padded) read straight from the live weight, sized by
+ *   mgdt_conv_packed_bytes(cin, cout, 1, dtype); refreshed in place by mgdt_conv_pack_batch descriptors of mode 10 + phase.
+ * mgdt_conv_pack_deconv2x2_dgrad: panel `phase` of the layer's data gradient as a 1x1 convolution cout -> cin over the stride-2 phase view of dy (the composed
+ *   route: dx = sum over the phases of mgdt_conv2d_fwd(x = dy[:, ky::2, kx::2], packed(phase), k 1, y = dx, r1 = dx from the second phase on)), read from the
+ *   live weight, bias_out zeroed; sized by mgdt_conv_packed_bytes(cout, cin, 1, dtype); refreshed by mgdt_conv_pack_batch descriptors of mode 14 + phase.
+ * mgdt_deconv2x2_dgrad: dx[b, y, x, ci] = sum_{ky, kx, co} w[ci][co][ky][kx] * dy[b, 2y+ky, 2x+kx, co] [+ r1] [+ r2]: one GEMM with K = 4 cout on the
+ *   fp32 matrix cores (bf16 values widened exactly, fp32 accumulation, one fixed summation order).  dy = N x 2H x 2W x cout, dx / r1 / r2 = N x H x W x cin,
+ *   all NHWC of `dtype` with channels % 4 == 0; dy's strides % 4 == 0 and its base aligned to 4 elements.  r1 may be dx itself (accumulate).
+ *   MGDT_BAD_SHAPE when w's tile for 16 input channels exceeds 64 KB of LDS (cout > 240).
+ * mgdt_deconv2x2_wgrad: dw[ci][co][ky][kx] = sum_{b, y, x} x[b, y, x, ci] * dy[b, 2y+ky, 2x+kx, co], fp32, in the parameter's layout.  Pixel splits leave
+ *   partial sums in ws (fp32 [mgdt_deconv2x2_wgrad_splits][cin][cout][2][2], mgdt_deconv2x2_wgrad_workspace_bytes); dw != NULL: their sum is written
+ *   (accumulate: added) by one mgdt_wgrad_final_batch job; dw == NULL: partial sums only, for a later mgdt_wgrad_final_batch with n = 4 cin cout and
+ *   nsplit = mgdt_deconv2x2_wgrad_splits(cin, cout) - the same bits.  x and dy as above, both with strides % 4 == 0 and aligned bases. */
+int mgdt_conv_pack_deconv2x2(const float* w, const float* bias, int cin, int cout, int phase, int dtype, void* packed_out, float* bias_out, mgdt_stream s);
+int mgdt_conv_pack_deconv2x2_dgrad(const float* w, int cin, int cout, int phase, int dtype, void* packed_out, float* bias_out, mgdt_stream s);
+int mgdt_deconv2x2_dgrad(const mgdt_view* dy, const float* w, const mgdt_view* r1, const mgdt_view* r2, const mgdt_view* dx, int dtype, mgdt_stream s);
+int mgdt_deconv2x2_wgrad_splits(int cin, int cout);
+size_t mgdt_deconv2x2_wgrad_workspace_bytes(int cin, int cout);
+int mgdt_deconv2x2_wgrad(const mgdt_view* x, const mgdt_view* dy, float* dw, int accumulate, void* ws, int dtype, mgdt_stream s);
 int mgdt_seg_concat_fwd(const float* y, int n, int rows, int a_total, const mgdt_view* const* mc, int n_levels, int nm, float* out, int dtype,
                         mgdt_stream s);
 int mgdt_seg_mask_geometry(int win_h, int win_w, int out_h, int out_w, int* geom4);

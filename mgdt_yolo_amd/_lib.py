@@ -175,6 +175,12 @@ PROTOTYPES = {
     'mgdt_nms_fwd': (_i, [_vp, _i, _i, _i, _f, _f, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'mgdt_nms_masks_fwd': (_i, [_vp, _i, _i, _i, _i, _f, _f, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'mgdt_deconv2x2_fwd': (_i, [VP, _vp, _vp, VP, _i, _vp]),
+    'mgdt_conv_pack_deconv2x2': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'mgdt_conv_pack_deconv2x2_dgrad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'mgdt_deconv2x2_dgrad': (_i, [VP, _vp, VP, VP, VP, _i, _vp]),
+    'mgdt_deconv2x2_wgrad_splits': (_i, [_i, _i]),
+    'mgdt_deconv2x2_wgrad_workspace_bytes': (_sz, [_i, _i]),
+    'mgdt_deconv2x2_wgrad': (_i, [VP, VP, _vp, _i, _vp, _i, _vp]),
     'mgdt_seg_concat_fwd': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     'mgdt_seg_mask_geometry': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     'mgdt_seg_masks_fwd': (_i, [VP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _i, _vp]),

@@ -65,7 +65,9 @@ __global__ void pack_kernel(const float* __restrict__ w, const float* __restrict
     int cin = cp * PE + j, cout = nb * 16 + r;
     float v = 0.f;
     if (tap < KS * KS && cin < Cin && cout < Cout) {
-      if (dgrad == 1) v = w[(((long)cin * Cout + cout) * KS + (KS - 1 - tap / KS)) * KS + (KS - 1 - tap % KS)];   // original layout [cin=co][cout=ci][ky][kx]
+      if (dgrad >= 14) v = w[((long)cout * Cin + cin) * 4 + (dgrad - 14)];        // its data gradient, a 1x1 convolution cout -> cin: the same element, roles swapped
+      else if (dgrad >= 10) v = w[((long)cin * Cout + cout) * 4 + (dgrad - 10)];   // phase panel of a 2x2 / stride 2 transposed convolution: w[cin][cout][2][2]
+      else if (dgrad == 1) v = w[(((long)cin * Cout + cout) * KS + (KS - 1 - tap / KS)) * KS + (KS - 1 - tap % KS)];   // original layout [cin=co][cout=ci][ky][kx]
       else if (dgrad >= 6) v = stem6_weight(w, dgrad - 5, cout, cin, tap);
       else if (dgrad >= 2) {   // stride-2 phase (py, px) of a 3x3 conv: tap (dy', dx') of the dy grid carries w[ky = py + 1 - 2*dy'][kx = px + 1 - 2*dx'] when that exists
         const int py = (dgrad - 2) >> 1, px = (dgrad - 2) & 1;
@@ -278,6 +280,38 @@ extern "C" int mgdt_conv_pack_fp8(const float* w, const float* cb, const float* 
   return MGDT_OK;
 }
 
+// panel (+ bias) of phase 2*ky + kx of nn.ConvTranspose2d(cin, cout, 2, 2, 0): the 1x1 convolution W[:, :, ky, kx]^T, read straight from the live
+// weight w[cin][cout][2][2]; used by mgdt_deconv2x2_fwd.  Sized by mgdt_conv_packed_bytes(cin, cout, 1, dtype).
+extern "C" int mgdt_conv_pack_deconv2x2(const float* w, const float* cb, int cin, int cout, int phase, int dtype, void* packed, float* bias_out, mgdt_stream s) {
+  if (!w || !packed || !bias_out) MGDT_FAIL(MGDT_BAD_ARG, "conv_pack_deconv2x2: null pointer");
+  if (cin < 1 || cout < 1 || phase < 0 || phase > 3 || (dtype != MGDT_F32 && dtype != MGDT_BF16))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "conv_pack_deconv2x2: cin %d cout %d phase %d dtype %d", cin, cout, phase, dtype);
+  int CP, nchunks, NTtot;
+  conv_geometry(cin, cout, 1, dtype, &CP, &nchunks, &NTtot);
+  long total = (long)nchunks * NTtot * 64 * piece_elems(dtype);
+  int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  const FoldArgs fa{cb, nullptr, nullptr, nullptr, nullptr, 0.f, cout, NTtot * 16, bias_out};
+  MGDT_DISPATCH_DTYPE(dtype, (pack_kernel<T><<<grid, 256, 0, (hipStream_t)s>>>(w, nullptr, cin, cout, 1, CP, nchunks, NTtot, (T*)packed, 10 + phase, fa)));
+  MGDT_CHECK_LAUNCH("conv_pack_deconv2x2");
+  return MGDT_OK;
+}
+
+// panel of phase 2*ky + kx of that layer's data gradient: the 1x1 convolution cout -> cin with W[:, :, ky, kx] (dx += W_phase dy_phase), read straight from the
+// live weight; bias_out is zeroed.  Sized by mgdt_conv_packed_bytes(cout, cin, 1, dtype).
+extern "C" int mgdt_conv_pack_deconv2x2_dgrad(const float* w, int cin, int cout, int phase, int dtype, void* packed, float* bias_out, mgdt_stream s) {
+  if (!w || !packed || !bias_out) MGDT_FAIL(MGDT_BAD_ARG, "conv_pack_deconv2x2_dgrad: null pointer");
+  if (cin < 1 || cout < 1 || phase < 0 || phase > 3 || (dtype != MGDT_F32 && dtype != MGDT_BF16))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "conv_pack_deconv2x2_dgrad: cin %d cout %d phase %d dtype %d", cin, cout, phase, dtype);
+  int CP, nchunks, NTtot;
+  conv_geometry(cout, cin, 1, dtype, &CP, &nchunks, &NTtot);
+  long total = (long)nchunks * NTtot * 64 * piece_elems(dtype);
+  int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  const FoldArgs fa{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, cin, NTtot * 16, bias_out};
+  MGDT_DISPATCH_DTYPE(dtype, (pack_kernel<T><<<grid, 256, 0, (hipStream_t)s>>>(w, nullptr, cout, cin, 1, CP, nchunks, NTtot, (T*)packed, 14 + phase, fa)));
+  MGDT_CHECK_LAUNCH("conv_pack_deconv2x2_dgrad");
+  return MGDT_OK;
+}
+
 // ---- batched re-pack: after an optimizer step every live packed panel of a training model is refreshed in a handful of launches instead of one (two) per
 // convolution (131 launches of ~4.5 us per step for the MSPA-GD n model).  One descriptor = one mgdt_conv_pack / mgdt_conv_pack_dgrad call.
 struct PackJob { const float* w; FoldArgs fa; int Cin, Cout, KS, CP, nchunks, NTtot, dgrad; void* out; };
@@ -323,7 +357,9 @@ __global__ void pack_batch_kernel(const PackJobs jobs) {
     int cin = cp * PE + j, cout = nb * 16 + r;
     float v = 0.f;
     if (tap < KS * KS && cin < Cin && cout < Cout) {
-      if (dgrad == 1) v = w[(((long)cin * Cout + cout) * KS + (KS - 1 - tap / KS)) * KS + (KS - 1 - tap % KS)];
+      if (dgrad >= 14) v = w[((long)cout * Cin + cin) * 4 + (dgrad - 14)];
+      else if (dgrad >= 10) v = w[((long)cin * Cout + cout) * 4 + (dgrad - 10)];
+      else if (dgrad == 1) v = w[(((long)cin * Cout + cout) * KS + (KS - 1 - tap / KS)) * KS + (KS - 1 - tap % KS)];
       else if (dgrad >= 6) v = stem6_weight(w, dgrad - 5, cout, cin, tap);
       else if (dgrad >= 2) {
         const int py = (dgrad - 2) >> 1, px = (dgrad - 2) & 1;
@@ -354,12 +390,13 @@ extern "C" int mgdt_conv_pack_batch(const mgdt_pack_desc* d, int n, mgdt_stream 
       const mgdt_pack_desc& e = d[i];
       if (e.dtype != dtype) continue;
       if (!e.w || !e.packed || !e.bias_out) MGDT_FAIL(MGDT_BAD_ARG, "conv_pack_batch: descriptor %d has a null pointer", i);
-      if (e.mode < 0 || e.mode > 9 || (e.mode >= 2 && e.k != 3) || (e.mode >= 6 && e.cin != e.mode - 5))
+      const bool deconv = e.mode >= 10;                                                     // mode 10 + phase / 14 + phase: see mgdt_conv_pack_deconv2x2 / _dgrad
+      if (e.mode < 0 || e.mode > 17 || (deconv ? e.k != 1 : (e.mode >= 2 && e.k != 3)) || (!deconv && e.mode >= 6 && e.cin != e.mode - 5))
         MGDT_FAIL(MGDT_BAD_SHAPE, "conv_pack_batch: descriptor %d mode %d", i, e.mode);
       PackJob& J = jobs.j[m++];
-      const bool stem6 = e.mode >= 6, fwd = e.mode == 0 || stem6;                           // stem6 (mode 5 + cin): see mgdt_conv_pack_stem6
+      const bool stem6 = e.mode >= 6 && !deconv, fwd = e.mode == 0 || stem6 || (deconv && e.mode < 14);     // stem6 (mode 5 + cin): see mgdt_conv_pack_stem6
       const int gi = stem6 ? stem6_channels(e.cin, dtype) : fwd ? e.cin : e.cout, go = fwd ? e.cout : e.cin;      // the data-gradient conv maps cout -> cin channels
-      conv_geometry(gi, go, e.k, dtype, &J.CP, &J.nchunks, &J.NTtot, (e.mode >= 2 && !stem6) ? phase_ntaps(e.mode) : 0);
+      conv_geometry(gi, go, e.k, dtype, &J.CP, &J.nchunks, &J.NTtot, (e.mode >= 2 && !stem6 && !deconv) ? phase_ntaps(e.mode) : 0);
       J.w = e.w; J.Cin = gi; J.Cout = go; J.KS = e.k; J.dgrad = e.mode; J.out = e.packed;
       J.fa = fwd ? FoldArgs{e.conv_bias, e.bn_gamma, e.bn_beta, e.bn_mean, e.bn_var, e.bn_eps, go, J.NTtot * 16, e.bias_out}
                          : FoldArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, go, J.NTtot * 16, e.bias_out};

@@ -148,16 +148,40 @@ def _v5_cfg(nc):
 
 
 # YOLOv5 detection graph: the reference's models/v5/yolov5.yaml.  A table of its own: CONFIGS lists the graphs that have a models/v8/ file.
-# yolov5-p6, YOLOv3 and YOLOv6 are not built.
+# yolov5-p6 and YOLOv3 are not built.
 V5_CONFIGS = {'yolov5': lambda nc=80: _v5_cfg(nc)}
 
 
+# [depth, width, max_channels] of models/v6/yolov6.yaml (the v8 table)
+V6_SCALES = {'n': [0.33, 0.25, 1024], 's': [0.33, 0.50, 1024], 'm': [0.67, 0.75, 768], 'l': [1.00, 1.00, 512], 'x': [1.00, 1.25, 512]}
+
+
+def _v6_cfg(nc):
+    """models/v6/yolov6.yaml (YOLOv6-3.0, P3-P5), row for row: 3x3 Conv + BN + ReLU throughout (`activation: nn.ReLU()`), repeated plain Conv rows,
+    SPPF, nn.ConvTranspose2d(c, c, 2, 2, 0) up-sampling in the head, Detect."""
+    backbone = [[-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 6, 'Conv', [128, 3, 1]], [-1, 1, 'Conv', [256, 3, 2]],
+                [-1, 12, 'Conv', [256, 3, 1]], [-1, 1, 'Conv', [512, 3, 2]], [-1, 18, 'Conv', [512, 3, 1]], [-1, 1, 'Conv', [1024, 3, 2]],
+                [-1, 6, 'Conv', [1024, 3, 1]], [-1, 1, 'SPPF', [1024, 5]]]
+    head = [[-1, 1, 'Conv', [256, 1, 1]], [-1, 1, 'nn.ConvTranspose2d', [256, 2, 2, 0]], [[-1, 6], 1, 'Concat', [1]], [-1, 1, 'Conv', [256, 3, 1]],
+            [-1, 9, 'Conv', [256, 3, 1]],
+            [-1, 1, 'Conv', [128, 1, 1]], [-1, 1, 'nn.ConvTranspose2d', [128, 2, 2, 0]], [[-1, 4], 1, 'Concat', [1]], [-1, 1, 'Conv', [128, 3, 1]],
+            [-1, 9, 'Conv', [128, 3, 1]],
+            [-1, 1, 'Conv', [128, 3, 2]], [[-1, 15], 1, 'Concat', [1]], [-1, 1, 'Conv', [256, 3, 1]], [-1, 9, 'Conv', [256, 3, 1]],
+            [-1, 1, 'Conv', [256, 3, 2]], [[-1, 10], 1, 'Concat', [1]], [-1, 1, 'Conv', [512, 3, 1]], [-1, 9, 'Conv', [512, 3, 1]],
+            [[19, 23, 27], 1, 'Detect', ['nc']]]
+    return {'nc': nc, 'activation': 'nn.ReLU()', 'scales': deepcopy(V6_SCALES), 'backbone': backbone, 'head': head}
+
+
+# YOLOv6 detection graph: the reference's models/v6/yolov6.yaml.  `activation` holds only for the build (nn.tasks.parse_model restores Conv.default_act).
+V6_CONFIGS = {'yolov6': lambda nc=80: _v6_cfg(nc)}
+
+
 # every built-in graph by name (the tables above stay apart: CONFIGS lists the detection graphs that have a models/v8/ file)
-ALL_CONFIGS = {**CONFIGS, **SEG_CONFIGS, **POSE_CONFIGS, **CLS_CONFIGS, **RTDETR_CONFIGS, **V5_CONFIGS}
+ALL_CONFIGS = {**CONFIGS, **SEG_CONFIGS, **POSE_CONFIGS, **CLS_CONFIGS, **RTDETR_CONFIGS, **V5_CONFIGS, **V6_CONFIGS}
 
 
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS / V5_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS / V5_CONFIGS / V6_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
     build = ALL_CONFIGS[name]
     d = build() if nc is None else build(nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from ... import ops
 
-__all__ = ('Conv', 'DWConv', 'Concat', 'autopad')
+__all__ = ('Conv', 'DWConv', 'ConvTranspose2d', 'Repeat', 'Concat', 'autopad')
 
 
 def autopad(k, p=None, d=1):
@@ -284,6 +284,55 @@ class DWConv(Conv):
 
     def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
         super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), d=d, act=act)
+
+
+class ConvTranspose2d(HipModule, nn.ConvTranspose2d):
+    """`nn.ConvTranspose2d` rows of a YAML (models/v6/yolov6.yaml:39,45: [c2, 2, 2, 0]): the torch class as parameter container (state_dict keys
+    `weight` (c1, c2, 2, 2) and `bias`, what a reference checkpoint holds), compute on the device.  Only kernel 2, stride 2, padding 0, one group,
+    with a bias is built (ops.check_deconv2x2): anything else raises here, before any launch.
+    forward: ops.deconv2x2 over four panels packed from the live weight (ops.PackedDeconv2x2Live: the trainer's ops.repack_all() refreshes them).
+    backward: db (the bias-only mode of bn_act_bwd, which also leaves a dense copy of the incoming gradient), dW and dx (ops.deconv2x2_wgrad /
+    ops.deconv2x2_dgrad): three launches plus the layer's share of the batched final sum where both gradients take their one-launch kernel (32 channels);
+    where dx composes by measurement (64 and 128 channels) it is four convolution launches over panels packed from the live weight, six launches in all."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        ops.check_deconv2x2(self.kernel_size, self.stride, self.padding, self.groups, self.output_padding, self.dilation)
+        if self.bias is None:
+            raise RuntimeError('transposed convolution: only the form with a bias is built (nn.ConvTranspose2d(c1, c2, 2, 2, 0)), got bias=False')
+
+    def forward(self, x, out=None):
+        """`out`: an NHWC view (B, c2, 2H, 2W) to write into (e.g. this layer's channels of the following Concat's buffer); allocated when None"""
+        dt = self.out_dtype(x) if out is None else out.dtype
+        pk = self._cached(('deconv', dt), [self.weight, self.bias], lambda: ops.PackedDeconv2x2Live(self.weight, self.bias, dt))
+        if self.training:
+            self._save_ctx(x)
+        return ops.deconv2x2(x, pk, out=out)
+
+    def backward(self, g, need_dx=True, dx_out=None, acc=False, r2=None):
+        """g: grad w.r.t. the output.  Fills .grad of weight / bias (overwrite), returns dx (same `dx_out` / `acc` / `r2` forms as Conv.backward)."""
+        x = self._ctx.pop()
+        dy = ops.bn_act_bwd(g, g, None, None, None, self.bias, ops.ACT_NONE, None, ops.grad_buf(self.bias))     # db = sum of g; dy = g, dense
+        ops.deconv2x2_wgrad(x, dy, ops.grad_buf(self.weight))
+        if not need_dx:
+            return None
+        dx = dx_out if dx_out is not None else ops.new_act(x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.dtype, dy.device)
+        return ops.deconv2x2_dgrad(dy, self.weight, dx, accumulate=bool(acc and dx_out is not None), r2=r2)
+
+
+class Repeat(nn.Sequential):
+    """A YAML row with repeats n > 1 of a module that does not take n itself (models/v6/yolov6.yaml: `[-1, 6, Conv, [128, 3, 1]]`): the reference's bare
+    nn.Sequential (same state_dict keys `0.conv.weight`, ...; every isinstance(m, nn.Sequential) test holds) with the reverse pass the layer loop needs."""
+
+    def backward(self, g, need_dx=True):
+        """children in reverse order; `need_dx=False` (the row is layer 0) is handed to the first child"""
+        mods = list(self)
+        for k in range(len(mods) - 1, -1, -1):
+            m = mods[k]
+            if not hasattr(m, 'backward'):
+                raise NotImplementedError(f'{type(m).__name__}.backward is not built yet (training path of this module: next)')
+            g = m.backward(g, need_dx=False) if (k == 0 and not need_dx and isinstance(m, (Conv, ConvTranspose2d))) else m.backward(g)
+        return g if need_dx else None
 
 
 class Concat(nn.Module):

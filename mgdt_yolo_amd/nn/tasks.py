@@ -18,13 +18,14 @@ import torch.nn as nn
 
 from .. import ops
 from ..yolo.utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts, make_divisible
-from .modules import (C2f, C3, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, Detect, DWConv, InjectionMultiSum_Auto_pool,
-                      Pose, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
+from .modules import (C2f, C3, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, ConvTranspose2d, Detect, DWConv, InjectionMultiSum_Auto_pool,
+                      Pose, Repeat, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
 
 # names a YAML row may use -> class (the reference resolves them with globals()[m] / getattr(torch.nn, ...), tasks.py:630)
 REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, C3, MSPA_C2f, SPPF, SimFusion_4in, SimFusion_3in, IFM,
                                     InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose, Classify, RTDETRDecoder)}
 REGISTRY['nn.Upsample'] = Upsample
+REGISTRY['nn.ConvTranspose2d'] = ConvTranspose2d
 
 
 class _TrainForwardFn(torch.autograd.Function):
@@ -298,7 +299,7 @@ class BaseModel(nn.Module):
             if not hasattr(m, 'backward'):
                 raise NotImplementedError(f'{type(m).__name__}.backward is not built yet (training path of this module: next)')
             first = m.i == 0
-            gin = m.backward(g, need_dx=False) if (first and isinstance(m, Conv)) else m.backward(g)
+            gin = m.backward(g, need_dx=False) if (first and isinstance(m, (Conv, Repeat))) else m.backward(g)
             srcs = [m.f] if isinstance(m.f, int) else list(m.f)
             gins = [gin] if isinstance(m.f, int) else list(gin)
             for f, gi in zip(srcs, gins):
@@ -814,7 +815,17 @@ def tta_geometry(h, w, strides):
 # ---------------------------------------------------------------------------------------------------------------
 def parse_model(d, ch, verbose=True):
     """YAML dict -> nn.Sequential + save-list, with the reference's argument-rewriting rules (tasks.py:604-699).
-    Also returns each layer's cumulative spatial reduction (for the head strides)."""
+    Also returns each layer's cumulative spatial reduction (for the head strides).
+    An `activation:` key replaces Conv.default_act for THIS build only: the previous value is restored on the way out, where the reference leaves
+    it set for the rest of the process (tasks.py:620-621).  The modules built keep their own `act`, so the model is the reference's."""
+    prev_act = Conv.default_act
+    try:
+        return _parse_model(d, ch, verbose)
+    finally:
+        Conv.default_act = prev_act
+
+
+def _parse_model(d, ch, verbose):
     max_channels = float('inf')
     nc, act, scales = (d.get(x) for x in ('nc', 'activation', 'scales'))
     kpt_shape = d.get('kpt_shape')       # the Pose row names it as an argument (tasks.py:607, :642)
@@ -850,6 +861,12 @@ def parse_model(d, ch, verbose=True):
                 args.insert(2, n)
                 n = 1
             r_out = r_in * (args[3] if m in (Conv, DWConv) and len(args) > 3 else 1)
+        elif m is ConvTranspose2d:              # nn.ConvTranspose2d rows (tasks.py:637-647): [c2, k, s, p] -> (c1, c2, k, s, p), c2 scaled like a Conv's
+            c1, c2 = ch[f], args[0]
+            if c2 != nc:
+                c2 = make_divisible(min(c2, max_channels) * width, 8)
+            args = [c1, c2, *args[1:]]
+            r_out = r_in / (args[3] if len(args) > 3 else 1)
         elif m is Classify:                     # tasks.py:655-656 of the upstream parser: c1 = ch[f], c2 = nc
             c1 = ch[f] if isinstance(f, int) else sum(ch[x] for x in f)
             c2 = args[0]
@@ -891,7 +908,7 @@ def parse_model(d, ch, verbose=True):
         else:
             c2 = ch[f]
             r_out = r_in
-        m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
+        m_ = Repeat(*(m(*args) for _ in range(n))) if n > 1 else m(*args)      # Repeat: the reference's nn.Sequential (same keys) with a backward
         t = f'{m.__module__}.{m.__name__}'
         m.np = sum(x.numel() for x in m_.parameters())
         m_.i, m_.f, m_.type = i, f, t

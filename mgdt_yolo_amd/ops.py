@@ -1095,6 +1095,172 @@ def deconv2x2(x, pk, out=None):
     return out
 
 
+class _DeconvPanel:
+    """One phase panel of PackedDeconv2x2Live: the fields repack_all() refreshes."""
+    __slots__ = ('w', 'bias', 'src', 'epoch', '__weakref__')
+
+
+class PackedDeconv2x2Live:
+    """The four 1x1 panels of one nn.ConvTranspose2d(cin, cout, 2, 2, 0), packed straight from the live (cin, cout, 2, 2) weight
+    (mgdt_conv_pack_deconv2x2), so under the trainer repack_all() refreshes them in place like every other panel (PackedDeconv2x2 packs from
+    transposed copies, which are never registered).  Same fields as PackedDeconv2x2: ops.deconv2x2 takes either."""
+    __slots__ = ('panels', 'ptrs', 'bias', 'cin', 'cout', 'dtype', '__weakref__')
+
+    def __init__(self, weight, bias, dtype):
+        check_deconv2x2(weight.shape[2:], (2, 2), (0, 0), 1)
+        if bias is None:
+            raise RuntimeError('transposed convolution: only the form with a bias is built')
+        lib = L.lib()
+        w = weight.detach().float().contiguous()
+        cb = bias.detach().float().contiguous()
+        _need_gpu(w)
+        self.cin, self.cout, self.dtype = w.shape[0], w.shape[1], dtype
+        code = dtype_code(dtype)
+        nbytes = lib.mgdt_conv_packed_bytes(self.cin, self.cout, 1, code)
+        self.panels = []
+        for ph in range(4):
+            pn = _DeconvPanel()
+            pn.w = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+            pn.bias = torch.empty((self.cout + 15) // 16 * 16, dtype=torch.float32, device=w.device)
+            pn.src, pn.epoch = None, None
+            _launch('conv_pack', 'mgdt_conv_pack_deconv2x2', ptr(w), ptr(cb), self.cin, self.cout, ph, code, ptr(pn.w), ptr(pn.bias), stream())
+            _register_pack(pn, (w, cb, None, None, None, None, 0.0, self.cin, self.cout, 1, code, 10 + ph))
+            self.panels.append(pn)
+        self.ptrs = (C.c_void_p * 4)(*[pn.w.data_ptr() for pn in self.panels])
+        self.bias = self.panels[0].bias
+
+    @property
+    def epoch(self):
+        """the oldest panel's stamp (None: not refreshable in place) - what pack_is_current() compares"""
+        ep = [pn.epoch for pn in self.panels]
+        return None if any(e is None for e in ep) else min(ep)
+
+
+# The ConvTranspose2d layer's reverse pass: dx and dW in one launch each (mgdt_deconv2x2_dgrad / mgdt_deconv2x2_wgrad) or composed from four strided-view
+# 1x1 launches per gradient.  None: per (cin, cout) class, the one-launch route where tools/yolov6_bench.py measured it faster than the composed one by more
+# than the run-to-run spread of the two (DESIGN section 5); True: wherever the kernels cover the case (tests, the tool); False: composed everywhere.
+DECONV_BWD_FUSED = None
+DECONV_DX_FUSED_CLASSES = ((32, 32),)
+DECONV_DW_FUSED_CLASSES = ((32, 32), (64, 64), (128, 128))
+
+
+def _deconv_fused(classes, cin, cout):
+    return (int(cin), int(cout)) in classes if DECONV_BWD_FUSED is None else bool(DECONV_BWD_FUSED)
+
+
+def _deconv_bwd_views(small, dy):
+    if small.shape[0] != dy.shape[0] or dy.shape[2] != 2 * small.shape[2] or dy.shape[3] != 2 * small.shape[3]:
+        raise RuntimeError(f'transposed convolution (kernel 2, stride 2): dy {tuple(dy.shape)} does not match the input {tuple(small.shape)}')
+
+
+def _deconv_vec_ok(t):
+    return (is_nhwc(t) and t.shape[1] % 4 == 0 and t.stride(0) % 4 == 0 and t.stride(2) % 4 == 0 and t.stride(3) % 4 == 0
+            and t.data_ptr() % (4 * t.element_size()) == 0)
+
+
+def deconv2x2_dgrad(dy, weight, dx, accumulate=False, r2=None):
+    """dx (+)= d loss / d x of conv_transpose2d(x, weight (cin, cout, 2, 2), stride 2) [+ r2]: dx[b, y, x, ci] = sum_{ky, kx, co} W[ci, co, ky, kx] *
+    dy[b, 2y+ky, 2x+kx, co].  One launch (mgdt_deconv2x2_dgrad, K = 4 cout over the 2x2 gather of dy), or the four phases as strided-view 1x1
+    convolutions over panels packed from the live weight, the later three accumulating (DECONV_BWD_FUSED chooses; a case the one-launch kernel does
+    not take composes)."""
+    _deconv_bwd_views(dx, dy)
+    _same(dy, dx, r2)
+    cin, cout = weight.shape[0], weight.shape[1]
+    if dx.shape[1] != cin or dy.shape[1] != cout or tuple(weight.shape[2:]) != (2, 2) or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise RuntimeError(f'deconv2x2_dgrad: weight {tuple(weight.shape)} {weight.dtype} does not fit dy {tuple(dy.shape)} -> dx {tuple(dx.shape)}')
+    fits = ((cout + 15) // 16 * 16 + 4) * 256 <= 65536                  # w's LDS tile for 16 input channels (cout <= 240)
+    vec = _deconv_vec_ok(dy) and is_nhwc(dx) and cin % 4 == 0 and (r2 is None or is_nhwc(r2))
+    if _deconv_fused(DECONV_DX_FUSED_CLASSES, cin, cout) and fits and vec:      # a case the kernel does not take composes, like the block kernels' refusals
+        if _PROF is not None:
+            es = dy.element_size()
+            _META['deconv2x2_dgrad'] = dict(shape=(dx.shape[0], cin, dx.shape[2], dx.shape[3], cout, 2, 2), flops=2.0 * dy.numel() * cin,
+                                            bytes=float((dy.numel() + dx.numel() * (1 + bool(accumulate) + (r2 is not None))) * es + weight.numel() * 4))
+        _launch('deconv2x2_dgrad', 'mgdt_deconv2x2_dgrad', vp(dy), ptr(weight), vp(dx if accumulate else None), vp(r2), vp(dx), dtype_code(dy.dtype), stream())
+        return dx
+    pks = None
+    if is_nhwc(dx) and cin % 4 == 0 and conv_can_mfma(dy[:, :, ::2, ::2], cout, cin, 1, 1, 1, dy.dtype) and (r2 is None or is_nhwc(r2)):
+        pks = _deconv_dgrad_panels(weight, dy.dtype)
+    for ph in range(4):
+        ky, kx = ph >> 1, ph & 1
+        sub = dy[:, :, ky::2, kx::2]
+        if pks is not None:            # the MFMA 1x1 convolution over the phase view, its panel packed from the live weight (4 launches in all)
+            res = [t for t in (dx if (accumulate or ph) else None, r2 if ph == 0 else None) if t is not None]
+            conv2d(sub, pks[ph], 1, ACT_NONE, out=dx, r1=(res + [None, None])[0], r2=(res + [None, None])[1])
+        else:                          # shapes the MFMA kernel does not take (e.g. bf16 with cout % 8): the direct data-gradient kernel on a transposed copy
+            conv_dgrad(sub, weight.detach()[:, :, ky, kx].t().contiguous(), 1, 1, dx, accumulate=bool(accumulate or ph), r2=r2 if ph == 0 else None)
+    return dx
+
+
+class _PackedDeconvDgrad:
+    """Panel of one phase of the layer's composed data gradient (a 1x1 convolution cout -> cin), packed from the live (cin, cout, 2, 2) weight
+    (mgdt_conv_pack_deconv2x2_dgrad) and refreshed by repack_all(); same fields as PackedConv."""
+    __slots__ = ('w', 'bias', 'k', 'cin', 'cout', 'dtype', 'direct', 'groups', 'key', 'owner', 'src', 'epoch', '__weakref__')
+
+    def __init__(self, weight, phase, dtype, key):
+        import weakref
+        self.owner = weakref.ref(weight)
+        cin, cout = weight.shape[0], weight.shape[1]
+        code = dtype_code(dtype)
+        self.k, self.cin, self.cout, self.dtype, self.direct, self.groups, self.key = 1, cout, cin, dtype, False, 1, key       # a conv cout -> cin
+        self.w = torch.empty(L.lib().mgdt_conv_packed_bytes(cout, cin, 1, code), dtype=torch.uint8, device=weight.device)
+        self.bias = torch.empty((cin + 15) // 16 * 16, dtype=torch.float32, device=weight.device)
+        self.src, self.epoch = None, None
+        wf = weight.detach().float().contiguous()
+        _launch('conv_pack', 'mgdt_conv_pack_deconv2x2_dgrad', ptr(wf), cin, cout, phase, code, ptr(self.w), ptr(self.bias), stream())
+        if wf.data_ptr() == weight.data_ptr():
+            _register_pack(self, (wf, None, None, None, None, None, 0.0, cin, cout, 1, code, 14 + phase))
+
+
+_DECONV_DGRAD_PK = {}
+
+
+def _deconv_dgrad_panels(weight, dtype):
+    """the four phase panels of `weight`, rebuilt only when the weight changed and repack_all() did not refresh them (as conv_dgrad keeps its panels)"""
+    key = (PARAM_EPOCH[0], weight._version, dtype)
+    ck = (weight.data_ptr(), dtype)
+    pks = _DECONV_DGRAD_PK.get(ck)
+    if pks is not None and pks[0].owner() is weight and pks[0].key[1:] == key[1:] and all(pack_is_current(q) for q in pks):
+        for q in pks:
+            q.key = key
+    if pks is None or pks[0].owner() is not weight or pks[0].key != key:
+        pks = _DECONV_DGRAD_PK[ck] = [_PackedDeconvDgrad(weight, ph, dtype, key) for ph in range(4)]
+    return pks
+
+
+def deconv2x2_wgrad(x, dy, dw, accumulate=False):
+    """dw (cin, cout, 2, 2) fp32 contiguous (+)= sum_{b, y, x} x[b, y, x, ci] * dy[b, 2y+ky, 2x+kx, co] - the parameter's own layout.  One launch
+    (mgdt_deconv2x2_wgrad) whose per-split partial sums join the batched final sum inside `with defer_wgrad():`, bit-identical to the immediate
+    form; or - DECONV_BWD_FUSED off - four strided-view 1x1 weight-gradient launches into a scratch (4, cout, cin) and one permuting copy (their
+    final sums are taken at once: the other pending sums stay pending)."""
+    _deconv_bwd_views(x, dy)
+    _same(x, dy)
+    cin, cout = x.shape[1], dy.shape[1]
+    if tuple(dw.shape) != (cin, cout, 2, 2) or dw.dtype != torch.float32 or not dw.is_contiguous():
+        raise RuntimeError(f'deconv2x2_wgrad: dw must be a contiguous fp32 ({cin}, {cout}, 2, 2) tensor, got {tuple(dw.shape)} {dw.dtype}')
+    if _deconv_fused(DECONV_DW_FUSED_CLASSES, cin, cout) and _deconv_vec_ok(x) and _deconv_vec_ok(dy):      # views the kernel's vector loads do not take compose
+        lib = L.lib()
+        ws = torch.empty(lib.mgdt_deconv2x2_wgrad_workspace_bytes(cin, cout), dtype=torch.uint8, device=x.device)
+        if _PROF is not None:
+            _META['deconv2x2_wgrad'] = dict(shape=(x.shape[0], cin, x.shape[2], x.shape[3], cout, 2, 2), flops=2.0 * dy.numel() * cin,
+                                            bytes=float((x.numel() + dy.numel()) * x.element_size() + ws.numel()))
+        if _WGRAD_DEFER[0] > 0 and accumulate:
+            flush_wgrad()                                  # an accumulating gradient must see the value the pending jobs will write
+        defer = _WGRAD_DEFER[0] > 0 and not accumulate
+        _launch('deconv2x2_wgrad', 'mgdt_deconv2x2_wgrad', vp(x), vp(dy), None if defer else ptr(dw), int(accumulate), ptr(ws), dtype_code(dy.dtype), stream())
+        if defer:
+            _WGRAD_PENDING.append((ws, dw, dw.numel(), lib.mgdt_deconv2x2_wgrad_splits(cin, cout)))
+        return dw
+    if _WGRAD_DEFER[0] > 0 and accumulate:
+        flush_wgrad()
+    scratch = torch.empty((4, cout, cin, 1, 1), dtype=torch.float32, device=x.device)
+    for ph in range(4):
+        conv_wgrad(x, dy[:, :, ph >> 1::2, ph & 1::2], 1, 1, scratch[ph], defer=False)
+    perm = scratch.view(2, 2, cout, cin).permute(3, 2, 0, 1)          # (cin, cout, ky, kx) view of the four (cout, cin) matrices
+    if accumulate:
+        return add(dw, copy(perm, torch.empty_like(dw)), out=dw)
+    return copy(perm, dw)
+
+
 def seg_concat(y, mcs):
     """mgdt_seg_concat_fwd: y (B, 4+nc, A) fp32 + per-level cv4 maps (B, nm, h, w) NHWC -> (B, 4+nc+nm, A) fp32 (torch.cat([y, mc], 1) of
     head.py:212 with mc = cat of the levels' .view(bs, nm, -1))."""
@@ -1631,7 +1797,8 @@ def gconv_wgrad(x, dy, k, stride, groups, dw, accumulate=False):
     return dw
 
 
-def conv_wgrad(x, dy, k, stride, dw, dbias=None, x2=None, accumulate=False):
+def conv_wgrad(x, dy, k, stride, dw, dbias=None, x2=None, accumulate=False, defer=True):
+    """`defer=False`: the final sum is taken now even inside `with defer_wgrad():` (a caller that reads dw right away)"""
     lib = L.lib()
     if (not is_nhwc(x) or x.shape[1] % 4) and x.dtype in (torch.float32, torch.uint8, torch.bfloat16) and x2 is None and not accumulate and x.shape[1] < 4:
         # the 3-channel image (NCHW): one strided copy into a 4-channel NHWC buffer (4th channel zero) puts the stem on the tiled NHWC kernel;
@@ -1661,7 +1828,7 @@ def conv_wgrad(x, dy, k, stride, dw, dbias=None, x2=None, accumulate=False):
                                    bytes=float(x.numel() * x.element_size() + dy.numel() * dy.element_size()))
     if _WGRAD_DEFER[0] > 0 and accumulate:
         flush_wgrad()                                  # an accumulating gradient must see the value the pending jobs will write
-    defer = (_WGRAD_DEFER[0] > 0 and dbias is None and not accumulate and is_nhwc(x) and x.shape[1] % 4 == 0 and dy.shape[1] % 4 == 0 and dw.is_contiguous())
+    defer = (defer and _WGRAD_DEFER[0] > 0 and dbias is None and not accumulate and is_nhwc(x) and x.shape[1] % 4 == 0 and dy.shape[1] % 4 == 0 and dw.is_contiguous())
     _launch('conv_wgrad', 'mgdt_conv_wgrad', vp(x), vp(x2), vp(dy), k, stride, None if defer else ptr(dw), ptr(dbias), int(accumulate), ptr(ws), dtype_code(dy.dtype), stream())
     if defer:
         _WGRAD_PENDING.append((ws, dw, dw.numel(), lib.mgdt_conv_wgrad_splits(x.shape[1], dy.shape[1], k)))
