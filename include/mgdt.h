@@ -567,6 +567,20 @@ int mgdt_wgrad_final_batch(const mgdt_wgrad_final_desc* descs, int n, mgdt_strea
 int mgdt_add_fwd(const mgdt_view* a, const mgdt_view* b, const mgdt_view* o, int dtype, mgdt_stream s);
 int mgdt_maxpool5_bwd(const mgdt_view* x, const mgdt_view* gy, float* gx_f32, int dtype, mgdt_stream s);
 int mgdt_nearest_bwd(const mgdt_view* gy, const mgdt_view* gx, int dtype, mgdt_stream s);
+/* nn.MaxPool2d(2, stride) with stride 1 or 2, padding 0, dilation 1, ceil_mode False (models/v3/yolov3-tiny.yaml), pool.hip.  x, y, gy, gx: NHWC views with
+ * any sn / sh / sw (a channel slice of a wider buffer, the interior of a padded map); y / gy = n x ((h - 2) / stride + 1) x ((w - 2) / stride + 1) x c, gx =
+ * the shape of x.  16-byte accesses along c where c, the strides and the bases allow (c % 8 in bf16, c % 4 in fp32), one element per lane otherwise.
+ * A NaN in a window is its maximum.  bwd recomputes the argmax from x (the first maximum in (ky, kx) order, a NaN replaces what came before; -0.0 == 0.0)
+ * and GATHERS: every input pixel sums gy over the windows that hold it and whose argmax it is, in (oy, ox) order - no atomics, bit-reproducible; the
+ * odd trailing row / column that stride 2 never reads gets 0.  gx is written in `dtype`, every element.  MGDT_BAD_ARG: null / empty view, another kernel
+ * or stride; MGDT_BAD_SHAPE: views that are not NHWC or whose sizes do not match (an input smaller than 2 x 2 included); nothing is launched then.
+ * mgdt_spp_pool_bwd: gx_f32 (dense fp32 [n][h][w][c], every element written) = sum over k in (5, 9, 13) of the adjoint of MaxPool2d(k, 1, k / 2) at x
+ * applied to g_k - SPP's three DIRECT windows (nn/modules/block.py:121-135), whose first maximum is not the one a chain of 5 x 5 pools routes to.  One
+ * launch; fixed summation order (5, 9, 13; per size ox ascending, within it oy ascending).  The plane sits in LDS up to 1638 pixels (40 x 40), a
+ * global-memory route with the same bits serves larger maps.  x, g5, g9, g13: NHWC views of one shape, any sn / sh / sw. */
+int mgdt_maxpool2d_fwd(const mgdt_view* x, const mgdt_view* y, int k, int stride, int dtype, mgdt_stream s);
+int mgdt_maxpool2d_bwd(const mgdt_view* x, const mgdt_view* gy, const mgdt_view* gx, int k, int stride, int dtype, mgdt_stream s);
+int mgdt_spp_pool_bwd(const mgdt_view* x, const mgdt_view* g5, const mgdt_view* g9, const mgdt_view* g13, float* gx_f32, int dtype, mgdt_stream s);
 
 /* adjoints of the MSPA pooling attention and GD-neck ops (block.py:209-399, spr_module.py, convnextv2.py:48-77, utils.py:145-182) */
 int mgdt_ew_binary(const mgdt_view* a, const mgdt_view* b, const mgdt_view* o, int mode, int dtype, mgdt_stream s);

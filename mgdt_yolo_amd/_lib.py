@@ -143,6 +143,9 @@ PROTOTYPES = {
     'mgdt_add_fwd': (_i, [VP, VP, VP, _i, _vp]),
     'mgdt_maxpool5_bwd': (_i, [VP, VP, _vp, _i, _vp]),
     'mgdt_nearest_bwd': (_i, [VP, VP, _i, _vp]),
+    'mgdt_maxpool2d_fwd': (_i, [VP, VP, _i, _i, _i, _vp]),
+    'mgdt_maxpool2d_bwd': (_i, [VP, VP, VP, _i, _i, _i, _vp]),
+    'mgdt_spp_pool_bwd': (_i, [VP, VP, VP, VP, _vp, _i, _vp]),
     'mgdt_ew_binary': (_i, [VP, VP, VP, _i, _i, _vp]),
     'mgdt_channel_affine': (_i, [VP, _vp, _vp, VP, _i, _vp]),
     'mgdt_nc_reduce_workspace_bytes': (_sz, [_i, _i]),

@@ -148,7 +148,7 @@ def _v5_cfg(nc):
 
 
 # YOLOv5 detection graph: the reference's models/v5/yolov5.yaml.  A table of its own: CONFIGS lists the graphs that have a models/v8/ file.
-# yolov5-p6 and YOLOv3 are not built.
+# yolov5-p6 is not built.
 V5_CONFIGS = {'yolov5': lambda nc=80: _v5_cfg(nc)}
 
 
@@ -176,12 +176,56 @@ def _v6_cfg(nc):
 V6_CONFIGS = {'yolov6': lambda nc=80: _v6_cfg(nc)}
 
 
+def _v3_darknet53():
+    """rows 0-10 of models/v3/yolov3.yaml and yolov3-spp.yaml: the darknet53 backbone (a stride-1 stem, Bottleneck rows with repeats)"""
+    return [[-1, 1, 'Conv', [32, 3, 1]], [-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'Bottleneck', [64]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 2, 'Bottleneck', [128]],
+            [-1, 1, 'Conv', [256, 3, 2]], [-1, 8, 'Bottleneck', [256]], [-1, 1, 'Conv', [512, 3, 2]], [-1, 8, 'Bottleneck', [512]],
+            [-1, 1, 'Conv', [1024, 3, 2]], [-1, 4, 'Bottleneck', [1024]]]
+
+
+def _v3_head(row12):
+    """the head both full-width files share; they differ in row 12 only (a 1x1 Conv in yolov3, SPP in yolov3-spp).  Rows 16 and 23 read `from = -2`."""
+    up = [-1, 1, 'nn.Upsample', ['None', 2, 'nearest']]
+    return [[-1, 1, 'Bottleneck', [1024, False]], row12, [-1, 1, 'Conv', [1024, 3, 1]], [-1, 1, 'Conv', [512, 1, 1]], [-1, 1, 'Conv', [1024, 3, 1]],
+            [-2, 1, 'Conv', [256, 1, 1]], list(up), [[-1, 8], 1, 'Concat', [1]], [-1, 1, 'Bottleneck', [512, False]], [-1, 1, 'Bottleneck', [512, False]],
+            [-1, 1, 'Conv', [256, 1, 1]], [-1, 1, 'Conv', [512, 3, 1]],
+            [-2, 1, 'Conv', [128, 1, 1]], list(up), [[-1, 6], 1, 'Concat', [1]], [-1, 1, 'Bottleneck', [256, False]], [-1, 2, 'Bottleneck', [256, False]],
+            [[27, 22, 15], 1, 'Detect', ['nc']]]
+
+
+def _v3_cfg(nc, row12):
+    return {'nc': nc, 'depth_multiple': 1.0, 'width_multiple': 1.0, 'backbone': _v3_darknet53(), 'head': _v3_head(row12)}
+
+
+def _v3_tiny_cfg(nc):
+    """models/v3/yolov3-tiny.yaml, row for row: stride-1 3x3 Convs with nn.MaxPool2d(2, 2, 0) between them, nn.ZeroPad2d((0, 1, 0, 1)) + nn.MaxPool2d(2, 1, 0)
+    at P5, a two-level head (P4, P5)."""
+    backbone = []
+    for c in (16, 32, 64, 128, 256):
+        backbone += [[-1, 1, 'Conv', [c, 3, 1]], [-1, 1, 'nn.MaxPool2d', [2, 2, 0]]]
+    backbone += [[-1, 1, 'Conv', [512, 3, 1]], [-1, 1, 'nn.ZeroPad2d', [[0, 1, 0, 1]]], [-1, 1, 'nn.MaxPool2d', [2, 1, 0]]]
+    head = [[-1, 1, 'Conv', [1024, 3, 1]], [-1, 1, 'Conv', [256, 1, 1]], [-1, 1, 'Conv', [512, 3, 1]],
+            [-2, 1, 'Conv', [128, 1, 1]], [-1, 1, 'nn.Upsample', ['None', 2, 'nearest']], [[-1, 8], 1, 'Concat', [1]], [-1, 1, 'Conv', [256, 3, 1]],
+            [[19, 15], 1, 'Detect', ['nc']]]
+    return {'nc': nc, 'depth_multiple': 1.0, 'width_multiple': 1.0, 'backbone': backbone, 'head': head}
+
+
+# YOLOv3 detection graphs: the reference's models/v3/{yolov3,yolov3-spp,yolov3-tiny}.yaml.  They carry depth_multiple / width_multiple (1.0) and no
+# `scales` table, and their names hold no scale letter.
+V3_CONFIGS = {
+    'yolov3': lambda nc=80: _v3_cfg(nc, [-1, 1, 'Conv', [512, 1, 1]]),
+    'yolov3-spp': lambda nc=80: _v3_cfg(nc, [-1, 1, 'SPP', [512, [5, 9, 13]]]),
+    'yolov3-tiny': lambda nc=80: _v3_tiny_cfg(nc),
+}
+
+
 # every built-in graph by name (the tables above stay apart: CONFIGS lists the detection graphs that have a models/v8/ file)
-ALL_CONFIGS = {**CONFIGS, **SEG_CONFIGS, **POSE_CONFIGS, **CLS_CONFIGS, **RTDETR_CONFIGS, **V5_CONFIGS, **V6_CONFIGS}
+ALL_CONFIGS = {**CONFIGS, **SEG_CONFIGS, **POSE_CONFIGS, **CLS_CONFIGS, **RTDETR_CONFIGS, **V5_CONFIGS, **V6_CONFIGS, **V3_CONFIGS}
 
 
 def get_config(name, scale='n', nc=None):
-    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS / V5_CONFIGS / V6_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems)."""
+    """cfg dict for `name` in CONFIGS / SEG_CONFIGS / POSE_CONFIGS / CLS_CONFIGS / RTDETR_CONFIGS / V5_CONFIGS / V6_CONFIGS / V3_CONFIGS at compound-scale letter `scale` (like 'yolov8n.yaml' file stems; the
+    YOLOv3 graphs have no `scales` table, so the parser never reads it for them)."""
     build = ALL_CONFIGS[name]
     d = build() if nc is None else build(nc)      # nc=None: the YAML file's own class count
     d['scale'] = scale

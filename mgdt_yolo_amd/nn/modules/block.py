@@ -12,7 +12,7 @@ from .conv import Conv, HipModule, act_code
 from .convnextv2 import ConvNeXtV2_Block
 from .spr_module import SPRModule
 
-__all__ = ('DFL', 'SPPF', 'C2f', 'C3', 'MSPA_C2f', 'Bottleneck', 'SimFusion_4in', 'SimFusion_3in', 'IFM', 'h_sigmoid',
+__all__ = ('DFL', 'SPP', 'SPPF', 'C2f', 'C3', 'MSPA_C2f', 'Bottleneck', 'SimFusion_4in', 'SimFusion_3in', 'IFM', 'h_sigmoid',
            'InjectionMultiSum_Auto_pool', 'Upsample', 'Proto')
 
 
@@ -347,6 +347,28 @@ class SPPF(HipModule):
         g2 = ops.add(sl(gcat, 2), ops.maxpool5_bwd(sl(cat, 2), sl(gcat, 3)))
         g1 = ops.add(sl(gcat, 1), ops.maxpool5_bwd(sl(cat, 1), g2))
         g0 = ops.add(sl(gcat, 0), ops.maxpool5_bwd(sl(cat, 0), g1))
+        return self.cv1.backward(g0)
+
+
+class SPP(SPPF):
+    """Spatial Pyramid Pooling (reference block.py:121-135) with k = (5, 9, 13): cv1 (1x1), the identity and three stride-1 max pools, cv2 (1x1) over the
+    four.  A stride-1 max over 9x9 / 13x13 with -inf padding is two / three chained 5x5 pools (max is exact and associative), so the forward IS SPPF's
+    (ops.sppf_pools fills the three slots of the concat buffer).  The reverse pass is not: autograd sends each output's gradient to the first maximum of
+    its DIRECT window, and a chain of 5x5 adjoints picks another pixel on ties and plateaus - ops.spp_pool_bwd routes the three gradients in one launch;
+    the identity slot's gradient is added by the caller, as in SPPF.  `m` holds the three nn.MaxPool2d for module-tree parity only."""
+
+    def __init__(self, c1, c2, k=(5, 9, 13)):
+        if tuple(k) != (5, 9, 13):
+            raise RuntimeError(f'SPP: k=(5, 9, 13) is what the YAMLs use and what the pooling kernels implement, got {tuple(k)}')
+        super().__init__(c1, c2, 5)
+        self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])
+
+    def backward(self, g):
+        c_ = self.cv1.conv.out_channels
+        cat, self._cat = self._cat, None
+        gcat = self.cv2.backward(g)
+        sl = lambda t, i: t[:, i * c_:(i + 1) * c_]
+        g0 = ops.add(sl(gcat, 0), ops.spp_pool_bwd(sl(cat, 0), sl(gcat, 1), sl(gcat, 2), sl(gcat, 3)))
         return self.cv1.backward(g0)
 
 

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from ... import ops
 
-__all__ = ('Conv', 'DWConv', 'ConvTranspose2d', 'Repeat', 'Concat', 'autopad')
+__all__ = ('Conv', 'DWConv', 'ConvTranspose2d', 'MaxPool2d', 'ZeroPad2d', 'Repeat', 'Concat', 'autopad')
 
 
 def autopad(k, p=None, d=1):
@@ -318,6 +318,54 @@ class ConvTranspose2d(HipModule, nn.ConvTranspose2d):
             return None
         dx = dx_out if dx_out is not None else ops.new_act(x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.dtype, dy.device)
         return ops.deconv2x2_dgrad(dy, self.weight, dx, accumulate=bool(acc and dx_out is not None), r2=r2)
+
+
+class MaxPool2d(HipModule, nn.MaxPool2d):
+    """`nn.MaxPool2d` rows of a YAML (models/v3/yolov3-tiny.yaml: [2, 2, 0] and [2, 1, 0]): the torch class as a parameter-free container, compute on
+    the device.  Only kernel 2 with stride 2 or 1, padding 0, dilation 1, ceil_mode=False, return_indices=False is built (ops.check_maxpool2d): anything
+    else raises here, before any launch.  Output size floor((H - 2) / s) + 1: with stride 2 an odd trailing row or column is not read.
+    forward: ops.maxpool2d (ATen's values: a NaN in a window is its maximum).  backward: ops.maxpool2d_bwd recomputes the argmax from the input, the
+    only context the layer keeps (no index tensor), and gathers - the first maximum in scan order takes the gradient, pixels no window read get zero."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._k, self._s = ops.check_maxpool2d(self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode, self.return_indices)
+
+    def forward(self, x, out=None):
+        if self.training:
+            self._save_ctx(x)
+        return ops.maxpool2d(x, self._k, self._s, out=out)
+
+    def backward(self, g, dx_out=None):
+        """g: grad w.r.t. the output -> grad w.r.t. the input, in the activation dtype (written to `dx_out` when given)"""
+        x = self._ctx.pop()
+        return ops.maxpool2d_bwd(x, g, self._k, self._s, gx=dx_out)
+
+
+class ZeroPad2d(HipModule, nn.ZeroPad2d):
+    """`nn.ZeroPad2d` rows of a YAML (models/v3/yolov3-tiny.yaml: [[0, 1, 0, 1]]): non-negative (left, right, top, bottom).  forward: a zero-filled NHWC
+    map of the padded size and one ops.copy into its interior view; backward: the interior view of the incoming gradient (no launch, no copy).  The
+    consumer sees the pad as ordinary zeros: a max pool behind it whose first maximum is a pad zero sends that gradient here, and the view drops it."""
+
+    def __init__(self, padding):
+        super().__init__(padding)
+        if len(self.padding) != 4 or any((not isinstance(p, int)) or p < 0 for p in self.padding):
+            raise RuntimeError(f'ZeroPad2d: four non-negative integers (left, right, top, bottom) are built, got {self.padding}')
+
+    def _interior(self, t, h, w):
+        left, _, top, _ = self.padding
+        return t[:, :, top:top + h, left:left + w]
+
+    def forward(self, x):
+        b, c, h, w = x.shape
+        left, right, top, bottom = self.padding
+        out = ops.new_act(b, c, h + top + bottom, w + left + right, x.dtype, x.device).zero_()
+        ops.copy(x, self._interior(out, h, w))
+        return out
+
+    def backward(self, g):
+        left, right, top, bottom = self.padding
+        return self._interior(g, g.shape[2] - top - bottom, g.shape[3] - left - right)
 
 
 class Repeat(nn.Sequential):

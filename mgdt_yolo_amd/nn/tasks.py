@@ -18,14 +18,16 @@ import torch.nn as nn
 
 from .. import ops
 from ..yolo.utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts, make_divisible
-from .modules import (C2f, C3, IFM, MSPA_C2f, SPPF, Bottleneck, Classify, Concat, Conv, ConvTranspose2d, Detect, DWConv, InjectionMultiSum_Auto_pool,
-                      Pose, Repeat, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample)
+from .modules import (C2f, C3, IFM, MSPA_C2f, SPP, SPPF, Bottleneck, Classify, Concat, Conv, ConvTranspose2d, Detect, DWConv, InjectionMultiSum_Auto_pool,
+                      MaxPool2d, Pose, Repeat, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample, ZeroPad2d)
 
 # names a YAML row may use -> class (the reference resolves them with globals()[m] / getattr(torch.nn, ...), tasks.py:630)
-REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, C3, MSPA_C2f, SPPF, SimFusion_4in, SimFusion_3in, IFM,
+REGISTRY = {c.__name__: c for c in (Conv, DWConv, Concat, Bottleneck, C2f, C3, MSPA_C2f, SPP, SPPF, SimFusion_4in, SimFusion_3in, IFM,
                                     InjectionMultiSum_Auto_pool, Detect, TOODHead, Segment, Pose, Classify, RTDETRDecoder)}
 REGISTRY['nn.Upsample'] = Upsample
 REGISTRY['nn.ConvTranspose2d'] = ConvTranspose2d
+REGISTRY['nn.MaxPool2d'] = MaxPool2d
+REGISTRY['nn.ZeroPad2d'] = ZeroPad2d
 
 
 class _TrainForwardFn(torch.autograd.Function):
@@ -852,7 +854,7 @@ def _parse_model(d, ch, verbose):
                     args[j] = nc if a == 'nc' else kpt_shape if (a == 'kpt_shape' and kpt_shape is not None) else ast.literal_eval(a)
         n = n_ = max(round(n * depth), 1) if n > 1 else n
         r_in = red[f] if isinstance(f, int) else None
-        if m in (Conv, DWConv, Bottleneck, SPPF, C2f, C3, MSPA_C2f):
+        if m in (Conv, DWConv, Bottleneck, SPP, SPPF, C2f, C3, MSPA_C2f):
             c1, c2 = ch[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
@@ -905,6 +907,9 @@ def _parse_model(d, ch, verbose):
         elif m is Upsample:
             c2 = ch[f]
             r_out = r_in / args[1]
+        elif m is MaxPool2d:                    # nn.MaxPool2d rows: [k, s, p]; the channels pass through, the stride (torch's default: the kernel) reduces
+            c2 = ch[f]
+            r_out = r_in * (args[1] if len(args) > 1 and args[1] is not None else args[0])
         else:
             c2 = ch[f]
             r_out = r_in

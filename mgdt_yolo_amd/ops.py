@@ -1877,6 +1877,64 @@ def maxpool5_bwd(x, gy):
     return gx if gy.dtype == torch.float32 else copy(gx, like(gy))
 
 
+def check_maxpool2d(kernel_size, stride, padding=0, dilation=1, ceil_mode=False, return_indices=False):
+    """Only the pools of models/v3/yolov3-tiny.yaml are built (kernel 2, stride 2 or 1, padding 0, dilation 1, floor mode, no indices): anything else
+    raises before a launch.  Returns (kernel, stride)."""
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    k, s = pair(kernel_size), pair(kernel_size if stride is None else stride)
+    if k != (2, 2) or s not in ((1, 1), (2, 2)) or pair(padding) != (0, 0) or pair(dilation) != (1, 1) or ceil_mode or return_indices:
+        raise RuntimeError(f'max pooling: only kernel 2, stride 2 or 1, padding 0, dilation 1, ceil_mode=False, return_indices=False is built '
+                           f'(nn.MaxPool2d rows of yolov3-tiny), got kernel {k} stride {s} padding {pair(padding)} dilation {pair(dilation)} '
+                           f'ceil_mode={bool(ceil_mode)} return_indices={bool(return_indices)}')
+    return 2, s[0]
+
+
+def _maxpool2d_size(x, stride):
+    h, w = x.shape[2], x.shape[3]
+    if h < 2 or w < 2:
+        raise RuntimeError(f'max pooling 2x2: the {h}x{w} input is smaller than the window (the output would be empty)')
+    return (h - 2) // stride + 1, (w - 2) // stride + 1
+
+
+def maxpool2d(x, k, stride, out=None):
+    """mgdt_maxpool2d_fwd: nn.MaxPool2d(2, stride) of an NHWC map (any sn / sh / sw); `out`: a view to write into."""
+    _need_gpu(x)
+    k, stride = check_maxpool2d(k, stride)
+    oh, ow = _maxpool2d_size(x, stride)
+    if out is None:
+        out = new_act(x.shape[0], x.shape[1], oh, ow, x.dtype, x.device)
+    _same(x, out)
+    if _PROF is not None:
+        _META['maxpool2d_fwd'] = dict(shape=(*x.shape, k, stride), flops=0.0, bytes=float((x.numel() + out.numel()) * x.element_size()))
+    _launch('maxpool2d_fwd', 'mgdt_maxpool2d_fwd', vp(x), vp(out), k, stride, dtype_code(x.dtype), stream())
+    return out
+
+
+def maxpool2d_bwd(x, gy, k, stride, gx=None):
+    """mgdt_maxpool2d_bwd: the adjoint of maxpool2d at x applied to gy, in the dtype of x, written to `gx` (a dense NHWC map when None)."""
+    _need_gpu(x)
+    k, stride = check_maxpool2d(k, stride)
+    _maxpool2d_size(x, stride)
+    gx = like(x) if gx is None else gx
+    _same(x, gy, gx)
+    if _PROF is not None:
+        _META['maxpool2d_bwd'] = dict(shape=(*x.shape, k, stride), flops=0.0, bytes=float((2 * x.numel() + gy.numel()) * x.element_size()))
+    _launch('maxpool2d_bwd', 'mgdt_maxpool2d_bwd', vp(x), vp(gy), vp(gx), k, stride, dtype_code(x.dtype), stream())
+    return gx
+
+
+def spp_pool_bwd(x, g5, g9, g13):
+    """mgdt_spp_pool_bwd: sum of the adjoints of MaxPool2d(5 / 9 / 13, 1, k // 2) at x applied to g5 / g9 / g13 (SPP's direct windows), one launch.
+    Dense NHWC gradient in the dtype of the g's (computed in fp32), the convention of maxpool5_bwd."""
+    _same(x, g5, g9, g13)
+    b, c, h, w = x.shape
+    gx = torch.empty((b, c, h, w), dtype=torch.float32, device=x.device).contiguous(memory_format=torch.channels_last)
+    if _PROF is not None:
+        _META['spp_pool_bwd'] = dict(shape=tuple(x.shape), flops=0.0, bytes=float(x.numel() * (4 * x.element_size() + 4)))
+    _launch('spp_pool_bwd', 'mgdt_spp_pool_bwd', vp(x), vp(g5), vp(g9), vp(g13), ptr(gx), dtype_code(x.dtype), stream())
+    return gx if g5.dtype == torch.float32 else copy(gx, like(g5))
+
+
 def nearest_bwd(gy, gx):
     _same(gy, gx)
     _launch('nearest_bwd', 'mgdt_nearest_bwd', vp(gy), vp(gx), dtype_code(gy.dtype), stream())
