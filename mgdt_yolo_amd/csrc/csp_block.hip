@@ -14,15 +14,23 @@
 // Layout on the CU: two NHWC maps P (bottleneck input / output) and T (its hidden map) over the (TH+2h) x (TW+2h) region, pixel stride
 // wd*2 bytes, and the concat buffer of the tile's own pixels without the last bottleneck's output (the back conv reads that one from P).
 // No padding: the 16-byte slots of a pixel row are XOR-swizzled by the pixel index (csp_psw, cat_at) so that every ds_read_b128 lane
-// group of the 3x3 convs and of the back conv hits 16 different slots of the 256-byte bank row.  Every 3x3 conv walks its output
-// rectangle as one linear pixel range (the wrap-around columns are computed and never consumed); the swizzle depends on the pixel
-// index mod 16 only, so a tap stays a per-lane constant byte offset: B operand = one ds_read_b128 at (pixel * stride + boff[tap]).
+// group of the 3x3 convs and of the back conv hits 16 different slots of the 256-byte bank row.
+// Pixel walk of the 3x3 convs: conv j (0 .. 2n - 1) needs the rectangle of rows / columns j + 1 .. RH - j - 2 / RW - j - 2 of the region.
+// Its pixels are numbered row-major and taken in groups of 16 (compact walk: one FastDiv per conv turns the number into the region
+// pixel); lanes past the end of the last group are clamped to the last pixel and store nothing.  Nothing outside the rectangle is
+// written: conv j + 1 reads the rectangle one ring wider than its own, which is conv j's; the shortcut reads `out` at the pixel it
+// writes; the concat copy and the back conv read tile pixels only, the last conv's rectangle.  For wd <= 16 (no swizzle) a tap is a
+// per-lane constant byte offset: B operand = one ds_read_b128 at (pixel * stride + boff[tap]); for wd 32 / 64 the slot XOR is formed
+// from the tap pixel's byte offset once per group and tap (bsw).  MGDT_CSP_COMPACT=0 selects the earlier linear walk (the range
+// [lo, hi) of region pixels from the rectangle's first to its last pixel, wrap-around columns computed and never consumed; there the
+// swizzle depends on the pixel index mod 16 only and is baked into boff): same MFMAs and rounding per needed pixel, same bits.
 // Pixel coordinates (image offset, tile index) are computed from the pixel index where they are needed, not stored in LDS tables.
 // GEMM orientation as conv_igemm: weights = A operand (rows = 16 output channels), pixels = B operand, so a lane ends with 4 consecutive
 // channels of one pixel = one 8-byte LDS / HBM store.  Each wave keeps the weight fragments of ONE cout block of the running conv in
 // registers (weights-stationary: 12..72 VGPRs) and streams pixel groups through them; the packed panels are the ordinary
 // mgdt_conv_pack layout, read straight from L2.  Pixels outside the image are written as zeros (the next conv's zero padding).
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "conv_igemm_kernel.h"
@@ -43,11 +51,15 @@ struct CspArgs {
   unsigned long long* dbg;             // MGDT_CSP_DBG: 8 wall-clock stamps (10 ns units) per workgroup
   int pool_gst;                        // back phase: waves per cout block = pool slots per tile (1 when there are >= 8 cout blocks)
   FastDiv fd_rw, fd_tw, fd_tx, fd_tpi; // pixel coordinates: division by region width / tile width / tiles per row / tiles per image without the ~40-instruction sequence
+  FastDiv fd_cw[4];                    // compact walk: division by the width RW - 2j - 2 of 3x3 conv j's output rectangle
 };
 
 constexpr int CSP_THREADS = 512;
 constexpr int CSP_NW = CSP_THREADS / 64;
 constexpr int CSP_NCHB_MAX = 8;        // back conv: K <= 256 concat channels (host-side bound)
+// workgroups per CU that the registers allow: the paired wd 8 form fits 80 VGPRs without scratch = three (its tile takes 41 KB of LDS),
+// wd 16 / 32 and the unpaired wd 8 form <= 128 = two, wd 64 one
+constexpr int csp_waves_per_simd(int wd, bool pair) { return wd == 8 && pair ? 6 : (wd <= 32 ? 4 : 2); }
 
 // SiLU only, branch-free (the host refuses anything else): a run-time activation switch here turned every epilogue into four serial
 // branchy exp -> rcp chains; as straight-line code the four values' transcendentals interleave
@@ -90,8 +102,9 @@ __device__ __forceinline__ f32x4 csp_merge(f32x4 va, f32x4 vb) {
 // group b in lanes 32-63; a lane's channels are 4 * (g & 1) ..) before the SiLU / round / store epilogue, which then runs once for both.
 // The front also loads a pair with all 64 lanes live and splits the rounded operand back into two B operands whose upper halves are real
 // zeros (0 * Inf of the neighbouring group must not reach this one).  Same arithmetic in the same order: the outputs are bit-identical.
-template <int WD, int MODE, bool PAIR = false>
-__global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_kernel(const CspArgs a) {   // 4: two workgroups per CU (<= 128 VGPRs)
+// COMPACT: the 3x3 convs form their 16-pixel groups over the pixels of the output rectangle only (see the header); false = the linear walk.
+template <int WD, int MODE, bool PAIR = false, bool COMPACT = true>
+__global__ __launch_bounds__(CSP_THREADS, csp_waves_per_simd(WD, PAIR)) void csp_block_kernel(const CspArgs a) {
   static_assert(!PAIR || (WD == 8 && MODE == 0), "the paired epilogue is the wd = 8 MSPA form");
   constexpr int CP = WD / 8;                         // 16-byte pieces per tap
   constexpr int NCHB = WD == 8 ? 2 : (WD == 16 ? 3 : (WD == 32 ? 5 : 8));   // K chunks of the back conv at n = 2 (concat <= 256 channels)
@@ -332,7 +345,16 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
   stamp(3);
 
   // ================================================================ middle: 2 * nbtl 3x3 convs, P -> T -> P ...
-  constexpr bool PREB = WD <= 16;                                // prefetch the back conv's first fragments too (register budget)
+  constexpr bool PREB = WD <= 16;                                // narrow: all of the back conv's first fragments are requested during the last 3x3 conv
+  // narrow convs request all of the next conv's fragments (the last conv: of the back conv's first cout block) while the running conv
+  // computes.  Wide convs request them when the wave has finished its own groups, in front of the barrier that ends the conv instead
+  // of behind it (A is dead there: no register cost, and the wave waits at the barrier anyway).  Requesting a part of them earlier
+  // (6 of 9 chunks at wd 32, 9 or 18 of 18 at wd 64) fits the registers but measured slower: see DESIGN.md section 8 item 1.
+  constexpr int NPRE = WD <= 16 ? NCH : 0;                       // chunks requested at the start of the running conv
+  constexpr int NPREB = PREB ? NCHB : 0;
+  constexpr bool RESW = COMPACT && WD >= 32;                     // compact walk of a swizzled map: the XOR term is re-formed per group
+  constexpr int CPL = CP >= 4 ? CP / 4 : 1;                      // wide: K chunks per tap (a chunk lies inside one tap, the lane's piece is 4 h + g)
+  constexpr int SWM = WD == 64 ? 0x70 : 0x30;                    // csp_psw(pix) << 4 = (pix * PS >> 3) & SWM
   bf16x8 AB[NCHB];
   f32x4 biasB = f32x4{0.f, 0.f, 0.f, 0.f};
   const int bgst = a.pool_gst, bgv = wave / (CSP_NW / bgst), obst = CSP_NW / bgst, ob0 = wave % obst;
@@ -340,34 +362,46 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
     const int gv = gvm, gst = gstm;
     const int cch = nbv * 16 + 4 * g;                            // this lane's first output channel
     const int slot0 = (MODE == 0 ? 3 : 2) * WD;                  // concat offset of the first bottleneck output
-    for (int j = 0; j < 2 * a.nbtl; ++j) {
+    // one 3x3 conv.  The last one is a copy of its own (LAST is a type, not a flag): what it requests for the back conv is then defined
+    // after the loop over the others, not carried through it in registers that the wide convs do not have
+    auto conv3 = [&](const int j, auto LAST) __attribute__((always_inline)) {
       const char* in = (j & 1) ? Tb : Pb;
       char* out = (j & 1) ? Pb : Tb;
-      // narrow convs: the next conv's fragments are requested now and land while this conv computes (wide ones: registers are better
-      // spent on two workgroups per CU, their fragments are loaded after the barrier)
-      constexpr bool PREN = WD <= 16;
-      bf16x8 An[PREN ? NCH : 1];
+      // narrow convs: the next conv's fragments are requested now and land while this conv computes
+      bf16x8 An[NPRE > 0 ? NPRE : 1];
       f32x4 biasn = bias;
-      const bool more = j + 1 < 2 * a.nbtl;                     // uniform
-      if (more) {
-        if (PREN) {
+      constexpr bool more = !decltype(LAST)::value;
+      if constexpr (more) {
 #pragma unroll
-          for (int kc = 0; kc < NCH; ++kc) An[kc] = *(const bf16x8*)(a.mid[j + 1] + ((size_t)(kc * NB + nbv) * 64 + lane) * 16);
-          biasn = *(const f32x4*)(a.mid_bias[j + 1] + nbv * 16 + 4 * g);
-        }
-      } else if (PREB && ob0 < a.nbo) {
+        for (int kc = 0; kc < NPRE; ++kc) An[kc] = *(const bf16x8*)(a.mid[j + 1] + ((size_t)(kc * NB + nbv) * 64 + lane) * 16);
+        biasn = *(const f32x4*)(a.mid_bias[j + 1] + nbv * 16 + 4 * g);
+      } else if (ob0 < a.nbo) {
 #pragma unroll
-        for (int kc = 0; kc < NCHB; ++kc)
+        for (int kc = 0; kc < NPREB; ++kc)
           if (kc < a.nchb) AB[kc] = *(const bf16x8*)(a.back + ((size_t)(kc * a.nbo + ob0) * 64 + lane) * 16);
         biasB = *(const f32x4*)(a.back_bias + ob0 * 16 + 4 * g);
       }
       const int lo = (j + 1) * a.RW + (j + 1), hi = (a.RH - j - 2) * a.RW + (a.RW - j - 1);
-      const int ng = (hi - lo + 15) >> 4;
+      const int wj = a.RW - 2 * j - 2, npx = (a.RH - 2 * j - 2) * wj;   // the output rectangle: rows / columns j + 1 .. of the region
+      const int ng = COMPACT ? (npx + 15) >> 4 : (hi - lo + 15) >> 4;
+      const FastDiv fdw = a.fd_cw[j];
+      // pixel group -> this lane's region pixel.  Compact: the group's pixels are idx = 16 grp + r of the rectangle, row-major; lanes past
+      // the end of the last group take the last pixel (their LDS reads stay inside the rectangle) and store nothing.  Linear: lo + idx,
+      // liveness is finish's q < hi.
+      auto gpx = [&](int grp, bool& lv) __attribute__((always_inline)) {
+        const int idx = grp * 16 + r;
+        lv = true;
+        if constexpr (!COMPACT) return lo + idx;
+        lv = idx < npx;
+        const int ic = min(idx, npx - 1);
+        const int row = (int)fdiv((uint32_t)ic, fdw);
+        return lo + row * a.RW + (ic - row * wj);
+      };
       const bool second = j & 1;
       const bool tocat = second && (j >> 1) + 1 < a.nbtl;       // the last bottleneck's output is read from P by the back conv
       // zero outside the image: only where a later conv reads it as padding, and only on tiles whose region crosses the image border
-      // (the last conv's outside pixels are wrap-around columns nobody reads)
-      const bool zchk = !inner && j + 1 < 2 * a.nbtl;
+      // (the last conv's rectangle is the tile itself, inside the image; the linear walk's outside pixels there are wrap-around columns)
+      const bool zchk = !inner && more;
       int boff[NCH];                                             // this lane's byte offset of chunk kc's piece relative to its pixel's row
 #pragma unroll
       for (int kc = 0; kc < NCH; ++kc) {
@@ -375,8 +409,16 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
         int tap = p / CP, cp = p - tap * CP;
         if (tap >= 9) { tap = 4; cp = 0; }                       // padded piece: weights are zero, read something finite
         const int toff = (tap / 3 - 1) * a.RW + (tap % 3 - 1);
-        boff[kc] = toff * PS + ((cp ^ csp_psw<WD>(lo + r + toff)) << 4);   // pixel = lo + 16 k + r: its swizzle is known here
+        // linear walk: pixel = lo + 16 k + r, its swizzle is known here.  Compact walk: q mod 16 differs from group to group, so a swizzled
+        // map (wd 32 / 64) gets the XOR term per group (bsw below); wd <= 16 has none and boff stays the whole offset
+        boff[kc] = toff * PS + ((RESW ? cp : cp ^ csp_psw<WD>(lo + r + toff)) << 4);
       }
+      // RESW: byte offset of chunk tap * CPL + h of pixel q.  X = (q + toff) * PS + 16 g has the tap pixel's index above bit 6 (wd 64) /
+      // bit 5 (wd 32), so its swizzle is a shift and a mask of X: 3 VALU per tap and one per further chunk, once per group
+      auto bsw = [&](int q, int tap) __attribute__((always_inline)) {
+        const int X = q * PS + boff[tap * CPL];
+        return X ^ ((X >> 3) & SWM);
+      };
       // cc = the lane's first output channel, live = false: a lane that holds no pixel of its own (paired form without a second group)
       auto finish = [&](int q, f32x4 acc, int cc, bool live) __attribute__((always_inline)) {
 #pragma unroll
@@ -392,38 +434,55 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
         }
       };
       for (int grp = gv; grp < ng; grp += 2 * gst) {             // two pixel groups per step: two independent accumulator chains
-        const int qa = lo + grp * 16 + r;
         const bool hasb = grp + gst < ng;                        // wave-uniform
-        const int qb = hasb ? qa + gst * 16 : qa;
-        const char* pa = in + qa * PS;
-        const char* pb = in + qb * PS;
+        bool lva, lvb;
+        const int qa = gpx(grp, lva);
+        const int qb = gpx(hasb ? grp + gst : grp, lvb);
         f32x4 acca = bias, accb = bias;
+        if constexpr (RESW) {
 #pragma unroll
-        for (int kc = 0; kc < NCH; ++kc) {
-          acca = mma(A[kc], *(const bf16x8*)(pa + boff[kc]), acca);
-          accb = mma(A[kc], *(const bf16x8*)(pb + boff[kc]), accb);
+          for (int tap = 0; tap < 9; ++tap) {
+            const int oa = bsw(qa, tap), ob = bsw(qb, tap);
+#pragma unroll
+            for (int h = 0; h < CPL; ++h) {
+              acca = mma(A[tap * CPL + h], *(const bf16x8*)(in + (oa ^ (h << 6))), acca);
+              accb = mma(A[tap * CPL + h], *(const bf16x8*)(in + (ob ^ (h << 6))), accb);
+            }
+          }
+        } else {
+          const char* pa = in + qa * PS;
+          const char* pb = in + qb * PS;
+#pragma unroll
+          for (int kc = 0; kc < NCH; ++kc) {
+            acca = mma(A[kc], *(const bf16x8*)(pa + boff[kc]), acca);
+            accb = mma(A[kc], *(const bf16x8*)(pb + boff[kc]), accb);
+          }
         }
         if constexpr (PAIR) {
-          finish(lane < 32 ? qa : qb, csp_merge(acca, accb), 4 * (g & 1), lane < 32 || hasb);   // one epilogue for both groups, every lane live
+          finish(lane < 32 ? qa : qb, csp_merge(acca, accb), 4 * (g & 1), lane < 32 ? lva : hasb && lvb);   // one epilogue for both groups, every lane live
         } else {
-          finish(qa, acca, cch, true);
-          if (hasb) finish(qb, accb, cch, true);
+          finish(qa, acca, cch, lva);
+          if (hasb) finish(qb, accb, cch, lvb);
         }
+      }
+      // this wave's groups are done and A is dead: what was not requested ahead is requested here and lands while the wave waits for the
+      // others at the barrier
+      if constexpr (more) {
+#pragma unroll
+        for (int kc = 0; kc < NPRE; ++kc) A[kc] = An[kc];
+#pragma unroll
+        for (int kc = NPRE; kc < NCH; ++kc) A[kc] = *(const bf16x8*)(a.mid[j + 1] + ((size_t)(kc * NB + nbv) * 64 + lane) * 16);
+        bias = biasn;
+      } else if (ob0 < a.nbo) {
+#pragma unroll
+        for (int kc = NPREB; kc < NCHB; ++kc)
+          if (kc < a.nchb) AB[kc] = *(const bf16x8*)(a.back + ((size_t)(kc * a.nbo + ob0) * 64 + lane) * 16);
       }
       __syncthreads();
       if (j == 0) stamp(4);
-      if (more) {
-        if (PREN) {
-#pragma unroll
-          for (int kc = 0; kc < NCH; ++kc) A[kc] = An[kc];
-          bias = biasn;
-        } else {
-#pragma unroll
-          for (int kc = 0; kc < NCH; ++kc) A[kc] = *(const bf16x8*)(a.mid[j + 1] + ((size_t)(kc * NB + nbv) * 64 + lane) * 16);
-          bias = *(const f32x4*)(a.mid_bias[j + 1] + nbv * 16 + 4 * g);
-        }
-      }
-    }
+    };
+    for (int j = 0; j + 1 < 2 * a.nbtl; ++j) conv3(j, std::false_type{});
+    conv3(2 * a.nbtl - 1, std::true_type{});
   }
   stamp(5);
 
@@ -444,13 +503,7 @@ __global__ __launch_bounds__(CSP_THREADS, (WD <= 32 ? 4 : 2)) void csp_block_ker
     // few cout blocks (< 8): the waves that share a block split the tile's pixel groups; their partial sums go to separate pool slots
     const int gst = bgst, gv = bgv;
     bf16x8 ABn[PREB ? 1 : NCHB];                                 // wide blocks: the next cout block's fragments land during this one's MFMAs
-    f32x4 biasBn = biasB;
-    if (!PREB && ob0 < a.nbo) {
-#pragma unroll
-      for (int kc = 0; kc < NCHB; ++kc)
-        if (kc < a.nchb) AB[kc] = *(const bf16x8*)(a.back + ((size_t)(kc * a.nbo + ob0) * 64 + lane) * 16);
-      biasB = *(const f32x4*)(a.back_bias + ob0 * 16 + 4 * g);
-    }
+    f32x4 biasBn = biasB;                                        // AB / biasB of cout block ob0: requested in the last 3x3 conv
     for (int ob = ob0; ob < a.nbo; ob += obst) {
       if (PREB && ob != ob0) {
 #pragma unroll
@@ -648,6 +701,7 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
   a.total_tiles = a.N * g.tiles_x * g.tiles_y;
   a.fd_rw = make_fastdiv((uint32_t)g.RW); a.fd_tw = make_fastdiv((uint32_t)g.TW); a.fd_tx = make_fastdiv((uint32_t)g.tiles_x);
   a.fd_tpi = make_fastdiv((uint32_t)(g.tiles_x * g.tiles_y));
+  for (int j = 0; j < 2 * nbtl; ++j) a.fd_cw[j] = make_fastdiv((uint32_t)(g.RW - 2 * j - 2));
   a.per_xcd = cdiv(a.total_tiles, 8);
   const int grid = 8 * a.per_xcd;
   hipStream_t st = (hipStream_t)s;
@@ -662,6 +716,9 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
   // experiment knob, read per call (not part of the ABI): MGDT_CSP_PAIR=0 = the unpaired wd = 8 form
   const char* ep = getenv("MGDT_CSP_PAIR");
   const bool pair = !(ep && ep[0] == '0');
+  // likewise MGDT_CSP_COMPACT=0 = the linear pixel walk of the 3x3 convs (same MFMAs per needed pixel: bit-identical outputs)
+  const char* ec = getenv("MGDT_CSP_COMPACT");
+  const bool compact = !(ec && ec[0] == '0');
 #define CSP_LAUNCH(...)                                                                                              \
   do {                                                                                                                      \
     static std::atomic<bool> attr{false};                                                                                            \
@@ -672,11 +729,13 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
     }                                                                                                                       \
     csp_block_kernel<__VA_ARGS__><<<grid, CSP_THREADS, g.lds, st>>>(a);                                                      \
   } while (0)
+#define CSP_WALK(...) do { if (compact) CSP_LAUNCH(__VA_ARGS__, true); else CSP_LAUNCH(__VA_ARGS__, false); } while (0)
   if (mode == 0) {
-    switch (wd) { case 8: if (pair) CSP_LAUNCH(8, 0, true); else CSP_LAUNCH(8, 0); break; case 16: CSP_LAUNCH(16, 0); break; case 32: CSP_LAUNCH(32, 0); break; default: CSP_LAUNCH(64, 0); break; }
+    switch (wd) { case 8: if (pair) CSP_WALK(8, 0, true); else CSP_WALK(8, 0, false); break; case 16: CSP_WALK(16, 0, false); break; case 32: CSP_WALK(32, 0, false); break; default: CSP_WALK(64, 0, false); break; }
   } else {
-    switch (wd) { case 16: CSP_LAUNCH(16, 1); break; case 32: CSP_LAUNCH(32, 1); break; default: CSP_LAUNCH(64, 1); break; }
+    switch (wd) { case 16: CSP_WALK(16, 1, false); break; case 32: CSP_WALK(32, 1, false); break; default: CSP_WALK(64, 1, false); break; }
   }
+#undef CSP_WALK
 #undef CSP_LAUNCH
   MGDT_CHECK_LAUNCH("csp_block_fwd");
   if (a.dbg) {
