@@ -218,7 +218,7 @@ static bool bnf_linear(const mgdt_view* v, int dtype, int V, BnfView* out) {
 }
 // widest vector all views allow: 8 channels (16 bytes) for bf16, else 4
 static int bnf_pick(int dtype, std::initializer_list<const mgdt_view*> views, BnfView* outs) {
-  static const int vmax = getenv("MGDT_BN_V") ? atoi(getenv("MGDT_BN_V")) : 4;      // experiment knob
+  const int vmax = KNOB_ONCE(knob_int("MGDT_BN_V", 4));      // experiment knob
   for (int V : {dtype == MGDT_BF16 && vmax >= 8 ? 8 : 4, 4}) {
     bool ok = true;
     int k = 0;

@@ -121,16 +121,8 @@ extern "C" int mgdt_classify_pool_fwd(const mgdt_view* x, const void* w, const f
     if (cout % nb == 0 && nb * row <= 64 * 1024) { a.NB = nb; break; }
   const size_t lds = a.NB * row + 4 * 16 * sizeof(float);
   if (lds > 160 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "classify_pool: c1 = %d needs %zu bytes of LDS for 16 output channels (<= 160 KiB)", x->c, lds);
-  if (lds > 64 * 1024) {
-    static std::atomic<bool> attr_f{false}, attr_b{false};
-    std::atomic<bool>& at = dtype == MGDT_F32 ? attr_f : attr_b;
-    if (!at) {
-      hipError_t e = dtype == MGDT_F32 ? hipFuncSetAttribute((const void*)classify_pool_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                                       : hipFuncSetAttribute((const void*)classify_pool_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "classify_pool: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      at = true;
-    }
-  }
+  if (lds > 64 * 1024)
+    if (int rc = lds_optin<classify_pool_kernel<float>, classify_pool_kernel<bf16>>("classify_pool")) return rc;
   const dim3 grid(cout / a.NB, x->n);
   MGDT_DISPATCH_DTYPE(dtype, (classify_pool_kernel<T><<<grid, 256, lds, (hipStream_t)s>>>(a)));
   MGDT_CHECK_LAUNCH("classify_pool_fwd");

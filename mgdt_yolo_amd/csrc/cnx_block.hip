@@ -466,14 +466,12 @@ extern "C" size_t mgdt_cnx_block_workspace_bytes(int n, int h, int w, int c) {
   return 4096 + (size_t)n * cdiv(h, th) * cdiv(w, tw) * 4 * c * sizeof(float);
 }
 
+static StampBuf cnx_stamps;      // MGDT_CNX_DBG: 8 words per workgroup of one launch
+
+// stamp_wgs: 0, or the workgroups whose stamps the caller reads back
 template <int KC1, bool TAIL>
-static int cnx_launch(CnxArgs& a, const CnxLds& L, hipStream_t st) {
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)cnx_block_kernel<KC1, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "cnx_block: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr = true;
-  }
+static int cnx_launch(CnxArgs& a, const CnxLds& L, int stamp_wgs, hipStream_t st) {
+  if (int rc = lds_optin<cnx_block_kernel<KC1, TAIL>>("cnx_block")) return rc;
   // every workgroup of a launch must be resident at once (per-image barrier): one workgroup per CU (LDS), 256 CUs
   static int cus = 0;
   if (!cus) {
@@ -485,6 +483,10 @@ static int cnx_launch(CnxArgs& a, const CnxLds& L, hipStream_t st) {
   const int per_launch = cus / a.tiles;                    // images per launch
   if (per_launch < 1) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_block: %d tiles per image exceed the %d compute units", a.tiles, cus);
   const int N = a.N;
+  if (stamp_wgs) {
+    if (!cnx_stamps.ensure((size_t)std::max(stamp_wgs, std::min(per_launch, N) * a.tiles) * 8)) MGDT_FAIL(MGDT_WORKSPACE, "cnx_block: no memory for the MGDT_CNX_DBG stamps");
+    a.dbg = cnx_stamps.p;
+  }
   for (int n0 = 0; n0 < N; n0 += per_launch) {
     a.n0 = n0;
     cnx_block_kernel<KC1, TAIL><<<std::min(per_launch, N - n0) * a.tiles, CNX_THREADS, L.total, st>>>(a, L);
@@ -505,16 +507,10 @@ extern "C" int mgdt_cnx_block_fwd(const mgdt_view* x, const float* dw_w49c, cons
   if (ws_bytes < mgdt_cnx_block_workspace_bytes(x->n, x->h, x->w, x->c) || (uintptr_t)ws % 16) MGDT_FAIL(MGDT_WORKSPACE, "cnx_block: workspace too small / unaligned");
   CnxArgs a;
   memset(&a, 0, sizeof(a));
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes) {
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * 2;
-    if (v->sc != 1 || v->sw % 8 || v->sh % 8 || v->sn % 8 || (uintptr_t)v->p % 16 || ext >= 0x7fffffffL) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * 2); *sh = (int)(v->sh * 2); *sw = (int)(v->sw * 2); *bytes = (uint32_t)ext;
-  };
+  const ViewPolicy pol = {8, true, 0, 0, false};      // 16-byte pieces of NHWC bf16
   const char* yp = nullptr;
-  bind(x, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes);
-  bind(y, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes);
-  if (!fits) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_block: views must be 16-byte aligned NHWC (sc == 1) below 2 GiB");
+  if (!bind_view(x, 2, pol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(y, 2, pol, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_block: views must be 16-byte aligned NHWC (sc == 1) below 2 GiB");
   a.y = (char*)yp;
   a.dww = dw_w49c; a.dwb = dw_b; a.lnw = ln_w; a.lnb = ln_b; a.eps = eps; a.packed = (const char*)packed; a.gamma = gamma; a.beta = beta;
   a.sync = (unsigned*)ws; a.part = (float*)((char*)ws + 4096);
@@ -526,24 +522,20 @@ extern "C" int mgdt_cnx_block_fwd(const mgdt_view* x, const float* dw_w49c, cons
   a.fd_rw = make_fastdiv((uint32_t)a.RW); a.fd_tw = make_fastdiv((uint32_t)a.TW);
   a.gelu = gelu_coef();
   const CnxLds L = cnx_lds(a.C, a.TH, a.TW);
-  static unsigned long long* dbgbuf = nullptr;
-  const bool dbg = getenv("MGDT_CNX_DBG") != nullptr;
-  if (dbg && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, (size_t)1024 * 8 * 8);
-  a.dbg = dbg ? dbgbuf : nullptr;
+  const bool dbg = knob_set("MGDT_CNX_DBG");
+  const int nwg = std::min(1024, std::min(a.N, 256 / a.tiles) * a.tiles);     // stamps read back
+  const int sw = dbg ? std::max(nwg, 1) : 0;
   hipStream_t st = (hipStream_t)s;
   int rc;
   switch (kc1) {
-    case 1: rc = tail ? cnx_launch<1, true>(a, L, st) : cnx_launch<1, false>(a, L, st); break;
-    case 2: rc = tail ? cnx_launch<2, true>(a, L, st) : cnx_launch<2, false>(a, L, st); break;
-    default: rc = tail ? cnx_launch<3, true>(a, L, st) : cnx_launch<3, false>(a, L, st); break;
+    case 1: rc = tail ? cnx_launch<1, true>(a, L, sw, st) : cnx_launch<1, false>(a, L, sw, st); break;
+    case 2: rc = tail ? cnx_launch<2, true>(a, L, sw, st) : cnx_launch<2, false>(a, L, sw, st); break;
+    default: rc = tail ? cnx_launch<3, true>(a, L, sw, st) : cnx_launch<3, false>(a, L, sw, st); break;
   }
   if (rc != MGDT_OK) return rc;
   MGDT_CHECK_LAUNCH("cnx_block_fwd");
   if (dbg) {
-    (void)hipStreamSynchronize(st);
-    const int nwg = std::min(1024, std::min(a.N, 256 / a.tiles) * a.tiles);
-    std::vector<unsigned long long> h((size_t)nwg * 8);
-    (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
+    const std::vector<unsigned long long> h = cnx_stamps.read((size_t)nwg * 8, st);
     unsigned long long t0 = ~0ull, t6 = 0;
     double ph[6] = {0, 0, 0, 0, 0, 0};
     for (int i = 0; i < nwg; ++i) {

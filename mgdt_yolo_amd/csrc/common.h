@@ -5,8 +5,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <vector>
 
 #include "../../include/mgdt.h"
+#include "launch_host.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -29,6 +31,42 @@ void mgdt_set_error(const char* fmt, ...);
     if (e_ != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "%s: %s", name, hipGetErrorString(e_)); \
   } while (0)
 
+// Opt the kernels in to `bytes` of dynamic LDS, once per process and instantiation (idempotent; racing setters write the same value).
+template <auto... Kernels>
+static int lds_optin(const char* who, int bytes = 160 * 1024) {
+  static std::atomic<bool> done{false};
+  if (!done) {
+    for (const void* k : {(const void*)Kernels...}) {
+      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+      if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+    }
+    done = true;
+  }
+  return MGDT_OK;
+}
+
+// Device buffer of one entry point's MGDT_*_DBG phase stamps (debug only).  ensure() runs before every stamped launch with what that launch's grid
+// writes, so a kernel never receives a pointer to less; with the knob unset nothing is allocated and the kernel receives a null pointer.
+struct StampBuf {
+  unsigned long long* p = nullptr;
+  size_t cap = 0;                                          // 8-byte words
+  bool ensure(size_t words) {                              // false: no memory (the entry point fails with MGDT_WORKSPACE and launches nothing)
+    if (cap >= words) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    if (hipMalloc((void**)&p, words * 8) != hipSuccess) { p = nullptr; return false; }
+    cap = words;
+    return true;
+  }
+  void zero(size_t words, hipStream_t st) { (void)hipMemsetAsync(p, 0, words * 8, st); }
+  std::vector<unsigned long long> read(size_t words, hipStream_t st) {      // waits for the stream
+    std::vector<unsigned long long> h(words);
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpy(h.data(), p, words * 8, hipMemcpyDeviceToHost);
+    return h;
+  }
+};
+
 static inline bool view_ok(const mgdt_view* v) { return v && v->p && v->n > 0 && v->h > 0 && v->w > 0 && v->c > 0; }
 static inline bool view_nhwc(const mgdt_view* v) { return v->sc == 1; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
@@ -40,7 +78,7 @@ size_t mgdt_gn_partial_bytes(int n, int c);
 bool mgdt_gn_partial_sums(const mgdt_view* a, const mgdt_view* b, double* partial, int dtype, hipStream_t st);
 
 // What the host decided about one launch of the LDS-staged 3x3 kernel (mgdt_conv3x3_lds_plan in conv3x3_lds.hip; reported by mgdt_conv2d_route)
-struct C3Plan { int NBW, MT, waves, ncg, nwg, tiles_x, tiles_per_img, ntiles, XP; size_t lds; long extx, exty; };
+struct C3Plan { int NBW, MT, waves, ncg, nwg, tiles_x, tiles_per_img, ntiles, XP; size_t lds; };
 
 // ---- scalar load/store with conversion ----
 template <typename T> __device__ __forceinline__ float ldf(const T* p);

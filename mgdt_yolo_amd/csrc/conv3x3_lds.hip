@@ -227,9 +227,9 @@ __global__ __launch_bounds__(256 * WS, 1) void conv3x3_lds_kernel(const C3Args a
 // The predicate half: true when the LDS-staged kernel takes the layer, with the plan of its launch in *p; false: conv_igemm takes it.  Looks at shapes and
 // strides only (mgdt_conv2d_route calls it without pointers).
 bool mgdt_conv3x3_lds_plan(const mgdt_view* x, const mgdt_view* y, int act, int CP, int nchunks, int NTtot, bool q8, int stride, C3Plan* p) {
-  static const int mode = getenv("MGDT_CONV3_LDS") ? atoi(getenv("MGDT_CONV3_LDS")) : 1;      // experiment knob: 0 = never
+  const int mode = KNOB_ONCE(knob_int("MGDT_CONV3_LDS", 1));      // experiment knob: 0 = never
   if (!mode) return false;
-  static const bool ws2 = !(getenv("MGDT_C3_WAVES8") && atoi(getenv("MGDT_C3_WAVES8")) == 0);   // experiment knob: 0 = the four-wave form everywhere
+  const bool ws2 = KNOB_ONCE(knob_int("MGDT_C3_WAVES8", 1) != 0);   // experiment knob: 0 = the four-wave form everywhere
   const bool wide = mode >= 3 || ws2;     // the eight-wave forms also win where the four-wave ones lost to the igemm kernel: 64 -> 128 stride 2 (26.9 vs 30.6 us) and 80 -> 80 on 12x16 tiles (48.2 vs 50.9 us)
   const int Cin = x->c, Cout = y->c;
   // stride 2 - instantiated: bf16, 4 cout blocks per workgroup, Cin = 32 / 64.  Measured (B = 32, bench step): 32 -> 64 at 160 -> 80 35.9 us (igemm 38-40): default;
@@ -239,9 +239,7 @@ bool mgdt_conv3x3_lds_plan(const mgdt_view* x, const mgdt_view* y, int act, int 
   if (Cin % 8 || Cin < 32 || Cin > 80 || Cout % 4 || Cout < 32 || (act != MGDT_ACT_SILU && act != MGDT_ACT_NONE && act != MGDT_ACT_RELU)) return false;
   const long M = (long)x->n * x->h * x->w;
   if (M < 16 * 1024 || x->h < 16 || x->w < 16) return false;                                    // small maps: the igemm kernel's finer tiles fill the chip better
-  p->extx = ((long)(x->n - 1) * x->sn + (long)(x->h - 1) * x->sh + (long)(x->w - 1) * x->sw + x->c) * 2;
-  p->exty = ((long)(y->n - 1) * y->sn + (long)(y->h - 1) * y->sh + (long)(y->w - 1) * y->sw + y->c) * 2;
-  if (p->extx >= 0x7fffffffL || p->exty >= 0x7fffffffL) return false;
+  if (!view_spans_32bit(x, 2) || !view_spans_32bit(y, 2)) return false;
   p->XP = q8 ? Cin + 16 : Cin * 2 + 16;
   // every cout block in ONE workgroup (the input region is then staged once per tile); layers whose whole weight panel does not fit next to the
   // region stay on the igemm kernel: splitting the couts over workgroups re-reads the input per group and measured no faster
@@ -275,19 +273,21 @@ bool mgdt_conv3x3_lds_plan(const mgdt_view* x, const mgdt_view* y, int act, int 
   return true;
 }
 
-// true when the layer is launched here (the caller returns), false: conv_igemm takes it
-bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
+// 1 when the layer is launched here (the caller returns), 0: conv_igemm takes it, < 0: a status (error text set), nothing launched
+int mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
                              const float* q8_oscale, float q8_xq, int stride) {
   const bool q8 = q8_oscale != nullptr;                    // e4m3 panel from mgdt_conv_pack_fp8
   C3Plan pl;
-  if (!mgdt_conv3x3_lds_plan(x, y, act, CP, nchunks, NTtot, q8, stride, &pl)) return false;
+  if (!mgdt_conv3x3_lds_plan(x, y, act, CP, nchunks, NTtot, q8, stride, &pl)) return 0;
   const int Cin = x->c, Cout = y->c, NBW = pl.NBW, MT = pl.MT, nwg = pl.nwg;
   const size_t lds = pl.lds;
   const bool ws2 = pl.waves == 8;
   C3Args a;
   memset(&a, 0, sizeof(a));
-  a.x = (const char*)x->p; a.xsn = (int)(x->sn * 2); a.xsh = (int)(x->sh * 2); a.xsw = (int)(x->sw * 2); a.x_bytes = (uint32_t)pl.extx;
-  a.y = (char*)y->p; a.ysn = (int)(y->sn * 2); a.ysh = (int)(y->sh * 2); a.ysw = (int)(y->sw * 2); a.y_bytes = (uint32_t)pl.exty;
+  const ViewPolicy pol = {0, false, 0, 0, false};      // the caller (mgdt_conv2d_fwd) has tested NHWC and alignment, the plan the extents
+  const char* yp = nullptr;
+  if (!bind_view(x, 2, pol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(y, 2, pol, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes)) return 0;
+  a.y = (char*)yp;
   a.wpk = (const char*)packed_w; a.bias = bias;
   a.N = x->n; a.H = x->h; a.W = x->w; a.Ho = y->h; a.Wo = y->w; a.Cin = Cin; a.Cout = Cout; a.CP = CP; a.nchunks = nchunks; a.NTtot = NTtot; a.act = act;
   a.XP = pl.XP;
@@ -295,52 +295,27 @@ bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void*
   a.ncg = pl.ncg;
   a.tiles_x = pl.tiles_x; a.tiles_per_img = pl.tiles_per_img; a.ntiles = pl.ntiles;
   a.fd_tpi = make_fastdiv((uint32_t)a.tiles_per_img); a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_cp = make_fastdiv((uint32_t)CP);
- #define C3_LAUNCH_Q8(NB, ACTV)                                                                                      \
+  static StampBuf stamps;      // MGDT_C3_DBG: 6 words per workgroup
+  const bool dbg = knob_set("MGDT_C3_DBG");
+  if (dbg && !stamps.ensure((size_t)nwg * 6)) MGDT_FAIL(MGDT_WORKSPACE, "conv2d(3x3 lds): no memory for the MGDT_C3_DBG stamps");
+  a.dbg = dbg ? stamps.p : nullptr;
+#define C3_GO(THREADS, ...)                                                                                          \
   {                                                                                                                  \
-    static std::atomic<bool> qattr{false}, qattr18{false}, qattr23{false};                                            \
-    if (nchunks == 18) {                                                                                             \
-      if (!qattr18) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<NB, ACTV, 18, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); qattr18 = true; } \
-      conv3x3_lds_kernel<NB, ACTV, 18, 4, true><<<nwg, 256, lds, st>>>(a);                                           \
-    } else if (nchunks == 23) {                                                                                      \
-      if (!qattr23) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<NB, ACTV, 23, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); qattr23 = true; } \
-      conv3x3_lds_kernel<NB, ACTV, 23, 4, true><<<nwg, 256, lds, st>>>(a);                                           \
-    } else {                                                                                                         \
-      if (!qattr) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<NB, ACTV, 0, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); qattr = true; } \
-      conv3x3_lds_kernel<NB, ACTV, 0, 4, true><<<nwg, 256, lds, st>>>(a);                                            \
-    }                                                                                                                \
+    if (int rc_ = lds_optin<conv3x3_lds_kernel<__VA_ARGS__>>("conv2d(3x3 lds)")) return rc_;                         \
+    conv3x3_lds_kernel<__VA_ARGS__><<<nwg, THREADS, lds, st>>>(a);                                                   \
   }
+#define C3_LAUNCH_Q8(NB, ACTV) \
+  if (nchunks == 18) C3_GO(256, NB, ACTV, 18, 4, true) else if (nchunks == 23) C3_GO(256, NB, ACTV, 23, 4, true) else C3_GO(256, NB, ACTV, 0, 4, true)
 #define C3_ACT_Q8(NB) \
   if (act == MGDT_ACT_SILU) C3_LAUNCH_Q8(NB, MGDT_ACT_SILU) else if (act == MGDT_ACT_RELU) C3_LAUNCH_Q8(NB, MGDT_ACT_RELU) else C3_LAUNCH_Q8(NB, MGDT_ACT_NONE)
-#define C3_LAUNCH(NB, ACTV, MTV, WSV)                                                                                     \
-  {                                                                                                                  \
-    static std::atomic<bool> attr{false}, attr18{false}, attr23{false};                                                                        \
-    if (nchunks == 18) {                                                                                             \
-      if (!attr18) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<NB, ACTV, 18, MTV, false, 1, WSV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr18 = true; } \
-      conv3x3_lds_kernel<NB, ACTV, 18, MTV, false, 1, WSV><<<nwg, 256 * WSV, lds, st>>>(a);                                                    \
-    } else if (nchunks == 23) {                                                                                      \
-      if (!attr23) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<NB, ACTV, 23, MTV, false, 1, WSV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr23 = true; } \
-      conv3x3_lds_kernel<NB, ACTV, 23, MTV, false, 1, WSV><<<nwg, 256 * WSV, lds, st>>>(a);                                               \
-    } else {                                                                                                         \
-      if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<NB, ACTV, 0, MTV, false, 1, WSV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-      conv3x3_lds_kernel<NB, ACTV, 0, MTV, false, 1, WSV><<<nwg, 256 * WSV, lds, st>>>(a);                                                     \
-    }                                                                                                                \
-  }
+#define C3_LAUNCH(NB, ACTV, MTV, WSV)                                                                                \
+  if (nchunks == 18) C3_GO(256 * WSV, NB, ACTV, 18, MTV, false, 1, WSV)                                              \
+  else if (nchunks == 23) C3_GO(256 * WSV, NB, ACTV, 23, MTV, false, 1, WSV)                                         \
+  else C3_GO(256 * WSV, NB, ACTV, 0, MTV, false, 1, WSV)
 #define C3_ACT(NB, MTV, WSV) \
   if (act == MGDT_ACT_SILU) C3_LAUNCH(NB, MGDT_ACT_SILU, MTV, WSV) else if (act == MGDT_ACT_RELU) C3_LAUNCH(NB, MGDT_ACT_RELU, MTV, WSV) else C3_LAUNCH(NB, MGDT_ACT_NONE, MTV, WSV)
-  static unsigned long long* dbgbuf = nullptr;
-  if (getenv("MGDT_C3_DBG") && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, 256 * 6 * 8);   // nwg <= 256
-  a.dbg = dbgbuf;
-#define C3_LAUNCH_S2(ACTV, NCHV)                                                                                      \
-  {                                                                                                                  \
-    static std::atomic<bool> sattr{false}, sattr8{false};                                                            \
-    if (ws2) {                                                                                                       \
-      if (!sattr8) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<4, ACTV, NCHV, 2, false, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); sattr8 = true; } \
-      conv3x3_lds_kernel<4, ACTV, NCHV, 2, false, 2, 2><<<nwg, 512, lds, st>>>(a);                                   \
-    } else {                                                                                                         \
-      if (!sattr) { (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<4, ACTV, NCHV, 2, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); sattr = true; } \
-      conv3x3_lds_kernel<4, ACTV, NCHV, 2, false, 2><<<nwg, 256, lds, st>>>(a);                                      \
-    }                                                                                                                \
-  }
+#define C3_LAUNCH_S2(ACTV, NCHV) \
+  if (ws2) C3_GO(512, 4, ACTV, NCHV, 2, false, 2, 2) else C3_GO(256, 4, ACTV, NCHV, 2, false, 2)
 #define C3_ACT_S2(NCHV) \
   if (act == MGDT_ACT_SILU) C3_LAUNCH_S2(MGDT_ACT_SILU, NCHV) else if (act == MGDT_ACT_RELU) C3_LAUNCH_S2(MGDT_ACT_RELU, NCHV) else C3_LAUNCH_S2(MGDT_ACT_NONE, NCHV)
   if (stride == 2) {
@@ -357,14 +332,13 @@ bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void*
 #undef C3_LAUNCH_S2
 #undef C3_LAUNCH_Q8
 #undef C3_LAUNCH
-  if (dbgbuf) {
-    std::vector<unsigned long long> h(256 * 6);
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
+#undef C3_GO
+  if (dbg) {
+    const std::vector<unsigned long long> h = stamps.read((size_t)nwg * 6, st);
     unsigned long long t0 = ~0ull, t1 = 0; double c = 0, m = 0, e = 0, nt = 0;
     for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, h[i * 6]); t1 = std::max(t1, h[i * 6 + 1]); c += h[i * 6 + 2]; m += h[i * 6 + 3]; e += h[i * 6 + 4]; nt += h[i * 6 + 5]; }
     fprintf(stderr, "conv3x3_lds cin %d cout %d %dx%d: %d wgs, %d tiles, span %.1f us; per tile (us): wait+commit %.2f mfma %.2f epilogue %.2f\n", Cin, Cout, x->h, x->w, nwg,
             a.ntiles, (t1 - t0) * 0.01, c / nt * 0.01, m / nt * 0.01, e / nt * 0.01);
   }
-  return true;
+  return 1;
 }

@@ -409,7 +409,7 @@ extern "C" int mgdt_conv_pack_batch(const mgdt_pack_desc* d, int n, mgdt_stream 
 }
 
 bool mgdt_conv3x3_lds_plan(const mgdt_view* x, const mgdt_view* y, int act, int CP, int nchunks, int NTtot, bool q8, int stride, C3Plan* p);   // conv3x3_lds.hip
-bool mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
+int mgdt_conv3x3_lds_launch(const mgdt_view* x, const mgdt_view* y, const void* packed_w, const float* bias, int act, int CP, int nchunks, int NTtot, hipStream_t st,
                              const float* q8_oscale, float q8_xq, int stride);
 
 template <typename T, int NT, int MT, bool Q8>
@@ -449,7 +449,7 @@ static int conv_check_shapes(const mgdt_view* x, const mgdt_view* y, int k, int 
   return MGDT_OK;
 }
 static inline bool conv_view_aligned(const mgdt_view* v, int q, int dtype) {
-  return v->sc == 1 && v->sw % q == 0 && v->sh % q == 0 && v->sn % q == 0 && ((uintptr_t)v->p % (q * dtype_size(dtype))) == 0;
+  return v->sc == 1 && view_aligned(v, q, (int)dtype_size(dtype));
 }
 // plain 3x3 bf16 layers: the only ones the LDS-staged kernel (conv3x3_lds.hip) is asked about
 static inline bool conv_lds_candidate(int tapmode, int dtype, int k, bool x2, bool in_scale, bool in_shift, bool r1, bool r2) {
@@ -459,32 +459,27 @@ static int igemm_plan(int nchunks, int NTtot, long M, bool q8, bool extra, Igemm
   const int WB = q8 ? 512 : 1024;
   // tile choice: NT = cout blocks per workgroup - as many as divide NTtot and keep the whole weight panel in LDS
   // (activations are then read NTtot/NT times; once when NT == NTtot), fewer when the grid would starve the 256 CUs
-  int LDS_PANEL_KIB = 144;   // measured (round 2, tools/knob_sweep.sh, B = 32 bf16): 96 -> 1.377, 128 -> 1.326, 144 / 150 -> 1.312 ms per step (NT 2 -> 4 on the 128 -> 256 stride-2 conv)
-  { const char* e = getenv("MGDT_CONV_PANEL_KIB"); if (e) LDS_PANEL_KIB = atoi(e); }   // experiment knob (not part of the ABI)
+  const int LDS_PANEL_KIB = knob_int("MGDT_CONV_PANEL_KIB", 144);   // experiment knob, read per call.  144: measured (round 2, tools/knob_sweep.sh, B = 32 bf16): 96 -> 1.377, 128 -> 1.326, 144 / 150 -> 1.312 ms per step (NT 2 -> 4 on the 128 -> 256 stride-2 conv)
   int NT = 1;
   for (int c : {8, 6, 5, 4, 3, 2, 1})
     if (NTtot % c == 0 && (long)nchunks * c * WB <= LDS_PANEL_KIB * 1024L) { NT = c; break; }
   int MT = 2;   // MT=2 with depth-4 prefetch measured faster than MT=4 on every wide layer of the target nets
-  if (!q8 && NT == 1 && NTtot == 1) { const char* e = getenv("MGDT_CONV_MT1"); MT = e && atoi(e) == 4 ? 4 : 2; }   // (MT = 8 spilled registers: removed)
+  if (!q8 && NT == 1 && NTtot == 1) MT = knob_int("MGDT_CONV_MT1", 2) == 4 ? 4 : 2;   // experiment knob, read per call (MT = 8 spilled registers: removed)
   int waves = 8;
   auto wgs = [&](int nt, int wv) { return (long)cdiv(M, 16 * wv * MT) * (NTtot / nt); };
   // (4-wave workgroups for small maps were tried: 8 waves measured faster on the whole net - fewer, fuller workgroups stage the weight panel less often)
   {
-    const char* e = getenv("MGDT_CONV_MINWG");            // experiment knob (not part of the ABI)
-    const int minwg = e ? atoi(e) : 128;               // measured: 64 -> 1.800, 128 -> 1.791, 256 -> 1.811, 512 -> 1.876 ms per step
+    const int minwg = knob_int("MGDT_CONV_MINWG", 128);   // experiment knob, read per call; measured: 64 -> 1.800, 128 -> 1.791, 256 -> 1.811, 512 -> 1.876 ms per step
     while (wgs(NT, waves) < minwg && NT > 1 && NT % 2 == 0) NT /= 2;    // ... and split the couts over workgroups
   }
   {   // a grid a few workgroups larger than what is resident at once (~3 eight-wave workgroups per CU) runs a second, almost empty round at the first one's
       // full cost: 32 -> 512 at 40x40 (B = 32) is 800 workgroups on 768 slots.  Halving NT gives twice as many half-size workgroups: two full rounds of half the work.
     // Measured (r02f): that layer 30.6 -> 28.1 us, but the whole step 1.294 -> 1.322 ms (the next kernels start behind a longer tail of small workgroups): off by default.
-    static const bool tail_split = getenv("MGDT_CONV_TAIL_SPLIT") != nullptr;     // experiment knob (not part of the ABI)
+    const bool tail_split = KNOB_ONCE(knob_set("MGDT_CONV_TAIL_SPLIT"));     // experiment knob (not part of the ABI)
     const long w0 = wgs(NT, waves);
     if (tail_split && w0 > 768 && w0 <= 960 && NT % 2 == 0) NT /= 2;
   }
-  {   // experiment knob (not part of the ABI)
-    const char* e;
-    if ((e = getenv("MGDT_CONV_WAVES"))) waves = std::min(8, std::max(1, atoi(e)));   // __launch_bounds__(512): at most 8 waves per workgroup
-  }
+  waves = std::min(8, std::max(1, knob_int("MGDT_CONV_WAVES", waves)));   // experiment knob, read per call.  __launch_bounds__(512): at most 8 waves per workgroup
   p->numTiles = cdiv(M, 16 * waves * MT);
   p->T8 = cdiv(p->numTiles, 8);
   p->tab_bytes = (nchunks + 3) / 4 * 4 * 4 * 16;   // uint4 per piece, padded to a multiple of 4 chunks (>= nchp in the kernel)
@@ -492,8 +487,7 @@ static int igemm_plan(int nchunks, int NTtot, long M, bool q8, bool extra, Igemm
   if (panel <= (size_t)LDS_PANEL_KIB * 1024) { p->seg_chunks = nchunks; p->nseg = 1; }
   else { p->seg_chunks = 64; p->nseg = cdiv(nchunks, p->seg_chunks); }   // NT == 1 here: 64 KiB segments
   p->lds = p->tab_bytes + (size_t)(q8 ? 2 : 1) * NT * 16 * sizeof(float) + (size_t)p->seg_chunks * NT * WB;
-  int gcap = waves == 8 ? 256 : 1024;   // measured with the 144 KiB panels: 256 -> 1.293, 384 -> 1.306, 512 -> 1.312 ms per step (one persistent workgroup per CU and cout group)
-  { const char* e = getenv("MGDT_CONV_GCAP"); if (e) gcap = atoi(e); }
+  const int gcap = knob_int("MGDT_CONV_GCAP", waves == 8 ? 256 : 1024);   // experiment knob, read per call; measured with the 144 KiB panels: 256 -> 1.293, 384 -> 1.306, 512 -> 1.312 ms per step (one persistent workgroup per CU and cout group)
   if (p->lds > 160 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: %zu bytes of LDS for NT=%d, %d chunks", p->lds, NT, p->seg_chunks);   // cannot happen with panels <= 150 KiB (table <= 9.4 KiB)
   p->gx = std::min(8 * p->T8, gcap); p->gy = NTtot / NT;   // persistent: ~2 (8-wave) / 4 (4-wave) workgroups per CU
   p->NT = NT; p->MT = MT; p->waves = waves;
@@ -546,21 +540,16 @@ static int conv2d_fwd_impl(const mgdt_view* x, const mgdt_view* x2, const float*
 
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  const long sz = (long)dtype_size(dtype);
-  auto extent = [&](const mgdt_view* v) { return ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz; };
-  // every view is addressed through a 32-bit buffer descriptor: extents < 2 GiB, row / pixel strides < 8 MiB (24-bit multiplies)
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes) {
-    if (!v || !v->p) return;
-    if (extent(v) >= 0x7fffffffL || v->sh * sz >= (1L << 23) || v->sw * sz >= (1L << 23)) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * sz); *sh = (int)(v->sh * sz); *sw = (int)(v->sw * sz); *bytes = (uint32_t)extent(v);
-  };
+  const int sz = (int)dtype_size(dtype);
+  // every view is addressed through a 32-bit buffer descriptor: extents < 2 GiB, row / pixel strides < 8 MiB (24-bit multiplies); alignment and
+  // sc == 1 were tested above (conv_view_aligned); x2, r1, r2 may be absent
+  const ViewPolicy pol = {0, false, 1L << 23, 1L << 23, true};
   const char* yp = nullptr;
-  bind(x, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes);
-  bind(x2, &a.x2, &a.x2sn, &a.x2sh, &a.x2sw, &a.x2_bytes);
-  bind(y, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes);
-  bind(r1, &a.r1, &a.r1sn, &a.r1sh, &a.r1sw, &a.r1_bytes);
-  bind(r2, &a.r2, &a.r2sn, &a.r2sh, &a.r2sw, &a.r2_bytes);
+  bool fits = bind_view(x, sz, pol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes);
+  fits &= bind_view(x2, sz, pol, &a.x2, &a.x2sn, &a.x2sh, &a.x2sw, &a.x2_bytes);
+  fits &= bind_view(y, sz, pol, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes);
+  fits &= bind_view(r1, sz, pol, &a.r1, &a.r1sn, &a.r1sh, &a.r1sw, &a.r1_bytes);
+  fits &= bind_view(r2, sz, pol, &a.r2, &a.r2sn, &a.r2sh, &a.r2sw, &a.r2_bytes);
   if (!fits) MGDT_FAIL(MGDT_BAD_SHAPE, "conv2d: a view spans >= 2 GiB or has a row stride >= 8 MiB");
   a.y = (char*)yp;
   a.in_scale = in_scale; a.in_shift = in_shift;
@@ -576,10 +565,13 @@ static int conv2d_fwd_impl(const mgdt_view* x, const mgdt_view* x2, const float*
   a.M = (int)M; a.HoWo = Ho * Wo;
   a.fd_howo = make_fastdiv((uint32_t)a.HoWo); a.fd_wo = make_fastdiv((uint32_t)Wo);
   // plain 3x3 stride-1 bf16 layers with 32-80 input channels on large maps: the LDS-staged kernel (conv3x3_lds.hip)
-  if (conv_lds_candidate(tapmode, dtype, k, x2 && x2->p, in_scale, in_shift, r1 && r1->p, r2 && r2->p) &&
-      mgdt_conv3x3_lds_launch(x, y, packed_w, bias, act, a.CP, a.nchunks, a.NTtot, (hipStream_t)s, q8_oscale, q8_xq, stride)) {
-    MGDT_CHECK_LAUNCH("conv2d(3x3 lds)");
-    return MGDT_OK;
+  if (conv_lds_candidate(tapmode, dtype, k, x2 && x2->p, in_scale, in_shift, r1 && r1->p, r2 && r2->p)) {
+    const int took = mgdt_conv3x3_lds_launch(x, y, packed_w, bias, act, a.CP, a.nchunks, a.NTtot, (hipStream_t)s, q8_oscale, q8_xq, stride);
+    if (took < 0) return took;
+    if (took) {
+      MGDT_CHECK_LAUNCH("conv2d(3x3 lds)");
+      return MGDT_OK;
+    }
   }
 
   IgemmPlan pl;

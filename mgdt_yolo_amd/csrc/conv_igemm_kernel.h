@@ -420,21 +420,16 @@ struct IgemmPlan { int NT, MT, D, extra, waves, gx, gy, numTiles, T8, tab_bytes,
 
 template <typename T, int NT, int MT, bool Q8 = false>
 int launch_igemm(const ConvArgs& a, const IgemmPlan& p, hipStream_t st) {
-  static std::atomic<bool> attr_set{false};  // idempotent; racing setters write the same value
   constexpr bool M1 = NT == 1;   // the segmented-panel variant exists for NT == 1 only (host never asks for it otherwise)
-  const void* ks[8] = {(const void*)conv_igemm_kernel<T, NT, MT, 2, false, false, Q8>, (const void*)conv_igemm_kernel<T, NT, MT, 4, false, false, Q8>,
-                       (const void*)conv_igemm_kernel<T, NT, MT, 2, true, false, Q8>,  (const void*)conv_igemm_kernel<T, NT, MT, 4, true, false, Q8>,
-                       (const void*)conv_igemm_kernel<T, NT, MT, 2, false, M1, Q8>,    (const void*)conv_igemm_kernel<T, NT, MT, 4, false, M1, Q8>,
-                       (const void*)conv_igemm_kernel<T, NT, MT, 2, true, M1, Q8>,     (const void*)conv_igemm_kernel<T, NT, MT, 4, true, M1, Q8>};
-  if (!attr_set) {
-    for (const void* k : ks) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "conv2d: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    attr_set = true;
-  }
+#define IGEMM_K(D, EXTRA, SEG) conv_igemm_kernel<T, NT, MT, D, EXTRA, SEG, Q8>
+#define IGEMM_KS IGEMM_K(2, false, false), IGEMM_K(4, false, false), IGEMM_K(2, true, false), IGEMM_K(4, true, false), \
+                 IGEMM_K(2, false, M1), IGEMM_K(4, false, M1), IGEMM_K(2, true, M1), IGEMM_K(4, true, M1)
+  void (*const ks[8])(ConvArgs) = {IGEMM_KS};
+  if (int rc = lds_optin<IGEMM_KS>("conv2d")) return rc;
+#undef IGEMM_KS
+#undef IGEMM_K
   void* kargs[] = {(void*)&a};
-  hipError_t le = hipLaunchKernel(ks[(p.nseg > 1 ? 4 : 0) + (p.extra ? 2 : 0) + (p.D == 4 ? 1 : 0)], dim3(p.gx, p.gy), dim3(p.waves * 64), kargs, p.lds, st);
+  hipError_t le = hipLaunchKernel((const void*)ks[(p.nseg > 1 ? 4 : 0) + (p.extra ? 2 : 0) + (p.D == 4 ? 1 : 0)], dim3(p.gx, p.gy), dim3(p.waves * 64), kargs, p.lds, st);
   if (le != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "conv2d: launch: %s", hipGetErrorString(le));
   MGDT_CHECK_LAUNCH("conv2d_fwd");
   return MGDT_OK;

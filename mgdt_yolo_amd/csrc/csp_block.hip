@@ -614,9 +614,8 @@ constexpr size_t CSP_LDS_2WG = 80 * 1024;
 constexpr double CSP_1WG_COST = 2.0;
 
 static bool csp_pick_tile(int mode, int H, int W, int N, int wd, int nbtl, int catC, size_t extra, CspGeom* best) {
-  const char* e = getenv("MGDT_CSP_TILE");       // experiment knob "th,tw" (not part of the ABI)
   int fth = 0, ftw = 0;
-  if (e && sscanf(e, "%d,%d", &fth, &ftw) != 2) fth = ftw = 0;
+  knob_pair("MGDT_CSP_TILE", &fth, &ftw);       // experiment knob "th,tw", read per call (not part of the ABI)
   const int qh = mode == 0 ? H / 2 : H, qw = mode == 0 ? W / 2 : W;     // MSPA: a tile must lie inside one adaptive_avg_pool2d(2) bin
   double best_cost = 1e30;
   bool found = false;
@@ -671,17 +670,10 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
   if (mode == 2) return csp_c3_fwd(x, mid, mid_bias, nbtl, shortcut, back, back_bias, wd, y, s);
   CspArgs a;
   memset(&a, 0, sizeof(a));
-  const long sz = 2;
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes, int q) {
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz;
-    if (v->sc != 1 || v->sw % q || v->sh % q || v->sn % q || (uintptr_t)v->p % (q * sz) || ext >= 0x7fffffffL) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * sz); *sh = (int)(v->sh * sz); *sw = (int)(v->sw * sz); *bytes = (uint32_t)ext;
-  };
+  const ViewPolicy pol = {4, true, 0, 0, false};      // 8-byte pieces of NHWC bf16
   const char* yp = nullptr;
-  bind(x, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes, 4);
-  bind(y, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes, 4);
-  if (!fits) MGDT_FAIL(MGDT_BAD_SHAPE, "csp_block: views must be aligned NHWC (sc == 1) and span < 2 GiB");
+  if (!bind_view(x, 2, pol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(y, 2, pol, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "csp_block: views must be aligned NHWC (sc == 1) and span < 2 GiB");
   a.y = (char*)yp;
   a.front = (const char*)front; a.front_bias = front_bias;
   for (int j = 0; j < 2 * nbtl; ++j) { a.mid[j] = (const char*)mid[j]; a.mid_bias[j] = mid_bias[j]; }
@@ -705,28 +697,17 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
   a.per_xcd = cdiv(a.total_tiles, 8);
   const int grid = 8 * a.per_xcd;
   hipStream_t st = (hipStream_t)s;
-  static unsigned long long* dbgbuf = nullptr;            // MGDT_CSP_DBG=1: per-workgroup phase stamps, printed after the launch (debug only)
-  static size_t dbgcap = 0;
-  if (getenv("MGDT_CSP_DBG") && dbgcap < (size_t)a.total_tiles * 8) {
-    if (dbgbuf) (void)hipFree(dbgbuf);
-    dbgcap = (size_t)a.total_tiles * 8;
-    (void)hipMalloc((void**)&dbgbuf, dbgcap * 8);
-  }
-  a.dbg = getenv("MGDT_CSP_DBG") ? dbgbuf : nullptr;
+  static StampBuf stamps;            // MGDT_CSP_DBG=1: per-workgroup phase stamps, printed after the launch (debug only)
+  const bool dbg = knob_set("MGDT_CSP_DBG");
+  if (dbg && !stamps.ensure((size_t)a.total_tiles * 8)) MGDT_FAIL(MGDT_WORKSPACE, "csp_block: no memory for the MGDT_CSP_DBG stamps");
+  a.dbg = dbg ? stamps.p : nullptr;
   // experiment knob, read per call (not part of the ABI): MGDT_CSP_PAIR=0 = the unpaired wd = 8 form
-  const char* ep = getenv("MGDT_CSP_PAIR");
-  const bool pair = !(ep && ep[0] == '0');
+  const bool pair = knob_unless0("MGDT_CSP_PAIR");
   // likewise MGDT_CSP_COMPACT=0 = the linear pixel walk of the 3x3 convs (same MFMAs per needed pixel: bit-identical outputs)
-  const char* ec = getenv("MGDT_CSP_COMPACT");
-  const bool compact = !(ec && ec[0] == '0');
+  const bool compact = knob_unless0("MGDT_CSP_COMPACT");
 #define CSP_LAUNCH(...)                                                                                              \
   do {                                                                                                                      \
-    static std::atomic<bool> attr{false};                                                                                            \
-    if (!attr) {                                                                                                            \
-      hipError_t e_ = hipFuncSetAttribute((const void*)csp_block_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      if (e_ != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "csp_block: hipFuncSetAttribute: %s", hipGetErrorString(e_));         \
-      attr = true;                                                                                                          \
-    }                                                                                                                       \
+    if (int rc_ = lds_optin<csp_block_kernel<__VA_ARGS__>>("csp_block")) return rc_;                                        \
     csp_block_kernel<__VA_ARGS__><<<grid, CSP_THREADS, g.lds, st>>>(a);                                                      \
   } while (0)
 #define CSP_WALK(...) do { if (compact) CSP_LAUNCH(__VA_ARGS__, true); else CSP_LAUNCH(__VA_ARGS__, false); } while (0)
@@ -739,9 +720,7 @@ extern "C" int mgdt_csp_block_fwd(int mode, const mgdt_view* x, const void* fron
 #undef CSP_LAUNCH
   MGDT_CHECK_LAUNCH("csp_block_fwd");
   if (a.dbg) {
-    std::vector<unsigned long long> h((size_t)a.total_tiles * 8);
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost);
+    const std::vector<unsigned long long> h = stamps.read((size_t)a.total_tiles * 8, st);
     unsigned long long t0 = ~0ull, t1 = 0;
     double ph[6] = {0, 0, 0, 0, 0, 0};
     for (int i = 0; i < a.total_tiles; ++i) {

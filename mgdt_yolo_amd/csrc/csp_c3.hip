@@ -185,9 +185,8 @@ int csp_c3_supported(int cin, int cout, int wd, int nbtl, int h, int w, int dtyp
 }
 
 static bool c3_pick_tile(int H, int W, int N, int wd, int nbtl, C3Geom* best) {
-  const char* e = getenv("MGDT_CSP_TILE");       // experiment knob "th,tw" shared with modes 0 / 1 (not part of the ABI)
   int fth = 0, ftw = 0;
-  if (e && sscanf(e, "%d,%d", &fth, &ftw) != 2) fth = ftw = 0;
+  knob_pair("MGDT_CSP_TILE", &fth, &ftw);       // experiment knob "th,tw" shared with modes 0 / 1, read per call (not part of the ABI)
   double best_cost = 1e30;
   bool found = false;
   for (int th = 2; th <= std::min(H, 32); ++th) {
@@ -226,11 +225,8 @@ int csp_c3_fwd(const mgdt_view* x, const void* const* mid, const float* const* m
                int wd, const mgdt_view* y, mgdt_stream s) {
   C3Args a;
   memset(&a, 0, sizeof(a));
-  auto ok = [&](const mgdt_view* v, int q) {     // q: elements per access (x: 16-byte loads, y: 8-byte stores)
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * 2;
-    return v->sc == 1 && v->sw % q == 0 && v->sh % q == 0 && v->sn % q == 0 && (uintptr_t)v->p % (2 * q) == 0 && ext < 0x7fffffffL;
-  };
-  if (!ok(x, 8) || !ok(y, 4)) MGDT_FAIL(MGDT_BAD_SHAPE, "csp_block (C3): views must be NHWC (sc == 1), x in 16-byte and y in 8-byte aligned pixels, span < 2 GiB");
+  // the kernel keeps 64-bit strides; x: 16-byte loads, y: 8-byte stores
+  if (!view_fits(x, 2, {8, true, 0, 0, false}) || !view_fits(y, 2, {4, true, 0, 0, false})) MGDT_FAIL(MGDT_BAD_SHAPE, "csp_block (C3): views must be NHWC (sc == 1), x in 16-byte and y in 8-byte aligned pixels, span < 2 GiB");
   C3Geom g;
   if (!c3_pick_tile(x->h, x->w, x->n, wd, nbtl, &g)) MGDT_FAIL(MGDT_BAD_SHAPE, "csp_block (C3): no tile fits %dx%d wd=%d n=%d", x->h, x->w, wd, nbtl);
   a.x = (const char*)x->p; a.xsn = x->sn * 2; a.xsh = x->sh * 2; a.xsw = x->sw * 2;
@@ -245,12 +241,7 @@ int csp_c3_fwd(const mgdt_view* x, const void* const* mid, const float* const* m
   hipStream_t st = (hipStream_t)s;
 #define C3_LAUNCH(WD_)                                                                                                                    \
   do {                                                                                                                                     \
-    static std::atomic<bool> attr{false};                                                                                                  \
-    if (!attr) {                                                                                                                           \
-      hipError_t e_ = hipFuncSetAttribute((const void*)csp_c3_kernel<WD_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3_LDS_MAX);  \
-      if (e_ != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "csp_block (C3): hipFuncSetAttribute: %s", hipGetErrorString(e_));                 \
-      attr = true;                                                                                                                         \
-    }                                                                                                                                      \
+    if (int rc_ = lds_optin<csp_c3_kernel<WD_>>("csp_block (C3)", (int)C3_LDS_MAX)) return rc_;                                            \
     csp_c3_kernel<WD_><<<(int)grid, C3_THREADS, g.lds, st>>>(a);                                                                           \
   } while (0)
   switch (wd) { case 16: C3_LAUNCH(16); break; case 32: C3_LAUNCH(32); break; default: C3_LAUNCH(64); break; }

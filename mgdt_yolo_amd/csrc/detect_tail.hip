@@ -213,17 +213,11 @@ static int detect_tail_launch(const mgdt_view* tb, const mgdt_view* tc, const vo
     MGDT_FAIL(MGDT_BAD_SHAPE, "detect_tail: shapes");
   DtArgs a;
   memset(&a, 0, sizeof(a));
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes, int q) {
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * 2;
-    if (v->sc != 1 || v->sw % q || v->sh % q || v->sn % q || (uintptr_t)v->p % (q * 2) || ext >= 0x7fffffffL) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * 2); *sh = (int)(v->sh * 2); *sw = (int)(v->sw * 2); *bytes = (uint32_t)ext;
-  };
+  const ViewPolicy in16 = {8, true, 0, 0, false}, out8 = {4, true, 0, 0, false};      // NHWC bf16: 16-byte loads, 8-byte stores
   const char* fp = nullptr;
-  bind(tb, &a.tb, &a.bsn, &a.bsh, &a.bsw, &a.tb_bytes, 8);
-  bind(tc, &a.tc, &a.csn, &a.csh, &a.csw, &a.tc_bytes, 8);
-  bind(feat, &fp, &a.fsn, &a.fsh, &a.fsw, &a.feat_bytes, 4);
-  if (!fits) MGDT_FAIL(MGDT_BAD_SHAPE, "detect_tail: views must be 16-byte aligned NHWC (sc == 1) below 2 GiB");
+  if (!bind_view(tb, 2, in16, &a.tb, &a.bsn, &a.bsh, &a.bsw, &a.tb_bytes) || !bind_view(tc, 2, in16, &a.tc, &a.csn, &a.csh, &a.csw, &a.tc_bytes) ||
+      !bind_view(feat, 2, out8, &fp, &a.fsn, &a.fsh, &a.fsw, &a.feat_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "detect_tail: views must be 16-byte aligned NHWC (sc == 1) below 2 GiB");
   a.feat = (char*)fp;
   a.wb = (const char*)wb; a.bb = bb; a.wc = (const char*)wc; a.bc = bc; a.y = y; a.best = best_keys;
   a.wb3 = (const char*)wb3; a.bb3 = bb3;
@@ -235,12 +229,8 @@ static int detect_tail_launch(const mgdt_view* tb, const mgdt_view* tc, const vo
   a.aug = aug ? 1 : 0; a.aug_flip = aug_flip ? 1 : 0; a.aug_s = aug_scale; a.aug_w = aug_img_w;
   const size_t lds = 1024 + (size_t)a.kch * a.nbc * 1024 + (size_t)(16 + a.nbc * 16) * 4 + (size_t)4 * DT_WT * 4 + 5 * 1024 + 64;
   if (lds > 150 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "detect_tail: nc=%d needs %zu B of LDS", nc, lds);
-  static size_t attr = 0;
-  if (lds > 64 * 1024 && lds > attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)detect_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "detect_tail: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr = 150 * 1024;
-  }
+  if (lds > 64 * 1024)
+    if (int rc = lds_optin<detect_tail_kernel>("detect_tail", 150 * 1024)) return rc;
   const int grid = std::min(cdiv(a.units, 4), 1024);
   detect_tail_kernel<<<grid, DT_THREADS, lds, (hipStream_t)s>>>(a);
   MGDT_CHECK_LAUNCH("detect_tail_fwd");

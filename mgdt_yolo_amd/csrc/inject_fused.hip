@@ -458,12 +458,7 @@ extern "C" int mgdt_conv1x1_inject_supported(int cin, int cout, int h, int w, in
 
 template <int KC, int NB>
 static int inj_launch(const InjArgs& a, size_t lds, hipStream_t st) {
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv1x1_inject_kernel<bf16, KC, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "conv1x1_inject: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  if (int rc = lds_optin<conv1x1_inject_kernel<bf16, KC, NB>>("conv1x1_inject", 80 * 1024)) return rc;
   conv1x1_inject_kernel<bf16, KC, NB><<<std::min(a.N * a.tiles_x * a.tiles_y, 512), INJ_THREADS, lds, st>>>(a);   // persistent: 2 per CU
   MGDT_CHECK_LAUNCH("conv1x1_inject_fwd");
   return MGDT_OK;
@@ -474,18 +469,19 @@ extern "C" int mgdt_conv1x1_inject_fwd(const mgdt_view* x, const void* packed_w,
   if (!view_ok(x) || !view_ok(ga) || !view_ok(gf) || !view_ok(y) || !packed_w || !bias) MGDT_FAIL(MGDT_BAD_ARG, "conv1x1_inject: null/empty argument");
   if (!mgdt_conv1x1_inject_supported(x->c, y->c, y->h, y->w, ga->h, ga->w, dtype))
     MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject: shapes/dtype not covered (see mgdt_conv1x1_inject_supported)");
-  const long sz = 2;
+  const int sz = 2;
   if (x->n != y->n || x->h != y->h || x->w != y->w || ga->n != y->n || gf->n != y->n || ga->c != y->c || gf->c != y->c || ga->h != gf->h || ga->w != gf->w ||
       ga->sn != gf->sn || ga->sh != gf->sh || ga->sw != gf->sw)
     MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject: x/y spatial sizes, ga/gf shapes and layouts must match");
-  auto ok = [&](const mgdt_view* v, int q) { return v->sc == 1 && v->sw % q == 0 && v->sh % q == 0 && v->sn % q == 0 && (uintptr_t)v->p % (q * sz) == 0; };
-  auto ext = [&](const mgdt_view* v) { return ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz; };
-  if (!ok(x, 8) || !ok(ga, 8) || !ok(gf, 8) || !ok(y, 4) || ext(x) >= 0x7fffffffL || ext(y) >= 0x7fffffffL)
-    MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject: views must be aligned NHWC (sc == 1) and < 2 GiB");
   InjArgs a;
   memset(&a, 0, sizeof(a));
-  a.x = (const char*)x->p; a.xsn = (int)(x->sn * sz); a.xsh = (int)(x->sh * sz); a.xsw = (int)(x->sw * sz); a.x_bytes = (uint32_t)ext(x);
-  a.y = (char*)y->p; a.ysn = (int)(y->sn * sz); a.ysh = (int)(y->sh * sz); a.ysw = (int)(y->sw * sz); a.y_bytes = (uint32_t)ext(y);
+  const char* yp = nullptr;
+  // x and y go through buffer descriptors; ga / gf are plain pointers with int strides: aligned NHWC, their extent is not tested
+  auto nhwc8 = [&](const mgdt_view* v) { return v->sc == 1 && view_aligned(v, 8, sz); };
+  if (!nhwc8(ga) || !nhwc8(gf) || !bind_view(x, sz, {8, true, 0, 0, false}, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) ||
+      !bind_view(y, sz, {4, true, 0, 0, false}, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject: views must be aligned NHWC (sc == 1) and < 2 GiB");
+  a.y = (char*)yp;
   a.ga = (const char*)ga->p; a.gf = (const char*)gf->p; a.gsn = (int)(ga->sn * sz); a.gsh = (int)(ga->sh * sz); a.gsw = (int)(ga->sw * sz);
   a.wpk = (const char*)packed_w; a.bias = bias;
   a.N = y->n; a.H = y->h; a.W = y->w; a.Cin = x->c; a.Cout = y->c; a.Hg = ga->h; a.Wg = ga->w;
@@ -533,12 +529,7 @@ extern "C" int mgdt_conv1x1_inject_conv_supported(int cin, int cmid, int cout2, 
 
 template <int KC, int NB2, bool GCONV>
 static int inj2_launch(const InjConvArgs& A, size_t lds, hipStream_t st) {
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv1x1_inject_conv_kernel<KC, 16, NB2, INJ2_TH, GCONV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "conv1x1_inject_conv: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  if (int rc = lds_optin<conv1x1_inject_conv_kernel<KC, 16, NB2, INJ2_TH, GCONV>>("conv1x1_inject_conv")) return rc;
   conv1x1_inject_conv_kernel<KC, 16, NB2, INJ2_TH, GCONV><<<std::min(A.a.N * A.a.tiles_x * A.a.tiles_y, 256), 64 * INJ2_TH, lds, st>>>(A);   // persistent: one per CU
   MGDT_CHECK_LAUNCH("conv1x1_inject_conv_fwd");
   return MGDT_OK;
@@ -562,24 +553,22 @@ extern "C" int mgdt_conv1x1_inject_conv_fwd(const mgdt_view* x, const void* pack
   if (!view_ok(x) || !view_ok(y2) || !packed_w || !bias || !packed_w2 || !bias2) MGDT_FAIL(MGDT_BAD_ARG, "conv1x1_inject_conv: null/empty argument");
   if (!mgdt_conv1x1_inject_conv_supported(x->c, ga->c, y2->c, x->h, x->w, ga->h, ga->w, dtype))
     MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject_conv: shapes/dtype not covered (see mgdt_conv1x1_inject_conv_supported)");
-  const long sz = 2;
+  const int sz = 2;
   if (x->n != y2->n || x->h != y2->h || x->w != y2->w || ga->n != x->n || gf->n != x->n || gf->c != ga->c || ga->h != gf->h || ga->w != gf->w ||
       ga->sn != gf->sn || ga->sh != gf->sh || ga->sw != gf->sw)
     MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject_conv: x/y2 spatial sizes, ga/gf shapes and layouts must match");
-  auto ok = [&](const mgdt_view* v, int q) { return v->sc == 1 && v->sw % q == 0 && v->sh % q == 0 && v->sn % q == 0 && (uintptr_t)v->p % (q * sz) == 0; };
-  auto ext = [&](const mgdt_view* v) { return ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz; };
-  if (!ok(x, 8) || (!gconv && (!ok(ga, 8) || !ok(gf, 8))) || (gconv && (!ok(gsrc, 8) || ((long)(gsrc->n - 1) * gsrc->sn + (long)(gsrc->h - 1) * gsrc->sh + (long)(gsrc->w - 1) * gsrc->sw + gsrc->c) * sz >= 0x7fffffffL)) ||
-      !ok(y2, 4) || ext(x) >= 0x7fffffffL || ext(y2) >= 0x7fffffffL)
-    MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject_conv: views must be aligned NHWC (sc == 1) and < 2 GiB");
   InjConvArgs A;
   memset(&A, 0, sizeof(A));
   InjArgs& a = A.a;
-  if (gconv) {
-    A.gx = (const char*)gsrc->p; A.gxsn = (int)(gsrc->sn * sz); A.gxsh = (int)(gsrc->sh * sz); A.gxsw = (int)(gsrc->sw * sz);
-    A.gx_bytes = (uint32_t)(((long)(gsrc->n - 1) * gsrc->sn + (long)(gsrc->h - 1) * gsrc->sh + (long)(gsrc->w - 1) * gsrc->sw + gsrc->c) * sz);
-    A.wg = (const char*)packed_wg; A.bias_g = bias_g;
-  }
-  a.x = (const char*)x->p; a.xsn = (int)(x->sn * sz); a.xsh = (int)(x->sh * sz); a.xsw = (int)(x->sw * sz); a.x_bytes = (uint32_t)ext(x);
+  const ViewPolicy in16 = {8, true, 0, 0, false}, out8 = {4, true, 0, 0, false};
+  const char* y2p = nullptr;
+  // x, y2 and gsrc go through buffer descriptors; ga / gf are plain pointers with int strides: aligned NHWC, their extent is not tested
+  auto nhwc8 = [&](const mgdt_view* v) { return v->sc == 1 && view_aligned(v, 8, sz); };
+  if ((gconv ? !bind_view(gsrc, sz, in16, &A.gx, &A.gxsn, &A.gxsh, &A.gxsw, &A.gx_bytes) : !nhwc8(ga) || !nhwc8(gf)) ||
+      !bind_view(x, sz, in16, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(y2, sz, out8, &y2p, &A.y2sn, &A.y2sh, &A.y2sw, &A.y2_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "conv1x1_inject_conv: views must be aligned NHWC (sc == 1) and < 2 GiB");
+  A.y2 = (char*)y2p;
+  if (gconv) { A.wg = (const char*)packed_wg; A.bias_g = bias_g; }
   a.ga = (const char*)ga->p; a.gf = (const char*)gf->p; a.gsn = (int)(ga->sn * sz); a.gsh = (int)(ga->sh * sz); a.gsw = (int)(ga->sw * sz);
   a.wpk = (const char*)packed_w; a.bias = bias;
   a.N = x->n; a.H = x->h; a.W = x->w; a.Cin = x->c; a.Cout = ga->c; a.Hg = ga->h; a.Wg = ga->w;
@@ -588,7 +577,6 @@ extern "C" int mgdt_conv1x1_inject_conv_fwd(const mgdt_view* x, const void* pack
   a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_ty = make_fastdiv((uint32_t)a.tiles_y);
   a.ry = (float)a.Hg / (float)a.H; a.rx = (float)a.Wg / (float)a.W;
   A.w2 = (const char*)packed_w2; A.bias2 = bias2; A.act2 = act2; A.C2 = y2->c;
-  A.y2 = (char*)y2->p; A.y2sn = (int)(y2->sn * sz); A.y2sh = (int)(y2->sh * sz); A.y2sw = (int)(y2->sw * sz); A.y2_bytes = (uint32_t)ext(y2);
   const int kc = inj_kc(a.Cin), nb2 = cdiv(y2->c, 16);
   const size_t lds = inj2_lds(kc, 16, nb2, a.PH, a.PW);
   hipStream_t st = (hipStream_t)s;

@@ -312,6 +312,8 @@ extern "C" size_t mgdt_cnx_mlp_workspace_bytes(int n, int h, int w, int c) {
   return (size_t)n * mlp_splits(n, h * w) * 4 * c * sizeof(float);
 }
 
+static StampBuf mlp_stamps;
+
 template <int KC1>
 static int mlp_launch(MlpArgs& a, const float* gamma, const float* beta, float* ws, hipStream_t st) {
   constexpr int MT = MLP_MT, HD = 128 * KC1;
@@ -319,29 +321,22 @@ static int mlp_launch(MlpArgs& a, const float* gamma, const float* beta, float* 
   const size_t w1b = mlp_w1_bytes(KC1), w2b = mlp_w2_bytes(KC1);
   const size_t lds_b = (size_t)(HD + 2 * KC1 * 16 + 4) * sizeof(float);
   const size_t lds_s = w1b + (size_t)(MLP_THREADS / 64) * HD * sizeof(float) + lds_b, lds_a = w1b + w2b + (size_t)2 * HD * sizeof(float) + lds_b;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    for (const void* k : {(const void*)cnx_mlp_kernel<bf16, KC1, MT, true>, (const void*)cnx_mlp_kernel<bf16, KC1, MT, false>}) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "cnx_mlp: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    attr_set = true;
-  }
+  if (int rc = lds_optin<cnx_mlp_kernel<bf16, KC1, MT, true>, cnx_mlp_kernel<bf16, KC1, MT, false>>("cnx_mlp")) return rc;
   a.ws = ws;
-  static unsigned long long* dbg_buf = nullptr;
-  if (getenv("MGDT_MLP_DBG") && !dbg_buf) (void)hipMalloc((void**)&dbg_buf, 2048 * 32);
-  a.dbg = dbg_buf;
+  // MGDT_MLP_DBG: 4 words per workgroup, the stats pass from word 0, the apply pass from word 4096
+  const int nwg = splits * a.N;
+  const size_t stamp_words = (size_t)(1024 + nwg) * 4;
+  const bool dbg = knob_set("MGDT_MLP_DBG");
+  if (dbg && !mlp_stamps.ensure(stamp_words)) MGDT_FAIL(MGDT_WORKSPACE, "cnx_mlp: no memory for the MGDT_MLP_DBG stamps");
+  a.dbg = dbg ? mlp_stamps.p : nullptr;
   cnx_mlp_kernel<bf16, KC1, MT, true><<<dim3(splits, a.N), MLP_THREADS, lds_s, st>>>(a);
   a.gamma = gamma; a.shift = beta;
   cnx_mlp_kernel<bf16, KC1, MT, false><<<dim3(splits, a.N), MLP_THREADS, lds_a, st>>>(a);
   MGDT_CHECK_LAUNCH("cnx_mlp_fwd");
-  if (dbg_buf) {
-    static unsigned long long h[2048 * 4];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost);
-    const int nwg = splits * a.N;
+  if (dbg) {
+    const std::vector<unsigned long long> h = mlp_stamps.read(stamp_words, st);
     for (int pass = 0; pass < 2; ++pass) {
-      const unsigned long long* q = h + pass * 4096;
+      const unsigned long long* q = h.data() + pass * 4096;
       unsigned long long t0 = ~0ull, t3 = 0, s0max = 0; double st_sum = 0, lp_sum = 0, st_max = 0, lp_max = 0;
       for (int i = 0; i < nwg && i < 1024; ++i) {
         t0 = std::min(t0, q[i * 4]); t3 = std::max(t3, q[i * 4 + 3]); s0max = std::max(s0max, q[i * 4]);
@@ -360,24 +355,16 @@ extern "C" int mgdt_cnx_mlp_fwd(const mgdt_view* t, const mgdt_view* res, const 
   if (!view_ok(t) || !view_ok(y) || !packed || !gamma || !beta || !ws) MGDT_FAIL(MGDT_BAD_ARG, "cnx_mlp: null/empty argument");
   const int kc1 = mlp_kc1(t->c, dtype);
   if (!kc1) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_mlp: c=%d dtype=%d not covered (bf16, c in {32, 64, 96})", t->c, dtype);
-  const long sz = (long)dtype_size(dtype);
+  const int sz = (int)dtype_size(dtype);
   auto same = [&](const mgdt_view* v) { return v->n == t->n && v->h == t->h && v->w == t->w && v->c == t->c; };
   if (!same(y) || (res && res->p && !same(res))) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_mlp: t, res and y must have one shape");
   MlpArgs a;
   memset(&a, 0, sizeof(a));
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes, int q) {
-    if (!v || !v->p) return;
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz;
-    if (v->sc != 1 || v->sw % q || v->sh % q || v->sn % q || (uintptr_t)v->p % (q * sz) || ext >= 0x7fffffffL || v->sh * sz >= (1L << 23) ||
-        v->sw * sz >= (1L << 23)) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * sz); *sh = (int)(v->sh * sz); *sw = (int)(v->sw * sz); *bytes = (uint32_t)ext;
-  };
+  const ViewPolicy in8 = {8, true, 1L << 23, 1L << 23, true}, io4 = {4, true, 1L << 23, 1L << 23, true};      // res may be absent
   const char* yp = nullptr;
-  bind(t, &a.t, &a.tsn, &a.tsh, &a.tsw, &a.t_bytes, 8);
-  bind(res, &a.res, &a.rsn, &a.rsh, &a.rsw, &a.r_bytes, 4);
-  bind(y, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes, 4);
-  if (!fits) MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_mlp: views must be 16-byte aligned NHWC (sc == 1), < 2 GiB, row stride < 8 MiB");
+  if (!bind_view(t, sz, in8, &a.t, &a.tsn, &a.tsh, &a.tsw, &a.t_bytes) || !bind_view(res, sz, io4, &a.res, &a.rsn, &a.rsh, &a.rsw, &a.r_bytes) ||
+      !bind_view(y, sz, io4, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "cnx_mlp: views must be 16-byte aligned NHWC (sc == 1), < 2 GiB, row stride < 8 MiB");
   a.y = (char*)yp;
   a.packed = (const char*)packed;
   a.N = t->n; a.H = t->h; a.W = t->w; a.C = t->c; a.HW = t->h * t->w;
@@ -552,20 +539,13 @@ extern "C" int mgdt_pw_chain3_fwd(const mgdt_view* x, const void* packed, int wd
   if (!nbk) MGDT_FAIL(MGDT_BAD_SHAPE, "pw_chain3: wd=%d dtype=%d not covered (bf16, wd %% 4 == 0, wd <= 64)", wd, dtype);
   if (x->c != 3 * wd || y->c != 3 * wd || x->n != y->n || x->h != y->h || x->w != y->w)
     MGDT_FAIL(MGDT_BAD_SHAPE, "pw_chain3: x and y must be N x H x W x 3*wd views");
-  const long sz = (long)dtype_size(dtype);
+  const int sz = (int)dtype_size(dtype);
   ChainArgs a;
   memset(&a, 0, sizeof(a));
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes) {
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz;
-    if (v->sc != 1 || v->sw % 4 || v->sh % 4 || v->sn % 4 || (uintptr_t)v->p % (4 * sz) || ext >= 0x7fffffffL || v->sh * sz >= (1L << 23) ||
-        v->sw * sz >= (1L << 23)) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * sz); *sh = (int)(v->sh * sz); *sw = (int)(v->sw * sz); *bytes = (uint32_t)ext;
-  };
+  const ViewPolicy pol = {4, true, 1L << 23, 1L << 23, false};
   const char* yp = nullptr;
-  bind(x, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes);
-  bind(y, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes);
-  if (!fits) MGDT_FAIL(MGDT_BAD_SHAPE, "pw_chain3: views must be 8-byte aligned NHWC (sc == 1), < 2 GiB, row stride < 8 MiB");
+  if (!bind_view(x, sz, pol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(y, sz, pol, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes))
+    MGDT_FAIL(MGDT_BAD_SHAPE, "pw_chain3: views must be 8-byte aligned NHWC (sc == 1), < 2 GiB, row stride < 8 MiB");
   a.y = (char*)yp;
   a.packed = (const char*)packed;
   const long M = (long)x->n * x->h * x->w;

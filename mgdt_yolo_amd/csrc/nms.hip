@@ -572,7 +572,7 @@ static int nms_run(const float* pred, int n, int nc, int nm, int a, float conf_t
   size_t lds = (size_t)NMS_LDS_KEYS * sizeof(u64) + (size_t)(5 * max_det + (max_det & 1)) * sizeof(float) + (size_t)max_det * sizeof(u64);   // keys | kept float4 + area | kept keys
   if (lds > 150 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "nms: max_det=%d too large for the LDS kept list", max_det);
   NmsArgs g;
-  g.dbg = getenv("MGDT_NMS_DBG") != nullptr;
+  g.dbg = knob_set("MGDT_NMS_DBG");      // read per call
   g.pred = pred; g.n = n; g.nc = nc; g.A = a; g.rows = 4 + nc + nm; g.nm = nm; g.conf = conf_thres; g.iou = iou_thres; g.classes = n_classes > 0 ? classes : nullptr;
   g.n_classes = n_classes; g.agnostic = agnostic; g.multi_label = multi_label; g.max_det = max_det; g.max_nms = max_nms;
   g.max_wh = max_wh; g.out = out; g.kept_anchor = kept_anchor; g.counts = counts; g.ws = (u64*)ws;
@@ -580,7 +580,8 @@ static int nms_run(const float* pred, int n, int nc, int nm, int a, float conf_t
   long cand = multi_label ? (long)a * nc : a;
   g.cap_pow2 = next_pow2((int)std::min<long>(cand, max_nms));
   g.ws_per_image = g.cap_pow2 + (multi_label ? 0 : a);
-  static size_t attr_lds = 0;   // static LDS (histogram) + dynamic must stay <= 160 KiB: ask for what is needed only
+  // not lds_optin: static LDS (histogram) + dynamic must stay <= 160 KiB, so this kernel asks for what is needed only and asks again when that grows
+  static size_t attr_lds = 0;
   if (lds > attr_lds) {
     hipError_t e = hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "nms: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));

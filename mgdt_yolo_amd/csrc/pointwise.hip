@@ -665,28 +665,27 @@ extern "C" int mgdt_spr_attn_scale_fwd(const float* pooled, int nsplit, int tile
     pl[i].y = p->p; pl[i].sn = p->sn; pl[i].sh = p->sh; pl[i].sw = p->sw; pl[i].F = x->h / p->h;
     pool8 = pool8 && vecN_ok(p, dtype, 8);
   }
-  static unsigned long long* dbgbuf = nullptr;      // MGDT_SPR_DBG: per workgroup {start, attention weights ready, end} in 10 ns ticks
-  if (getenv("MGDT_SPR_DBG") && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, 4096 * 8 * 8);
+  static StampBuf stamps;      // MGDT_SPR_DBG: 8 words per workgroup {start, attention weights ready, end} in 10 ns ticks
+  const bool dbg = knob_set("MGDT_SPR_DBG");
   int gK = 0;
   MGDT_DISPATCH_TV(dtype, vecN_ok(x, dtype, 8) && vecN_ok(y, dtype, 8) && pool8, {
     const long vecs = (long)x->h * x->w * (c / V);
-    static const long per_wg = getenv("MGDT_SPR_VECS") ? atol(getenv("MGDT_SPR_VECS")) : 2048;   // experiment knob: vectors per workgroup
+    const long per_wg = KNOB_ONCE(knob_long("MGDT_SPR_VECS", 2048));   // experiment knob: vectors per workgroup
     // every workgroup repeats the attention prologue (the reduction of the per-tile sums dominates it): ~12 workgroups per image measured best on all
     // four backbone levels (33.5 / 21.0 / 17.2 / 20.6 us vs 41.9 / 23.2 / 17.2 / 20.6 with up to 64)
-    static const long kmax = getenv("MGDT_SPR_KMAX") ? atol(getenv("MGDT_SPR_KMAX")) : 12;
+    const long kmax = KNOB_ONCE(knob_long("MGDT_SPR_KMAX", 12));
     const int K = (int)std::max<long>(1, std::min<long>(kmax, vecs / per_wg));
+    if (dbg && !stamps.ensure((size_t)K * x->n * 8)) MGDT_FAIL(MGDT_WORKSPACE, "spr_attn_scale: no memory for the MGDT_SPR_DBG stamps");
     spr_attn_scale_kernel<T, V><<<dim3(K, x->n), 256, lds, (hipStream_t)s>>>(pooled, fc1_w, fc1_b, fc2_w, fc2_b, c, groups, x->h, x->w, (const T*)x->p, x->sn,
                                                                               x->sh, x->sw, (T*)y->p, y->sn, y->sh, y->sw, make_fastdiv((uint32_t)(c / V)),
                                                                               make_fastdiv((uint32_t)x->w), nsplit, tiles_x, tiles_y, pl[0], pl[1],
                                                                               make_fastdiv((uint32_t)(tiles_x > 0 ? nsplit / (tiles_x * tiles_y) : 1)),
-                                                                              make_fastdiv((uint32_t)std::max(tiles_x, 1)), make_fastdiv((uint32_t)(5 * cw / 4)), fast, dbgbuf);
+                                                                              make_fastdiv((uint32_t)std::max(tiles_x, 1)), make_fastdiv((uint32_t)(5 * cw / 4)), fast, dbg ? stamps.p : nullptr);
     gK = K;
   });
   MGDT_CHECK_LAUNCH("spr_attn_scale_fwd");
-  if (dbgbuf && gK * x->n <= 4096) {
-    (void)hipStreamSynchronize((hipStream_t)s);
-    std::vector<unsigned long long> h((size_t)gK * x->n * 8);
-    (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
+  if (dbg) {
+    const std::vector<unsigned long long> h = stamps.read((size_t)gK * x->n * 8, (hipStream_t)s);
     unsigned long long t0 = ~0ull, t1 = 0; double ph[7] = {0, 0, 0, 0, 0, 0, 0};
     const int ns = fast ? 8 : 3;
     for (int i = 0; i < gK * x->n; ++i) { t0 = std::min(t0, h[i * 8]); t1 = std::max(t1, h[i * 8 + ns - 1]); for (int k = 0; k + 1 < ns; ++k) ph[k] += (double)(h[i * 8 + k + 1] - h[i * 8 + k]); }
@@ -867,7 +866,7 @@ extern "C" int mgdt_sppf_pool_fwd(const mgdt_view* x, const mgdt_view* y1, const
       MGDT_FAIL(MGDT_BAD_SHAPE, "sppf_pool: views must be matching NHWC, c%%4==0");
   {
     // two-phase form: LDS = rows + three row-maximum planes in the storage type
-    static const bool old_form = getenv("MGDT_SPPF_CHAINED") != nullptr;      // experiment knob: the chained three-pass kernel
+    const bool old_form = KNOB_ONCE(knob_set("MGDT_SPPF_CHAINED"));      // experiment knob: the chained three-pass kernel
     bool all8 = true;
     for (const mgdt_view* v : {x, y1, y2, y3}) all8 = all8 && vecN_ok(v, dtype, 8);
     const int V3 = (dtype == MGDT_BF16 && all8) ? 8 : 4;
@@ -1248,7 +1247,7 @@ static DwPlan dwconv7_ln_plan(int n, int h, int w, int c, int dtype) {
     const long nwg = (long)n * cdiv(h, ts) * cdiv(w, ts), per_cu = std::max<long>(1, std::min<long>(160 * 1024 / (long)(l + 256), 2048 / (ts * Qt)));
     return cdiv(nwg, 256 * per_cu) * ts * ts;
   };
-  static const int force_ts = getenv("MGDT_DW_TS") ? atoi(getenv("MGDT_DW_TS")) : 0;      // experiment knob: 8 or 10 picks between the two row kernels
+  const int force_ts = KNOB_ONCE(knob_int("MGDT_DW_TS", 0));      // experiment knob: 8 or 10 picks between the two row kernels
   const long c8 = cost_of(8), c10 = cost_of(10);
   const int ts = force_ts == 8 || force_ts == 10 ? force_ts : (c10 >= 0 && (c8 < 0 || c10 < c8) ? 10 : 8);
   if (Qt <= 32 && (ts == 8 ? c8 : c10) >= 0)
@@ -1287,31 +1286,26 @@ static int dwconv7_ln_impl(const mgdt_view* x, const float* dw_w, const float* d
   if (pl.family != MGDT_DW_GENERIC) {   // row kernel: one thread per (channel quad, tile row)
     const int Qt = x->c / 4, ts = pl.ts, tiles = cdiv(x->h, ts) * cdiv(x->w, ts);
     const size_t lds_t = (size_t)pl.lds;
-    static unsigned long long* dbgbuf = nullptr;
-    if (getenv("MGDT_DW_DBG") && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, (size_t)x->n * tiles * 6 * 8);
-    static std::atomic<bool> attr10_f32{false}, attr10_bf16{false};
+    static StampBuf stamps;      // MGDT_DW_DBG: 6 words per workgroup
+    const int nwg = x->n * tiles;
+    const bool dbg = knob_set("MGDT_DW_DBG");
+    if (dbg && !stamps.ensure((size_t)nwg * 6)) MGDT_FAIL(MGDT_WORKSPACE, "dwconv7_ln: no memory for the MGDT_DW_DBG stamps");
+    unsigned long long* const dbgbuf = dbg ? stamps.p : nullptr;
     if (ts == 10) {
       MGDT_DISPATCH_DTYPE(dtype, {
-        std::atomic<bool>& fl = sizeof(T) == 2 ? attr10_bf16 : attr10_f32;
-        if (!fl.load()) {
-          (void)hipFuncSetAttribute((const void*)dwconv7_ln_row_kernel<T, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-          fl.store(true);
-        }
-        dwconv7_ln_row_kernel<T, 10><<<x->n * tiles, 10 * Qt, lds_t, (hipStream_t)s>>>(
+        if (int rc = lds_optin<dwconv7_ln_row_kernel<T, 10>>("dwconv7_ln", 80 * 1024)) return rc;
+        dwconv7_ln_row_kernel<T, 10><<<nwg, 10 * Qt, lds_t, (hipStream_t)s>>>(
             (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c,
             u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0, dbgbuf);
       });
     } else {
-      MGDT_DISPATCH_DTYPE(dtype, (dwconv7_ln_row_kernel<T, 8><<<x->n * tiles, 8 * Qt, lds_t, (hipStream_t)s>>>(
+      MGDT_DISPATCH_DTYPE(dtype, (dwconv7_ln_row_kernel<T, 8><<<nwg, 8 * Qt, lds_t, (hipStream_t)s>>>(
                                      (const T*)x->p, x->sn, x->sh, x->sw, dw_w, dw_b, ln_w, ln_b, eps, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w, x->c,
                                      u ? (T*)u->p : nullptr, u ? u->sn : 0, u ? u->sh : 0, u ? u->sw : 0, dbgbuf)));
     }
     MGDT_CHECK_LAUNCH("dwconv7_ln_fwd(row)");
-    if (dbgbuf) {
-      const int nwg = x->n * tiles;
-      std::vector<unsigned long long> h((size_t)nwg * 6);
-      (void)hipStreamSynchronize((hipStream_t)s);
-      (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
+    if (dbg) {
+      const std::vector<unsigned long long> h = stamps.read((size_t)nwg * 6, (hipStream_t)s);
       unsigned long long t0 = ~0ull, t5 = 0; double ph[5] = {0, 0, 0, 0, 0};
       for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, h[i * 6]); t5 = std::max(t5, h[i * 6 + 5]); for (int j = 0; j < 5; ++j) ph[j] += (double)(h[i * 6 + j + 1] - h[i * 6 + j]); }
       fprintf(stderr, "dwconv row x10ns: span %llu; avg per WG: halo %.0f weights+sync %.0f taps %.0f layernorm %.0f store %.0f\n", t5 - t0, ph[0] / nwg, ph[1] / nwg,
@@ -1519,16 +1513,8 @@ static int detect_decode_launch(const mgdt_view* feat, int reg_max, int nc, floa
   const int no = feat->c;
   size_t lds = (size_t)DEC_A * (no + 1) * sizeof(float);
   if (vec4_ok(feat, dtype) && lds <= 144 * 1024) {
-    if (lds > 64 * 1024) {      // reg_max = 16 heads (TOODHead): the transposed tile needs more than the default dynamic LDS limit
-      static std::atomic<bool> attr_set{false};
-      if (!attr_set) {
-        for (const void* k : {(const void*)detect_decode_tile_kernel<float>, (const void*)detect_decode_tile_kernel<bf16>}) {
-          hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-          if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "detect_decode: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-        attr_set = true;
-      }
-    }
+    if (lds > 64 * 1024)      // reg_max = 16 heads (TOODHead): the transposed tile needs more than the default dynamic LDS limit
+      if (int rc = lds_optin<detect_decode_tile_kernel<float>, detect_decode_tile_kernel<bf16>>("detect_decode", 144 * 1024)) return rc;
     dim3 grid(cdiv((long)feat->h * feat->w, DEC_A), feat->n);
     MGDT_DISPATCH_DTYPE(dtype, (detect_decode_tile_kernel<T><<<grid, 256, lds, (hipStream_t)s>>>((const T*)feat->p, feat->sn, feat->sh, feat->sw, feat->h, feat->w,
                                                                                                  reg_max, nc, stride, a_off, a_total, y, aug)));

@@ -333,8 +333,7 @@ extern "C" int mgdt_stem2_geometry(int n, int h, int w, int cu_count, int* out) 
   const int H0 = (h - 1) / 2 + 1, W0 = (w - 1) / 2 + 1, H1 = (H0 - 1) / 2 + 1, W1 = (W0 - 1) / 2 + 1;
   const long tiles = (long)n * cdiv(W1, ST_TW) * cdiv(H1, ST_TH);
   if (tiles >= 0x7fffffffL) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2_geometry: too many tiles");
-  const char* e = getenv("MGDT_STEM_WGS");
-  out[0] = (int)tiles; out[1] = stem2_grid((int)tiles, cu_count, e ? atoi(e) : 0); out[2] = ST_LDS_BYTES; out[3] = ST_WGS_PER_CU; out[4] = cu_count;
+  out[0] = (int)tiles; out[1] = stem2_grid((int)tiles, cu_count, knob_stem_wgs()); out[2] = ST_LDS_BYTES; out[3] = ST_WGS_PER_CU; out[4] = cu_count;
   return MGDT_OK;
 }
 
@@ -342,13 +341,14 @@ extern "C" int mgdt_stem2_geometry(int n, int h, int w, int cu_count, int* out) 
 // decomposition and the loader.  Pointers are tested for alignment only.
 static int stem2_plan(const mgdt_view* x, int x_dtype, const mgdt_view* y, StemArgs& a) {
   memset(&a, 0, sizeof(a));
-  if (x->c != 3 || y->c != 32 || y->sc != 1 || y->sw % 4 || y->sh % 4 || y->sn % 4 || (uintptr_t)y->p % 8) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: x must have 3 channels, y 32 (NHWC, 8-byte aligned)");
+  if (x->c != 3 || y->c != 32 || y->sc != 1 || !view_aligned(y, 4, 2)) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: x must have 3 channels, y 32 (NHWC, 8-byte aligned)");
   const int H0 = (x->h - 1) / 2 + 1, W0 = (x->w - 1) / 2 + 1, H1 = (H0 - 1) / 2 + 1, W1 = (W0 - 1) / 2 + 1;
   if (y->n != x->n || y->h != H1 || y->w != W1) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: y is %dx%dx%d, expected %dx%dx%d", y->n, y->h, y->w, x->n, H1, W1);
-  const long yext = ((long)(y->n - 1) * y->sn + (long)(y->h - 1) * y->sh + (long)(y->w - 1) * y->sw + y->c) * 2;
-  if (yext >= 0x7fffffffL) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: y spans >= 2 GiB");
+  // NHWC and 8-byte pieces were tested above (their own message), so only the extent can refuse here; a route query's pointer is only tested for alignment
+  const char* yp = nullptr;
+  if (!bind_view(y, 2, {4, true, 0, 0, true}, &yp, &a.ysn, &a.ysh, &a.ysw, &a.y_bytes)) MGDT_FAIL(MGDT_BAD_SHAPE, "stem2: y spans >= 2 GiB");
   a.x = x->p; a.xsn = x->sn; a.xsc = x->sc; a.xsh = x->sh; a.xsw = x->sw;
-  a.y = (char*)y->p; a.ysn = (int)(y->sn * 2); a.ysh = (int)(y->sh * 2); a.ysw = (int)(y->sw * 2); a.y_bytes = (uint32_t)yext;
+  a.y = (char*)yp;
   a.N = x->n; a.H = x->h; a.W = x->w; a.H0 = H0; a.W0 = W0; a.H1 = H1; a.W1 = W1;
   a.tiles_x = cdiv(W1, ST_TW); a.tiles_y = cdiv(H1, ST_TH);
   a.total = a.N * a.tiles_x * a.tiles_y;
@@ -359,8 +359,7 @@ static int stem2_plan(const mgdt_view* x, int x_dtype, const mgdt_view* y, StemA
 
 // the persistent grid and the XCD ranges of a plan on a device with `cus` compute units
 static int stem2_plan_grid(StemArgs& a, int cus) {
-  const char* e = getenv("MGDT_STEM_WGS");           // experiment knob: cap on the grid (not part of the ABI)
-  const int grid = stem2_grid(a.total, cus, e ? atoi(e) : 0);
+  const int grid = stem2_grid(a.total, cus, knob_stem_wgs());           // experiment knob, read per call: cap on the grid (not part of the ABI)
   a.per_xcd = cdiv(a.total, std::min(grid, 8));
   return grid;
 }
@@ -391,17 +390,11 @@ extern "C" int mgdt_stem2_fwd(const mgdt_view* x, int x_dtype, const void* packe
   if (cus <= 0) MGDT_FAIL(MGDT_LAUNCH_FAIL, "stem2: cannot read the device's compute-unit count");
   const int grid = stem2_plan_grid(a, cus);
   hipStream_t st = (hipStream_t)s;
-  static unsigned long long* dbgbuf = nullptr;            // MGDT_STEM_DBG=1: per-workgroup phase sums, printed after the launch (debug only)
-  static size_t dbgcap = 0;
-  const bool dbg = getenv("MGDT_STEM_DBG") != nullptr;
-  if (dbg && dbgcap < (size_t)grid * 8) {
-    if (dbgbuf) (void)hipFree(dbgbuf);
-    dbgcap = (size_t)grid * 8;
-    (void)hipMalloc((void**)&dbgbuf, dbgcap * 8);
-  }
-  a.dbg = dbg ? dbgbuf : nullptr;
-  if (dbg && !dbgbuf) MGDT_FAIL(MGDT_WORKSPACE, "stem2: no memory for the MGDT_STEM_DBG stamps");
-  if (dbg) (void)hipMemsetAsync(dbgbuf, 0, (size_t)grid * 64, st);        // a workgroup whose XCD range is empty writes nothing
+  static StampBuf stamps;            // MGDT_STEM_DBG=1: per-workgroup phase sums, printed after the launch (debug only)
+  const bool dbg = knob_set("MGDT_STEM_DBG");
+  if (dbg && !stamps.ensure((size_t)grid * 8)) MGDT_FAIL(MGDT_WORKSPACE, "stem2: no memory for the MGDT_STEM_DBG stamps");
+  a.dbg = dbg ? stamps.p : nullptr;
+  if (dbg) stamps.zero((size_t)grid * 8, st);        // a workgroup whose XCD range is empty writes nothing
 #define STEM_LAUNCH(TXV)                                                      \
   do {                                                                        \
     if (dbg) stem2_kernel<TXV, true><<<grid, 256, 0, st>>>(a);                \
@@ -413,9 +406,7 @@ extern "C" int mgdt_stem2_fwd(const mgdt_view* x, int x_dtype, const void* packe
 #undef STEM_LAUNCH
   MGDT_CHECK_LAUNCH("stem2_fwd");
   if (dbg) {
-    std::vector<unsigned long long> h((size_t)grid * 8);
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost);
+    const std::vector<unsigned long long> h = stamps.read((size_t)grid * 8, st);
     double ph[7] = {0, 0, 0, 0, 0, 0, 0}, nt = 0, nw = 0;
     unsigned long long mx = 0;
     for (int i = 0; i < grid; ++i) {

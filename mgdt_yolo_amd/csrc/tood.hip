@@ -135,13 +135,14 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restri
   }
 }
 
-// launches gn_finalize_kernel; C > 4064 needs more than 64 KiB of dynamic LDS (the opt-in is idempotent, same value from every caller)
-static bool gn_finalize(const double* partial, const float* gamma, const float* beta, int n, int C, int G, double count, float eps, float* AB, float* A, float* B,
+// launches gn_finalize_kernel; C > 4064 needs more than 64 KiB of dynamic LDS
+static int gn_finalize(const char* who, const double* partial, const float* gamma, const float* beta, int n, int C, int G, double count, float eps, float* AB, float* A, float* B,
                         float* mean, float* rstd, double* stats, hipStream_t st) {
   const size_t lds = (size_t)(2 * C + 2 * G) * sizeof(double);
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)gn_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+  if (lds > 64 * 1024)
+    if (int rc = lds_optin<gn_finalize_kernel>(who)) return rc;
   gn_finalize_kernel<<<n, 256, lds, st>>>(partial, gamma, beta, C, G, count, eps, AB, A, B, mean, rstd, stats);
-  return true;
+  return MGDT_OK;
 }
 
 template <typename T>
@@ -173,8 +174,7 @@ extern "C" int mgdt_groupnorm_fwd(const mgdt_view* x, const float* gamma, const 
   float* AB = (float*)((char*)ws + mgdt_gn_partial_bytes(x->n, x->c));
   const int Q = x->c / 4;
   if (!mgdt_gn_partial_sums(x, nullptr, partial, dtype, st)) MGDT_FAIL(MGDT_BAD_SHAPE, "groupnorm: 4-aligned NHWC view, c <= 4096, h*w < 2^31 - 2^16");
-  if (!gn_finalize(partial, gamma, beta, x->n, x->c, groups, (double)x->h * x->w, eps, AB, nullptr, nullptr, nullptr, nullptr, nullptr, st))
-    MGDT_FAIL(MGDT_LAUNCH_FAIL, "groupnorm: hipFuncSetAttribute");
+  if (int rc = gn_finalize("groupnorm", partial, gamma, beta, x->n, x->c, groups, (double)x->h * x->w, eps, AB, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return rc;
   const long total = (long)x->n * x->h * x->w * Q;
   const int grid = (int)std::min<long>((total + 255) / 256, 8192);
   MGDT_DISPATCH_DTYPE(dtype, (gn_apply_kernel<T><<<grid, 256, 0, st>>>((const T*)x->p, x->sn, x->sh, x->sw, AB, act, (T*)y->p, y->sn, y->sh, y->sw, x->h, x->w,
@@ -194,8 +194,7 @@ extern "C" int mgdt_gn_affine(const mgdt_view* y, const float* gamma, const floa
   double* partial = (double*)ws;
   double* stats = (double*)((char*)ws + mgdt_gn_partial_bytes(y->n, y->c));
   if (!mgdt_gn_partial_sums(y, nullptr, partial, dtype, st)) MGDT_FAIL(MGDT_BAD_SHAPE, "gn_affine: 4-aligned NHWC view, c <= 4096");
-  if (!gn_finalize(partial, gamma, beta, y->n, y->c, groups, (double)y->h * y->w, eps, nullptr, A, B, mean_ng, rstd_ng, stats, st))
-    MGDT_FAIL(MGDT_LAUNCH_FAIL, "gn_affine: hipFuncSetAttribute");
+  if (int rc = gn_finalize("gn_affine", partial, gamma, beta, y->n, y->c, groups, (double)y->h * y->w, eps, nullptr, A, B, mean_ng, rstd_ng, stats, st)) return rc;
   MGDT_CHECK_LAUNCH("gn_affine");
   return MGDT_OK;
 }
@@ -357,11 +356,8 @@ extern "C" int mgdt_dcnv2_mfma_fwd(const mgdt_view* x, const mgdt_view* offset_m
   const int grid = (int)std::min<long>(cdiv(M, 64), 2048);
   const size_t lds = (size_t)nchunks * NB * 1024;
   if (lds > 144 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "dcnv2_mfma: weight panel %zu B does not fit", lds);
-  if (lds > 64 * 1024) {      // 64 -> 64 channels (the scale-s head): 72 KiB of dynamic LDS needs the opt-in (idempotent, same value from every caller)
-    const void* ks[4] = {(const void*)dcnv2_mfma_kernel<1>, (const void*)dcnv2_mfma_kernel<2>, (const void*)dcnv2_mfma_kernel<3>, (const void*)dcnv2_mfma_kernel<4>};
-    hipError_t e = hipFuncSetAttribute(ks[NB > 4 ? 3 : NB - 1], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "dcnv2_mfma: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
+  if (lds > 64 * 1024)      // 64 -> 64 channels (the scale-s head): 72 KiB of dynamic LDS needs the opt-in
+    if (int rc = lds_optin<dcnv2_mfma_kernel<1>, dcnv2_mfma_kernel<2>, dcnv2_mfma_kernel<3>, dcnv2_mfma_kernel<4>>("dcnv2_mfma")) return rc;
 #define DCN_L(B) dcnv2_mfma_kernel<B><<<grid, 256, lds, (hipStream_t)s>>>((const bf16*)x->p, x->sn, x->sh, x->sw, (const bf16*)offset_mask->p, offset_mask->sn, \
                                                                          offset_mask->sh, offset_mask->sw, (const char*)packed_w, (bf16*)y->p, y->sn, y->sh, y->sw, \
                                                                          x->n, x->h, x->w, x->c, nchunks)
@@ -381,11 +377,8 @@ extern "C" int mgdt_dcnv2_fwd(const mgdt_view* x, const mgdt_view* offset_mask, 
   dim3 grid((unsigned)cdiv(M, 256), (unsigned)cdiv(y->c, 16));
   const size_t lds = (size_t)9 * x->c * 16 * sizeof(float);
   if (lds > 160 * 1024) MGDT_FAIL(MGDT_BAD_SHAPE, "dcnv2: weight tile %zu B (cin %d) does not fit the 160 KiB of LDS: cin <= 284", lds, x->c);
-  if (lds > 64 * 1024) {      // cin > 113: more dynamic LDS than a launch gets without the opt-in (idempotent, same value from every caller)
-    const void* k = dtype == MGDT_BF16 ? (const void*)dcnv2_kernel<bf16> : (const void*)dcnv2_kernel<float>;
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, "dcnv2: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
+  if (lds > 64 * 1024)      // cin > 113: more dynamic LDS than a launch gets without the opt-in
+    if (int rc = lds_optin<dcnv2_kernel<bf16>, dcnv2_kernel<float>>("dcnv2")) return rc;
   MGDT_DISPATCH_DTYPE(dtype, (dcnv2_kernel<T><<<grid, 256, lds, (hipStream_t)s>>>((const T*)x->p, x->sn, x->sh, x->sw, (const T*)offset_mask->p, offset_mask->sn,
                                                                                    offset_mask->sh, offset_mask->sw, w_gemm, bias, (T*)y->p, y->sn, y->sh, y->sw,
                                                                                    x->n, x->h, x->w, x->c, y->c)));

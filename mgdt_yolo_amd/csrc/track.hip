@@ -401,16 +401,6 @@ __global__ __launch_bounds__(TK_CAP) void bytetrack_export_kernel(char* __restri
 static size_t tk_update_lds(int cap) { return (size_t)TK_CAP * TK_LD * 4 + ((tk_state_bytes(cap) + 15) & ~(size_t)15) + TK_CAP * 8 + (TK_CAP + 4) * 4 + 10 * TK_CAP * 4 + TK_CAP * 4 + 3 * TK_CAP * 16; }
 static size_t tk_assign_lds() { return (size_t)TK_CAP * TK_LD * 4 + TK_CAP * 8 + (TK_CAP + 4) * 4 + 2 * TK_CAP * 4; }
 
-#define TK_BIG_LDS(kernel, what)                                                                                              \
-  do {                                                                                                                        \
-    static std::atomic<bool> attr{false};                                                                                     \
-    if (!attr) {                                                                                                              \
-      hipError_t e_ = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);       \
-      if (e_ != hipSuccess) MGDT_FAIL(MGDT_LAUNCH_FAIL, what ": hipFuncSetAttribute: %s", hipGetErrorString(e_));             \
-      attr = true;                                                                                                            \
-    }                                                                                                                         \
-  } while (0)
-
 extern "C" size_t mgdt_bytetrack_state_bytes(int streams, int cap) {
   if (streams < 1 || cap < 1 || cap > TK_CAP) return 0;
   return (size_t)streams * tk_state_bytes(cap);
@@ -432,7 +422,7 @@ extern "C" int mgdt_bytetrack_update(const float* rows, const int32_t* counts, c
   if (!rows || !counts || !state || !tracks || !ntracks || !flags) MGDT_FAIL(MGDT_BAD_ARG, "bytetrack_update: null pointer");
   if (streams < 1 || streams > 65535 || cap < 1 || cap > TK_CAP || max_det < 1 || max_det > (1 << 20))
     MGDT_FAIL(MGDT_BAD_SHAPE, "bytetrack_update: streams=%d (1..65535) cap=%d (1..%d) max_det=%d (1..2^20)", streams, cap, TK_CAP, max_det);
-  TK_BIG_LDS(bytetrack_update_kernel, "bytetrack_update");
+  if (int rc = lds_optin<bytetrack_update_kernel>("bytetrack_update")) return rc;
   bytetrack_update_kernel<<<streams, 64, tk_update_lds(cap), (hipStream_t)s>>>(rows, counts, active, (char*)state, cap, max_det,
                                                                                 TkCfg{track_high_thresh, track_low_thresh, new_track_thresh, match_thresh, max_time_lost},
                                                                                 tracks, ntracks, flags);
@@ -445,7 +435,7 @@ extern "C" int mgdt_track_assign(const float* cost, const int32_t* n, const int3
   if (!cost || !n || !m || !x) MGDT_FAIL(MGDT_BAD_ARG, "track_assign: null pointer");
   if (batch < 1 || batch > 65535 || n_max < 1 || n_max > TK_CAP || m_max < 1 || m_max > TK_CAP)
     MGDT_FAIL(MGDT_BAD_SHAPE, "track_assign: batch=%d (1..65535) n_max=%d m_max=%d (1..%d)", batch, n_max, m_max, TK_CAP);
-  TK_BIG_LDS(track_assign_kernel, "track_assign");
+  if (int rc = lds_optin<track_assign_kernel>("track_assign")) return rc;
   track_assign_kernel<<<batch, 64, tk_assign_lds(), (hipStream_t)s>>>(cost, n, m, n_max, m_max, thresh, x);
   MGDT_CHECK_LAUNCH("track_assign");
   return MGDT_OK;

@@ -334,12 +334,12 @@ bool mgdt_wgrad_mfma_launch(const mgdt_view* x, const mgdt_view* x2, const mgdt_
 int mgdt_wgrad_bf16_groups(int cin, int cout, int k);   // wgrad_bf16.hip
 static inline int wgrad_splits(int cin, int cout, int k) {
   const long nel = (long)cin * cout * k * k;
-  static const long cap = getenv("MGDT_WGRAD_SPLITS") ? atol(getenv("MGDT_WGRAD_SPLITS")) : 512;     // experiment knob
-  static const long budget = getenv("MGDT_WGRAD_PARTIAL_ELEMS") ? atol(getenv("MGDT_WGRAD_PARTIAL_ELEMS")) : (4L << 20);     // experiment knob
+  const long cap = KNOB_ONCE(knob_long("MGDT_WGRAD_SPLITS", 512));     // experiment knob
+  const long budget = KNOB_ONCE(knob_long("MGDT_WGRAD_PARTIAL_ELEMS", 4L << 20));     // experiment knob
   long ns = std::max<long>(WG_SPLITS, std::min<long>(cap, budget / std::max<long>(nel, 1)));
   // big channel tiles leave few (cout, cin) groups: up to twice the splits so that groups x splits reaches ~2 workgroups per CU (the 64->96 3x3 head
   // convolution ran 216 workgroups of 4 waves on 256 CUs)
-  static const long fill = getenv("MGDT_WGRAD_FILL") ? atol(getenv("MGDT_WGRAD_FILL")) : 448;     // experiment knob, 0 = off
+  const long fill = KNOB_ONCE(knob_long("MGDT_WGRAD_FILL", 448));     // experiment knob, 0 = off
   const int g = fill ? mgdt_wgrad_bf16_groups(cin, cout, k) : 0;
   if (g > 0 && g * ns < fill) ns = std::min<long>({cap, 2 * ns, (fill + g - 1) / g});
   return (int)ns;
@@ -493,8 +493,8 @@ extern "C" int mgdt_conv_wgrad(const mgdt_view* x, const mgdt_view* x2, const mg
   mgdt_view b = (x2 && x2->p) ? *x2 : null_view();
   const int nsplit = wgrad_splits(x->c, dy->c, k);
   if ((long)dy->n * dy->h * dy->w >= 0x7fffffffL) MGDT_FAIL(MGDT_BAD_SHAPE, "conv_wgrad: too many pixels");
-  static const bool no_mfma = getenv("MGDT_WGRAD_VALU") != nullptr;     // experiment knob: the VALU outer-product kernel
-  static const bool no_bf16 = getenv("MGDT_WGRAD_F32MFMA") != nullptr;   // experiment knob: fp32 MFMA for bf16 tensors too
+  const bool no_mfma = KNOB_ONCE(knob_set("MGDT_WGRAD_VALU"));     // experiment knob: the VALU outer-product kernel
+  const bool no_bf16 = KNOB_ONCE(knob_set("MGDT_WGRAD_F32MFMA"));   // experiment knob: fp32 MFMA for bf16 tensors too
   if (!no_mfma && !no_bf16 && dtype == MGDT_BF16 && mgdt_wgrad_bf16_launch(x, x2, dy, k, stride, (float*)ws, nsplit, st)) {
   } else if (no_mfma || !mgdt_wgrad_mfma_launch(x, x2, dy, k, stride, (float*)ws, nsplit, dtype, st)) {
     dim3 grid(cdiv(dy->c, 16), cdiv(x->c, 16), k * k * nsplit);

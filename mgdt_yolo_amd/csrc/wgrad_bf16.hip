@@ -248,20 +248,9 @@ bool mgdt_wgrad_bf16_launch(const mgdt_view* x, const mgdt_view* x2, const mgdt_
   if (x->c % 4 || dy->c % 8) return false;
   WbArgs a;
   memset(&a, 0, sizeof(a));
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes, int al) {
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * 2;
-    if (ext >= 0x7fffffffL || (uintptr_t)v->p % (2 * al) || v->sn % al || v->sh % al || v->sw % al) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * 2); *sh = (int)(v->sh * 2); *sw = (int)(v->sw * 2); *bytes = (uint32_t)ext;
-  };
-  const int xal = x->c % 8 ? 4 : 8;
-  bind(x, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes, xal);
-  if (x2 && x2->p) {
-    if (x2->sc != 1) return false;
-    bind(x2, &a.x2, &a.x2sn, &a.x2sh, &a.x2sw, &a.x2_bytes, xal);
-  }
-  bind(dy, &a.dy, &a.dsn, &a.dsh, &a.dsw, &a.dy_bytes, 8);
-  if (!fits) return false;
+  const ViewPolicy xpol = {x->c % 8 ? 4 : 8, false, 0, 0, false}, dpol = {8, false, 0, 0, false};      // sc == 1 is tested above and below
+  if (!bind_view(x, 2, xpol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(dy, 2, dpol, &a.dy, &a.dsn, &a.dsh, &a.dsw, &a.dy_bytes)) return false;
+  if (x2 && x2->p && (x2->sc != 1 || !bind_view(x2, 2, xpol, &a.x2, &a.x2sn, &a.x2sh, &a.x2sw, &a.x2_bytes))) return false;
   a.partial = partial;
   a.H = x->h; a.W = x->w; a.Cin = x->c; a.Ho = dy->h; a.Wo = dy->w; a.Cout = dy->c; a.KS = k; a.stride = stride; a.pad = k / 2; a.nsplit = nsplit;
   a.tiles_x = cdiv(a.Wo, 8);
@@ -290,7 +279,7 @@ bool mgdt_wgrad_bf16_launch(const mgdt_view* x, const mgdt_view* x2, const mgdt_
   a.fd_xitems = make_fastdiv((uint32_t)(a.XTH * a.XTW * a.ci8)); a.fd_ditems = make_fastdiv((uint32_t)(64 * a.co8));
   const size_t lds = std::max(per_tile * a.NTS, (size_t)(cfg.WK > 1 ? 4 : 0) * cfg.AT * cfg.NCW * 1024);
   dim3 grid(ncog * a.ncig, nsplit);
-  static const bool dbg = getenv("MGDT_WGRAD_DBG") != nullptr;
+  const bool dbg = KNOB_ONCE(knob_set("MGDT_WGRAD_DBG"));
   if (dbg) fprintf(stderr, "wgrad_bf16 cin %d cout %d k %d s %d %dx%d: AT %d NCW %d WA %d WB %d WK %d BT %d NTS %d grid %d x %d lds %zu\n", a.Cin, a.Cout, k, stride, a.Ho, a.Wo, cfg.AT, cfg.NCW, cfg.WA, cfg.WB, cfg.WK, cfg.BT, a.NTS, ncog * a.ncig, nsplit, lds);
 #define WB_CASE(at, ncw) if (cfg.AT == at && cfg.NCW == ncw) { wb_launch<at, ncw>(a, grid, lds, st); return true; }
   WB_CASE(1, 1) WB_CASE(1, 2) WB_CASE(1, 3) WB_CASE(1, 5) WB_CASE(1, 9) WB_CASE(1, 12)

@@ -150,20 +150,10 @@ bool mgdt_wgrad_mfma_launch(const mgdt_view* x, const mgdt_view* x2, const mgdt_
   if ((k != 1 && k != 3) || (stride != 1 && stride != 2) || x->sc != 1 || dy->sc != 1) return false;
   WgArgs a;
   memset(&a, 0, sizeof(a));
-  const long sz = (long)dtype_size(dtype);
-  bool fits = true;
-  auto bind = [&](const mgdt_view* v, const char** p, int* sn, int* sh, int* sw, uint32_t* bytes) {
-    const long ext = ((long)(v->n - 1) * v->sn + (long)(v->h - 1) * v->sh + (long)(v->w - 1) * v->sw + v->c) * sz;
-    if (ext >= 0x7fffffffL || v->sh * sz >= (1L << 28)) { fits = false; return; }
-    *p = (const char*)v->p; *sn = (int)(v->sn * sz); *sh = (int)(v->sh * sz); *sw = (int)(v->sw * sz); *bytes = (uint32_t)ext;
-  };
-  bind(x, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes);
-  if (x2 && x2->p) {
-    if (x2->sc != 1) return false;
-    bind(x2, &a.x2, &a.x2sn, &a.x2sh, &a.x2sw, &a.x2_bytes);
-  }
-  bind(dy, &a.dy, &a.dsn, &a.dsh, &a.dsw, &a.dy_bytes);
-  if (!fits) return false;
+  const int sz = (int)dtype_size(dtype);
+  const ViewPolicy pol = {0, false, 1L << 28, 0, false};      // element-wise loads; sc == 1 is tested above and below
+  if (!bind_view(x, sz, pol, &a.x, &a.xsn, &a.xsh, &a.xsw, &a.x_bytes) || !bind_view(dy, sz, pol, &a.dy, &a.dsn, &a.dsh, &a.dsw, &a.dy_bytes)) return false;
+  if (x2 && x2->p && (x2->sc != 1 || !bind_view(x2, sz, pol, &a.x2, &a.x2sn, &a.x2sh, &a.x2sw, &a.x2_bytes))) return false;
   a.partial = partial;
   a.N = x->n; a.H = x->h; a.W = x->w; a.Cin = x->c; a.Ho = dy->h; a.Wo = dy->w; a.Cout = dy->c; a.KS = k; a.stride = stride; a.pad = k / 2;
   a.nsplit = nsplit; a.M = dy->n * dy->h * dy->w; a.HoWo = dy->h * dy->w;

@@ -13,8 +13,6 @@ test_restatement_soundness shows for each restatement that its fp32 evaluation s
 accumulation order and the rare one-ulp flip of an intermediate do not break the bound by themselves.
 """
 import ctypes as C
-import os
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
@@ -22,6 +20,7 @@ import torch
 
 from kernel_ref import (BF16, DEV, F32, ConvP, _borders_untouched, _check, _gen, _nhwc, _out_buf, _rand, inj_bilinear, inj_lerp, ref_csp_block,
                         ref_detect_decode, ref_detect_map, ref_inject, ref_inject_conv, ref_pw_chain3)
+from knobs import forced_tile as _forced_tile
 
 gpu = pytest.mark.gpu
 F64 = torch.float64
@@ -137,21 +136,6 @@ def tail_lds(c3, nc):
 
 
 INJ_CAP, INJ2_CAP, TAIL_CAP_UNITS, CONV_CAP_ROWS = 512, 256, 1024 * 4, 256 * 256     # persistent grids: patches / patches / 32-anchor units / output rows
-
-
-@contextmanager
-def _forced_tile(tile):
-    old = os.environ.get('MGDT_CSP_TILE')
-    if tile:
-        os.environ['MGDT_CSP_TILE'] = f'{tile[0]},{tile[1]}'
-    try:
-        yield
-    finally:
-        if tile:
-            if old is None:
-                os.environ.pop('MGDT_CSP_TILE')
-            else:
-                os.environ['MGDT_CSP_TILE'] = old
 
 
 def _c_tiles(mode, B, cin, cout, wd, n, H, W, tile):

@@ -1,11 +1,11 @@
 """Tile geometry of the whole-block CSP kernel (mgdt_csp_block_fwd): LDS per workgroup at the bench shapes (host only), and the
 single launch against the per-conv launch chain at the bench shapes and at forced tiles of both residencies (GPU)."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
+from knobs import forced_tile
 from mgdt_yolo_amd import _lib
 from mgdt_yolo_amd.seeding import seed_state_dict_
 
@@ -21,17 +21,8 @@ def _tiles(mode, n, c, nbtl, hw, tile=None):
     wd = c // 4 if mode == 0 else c // 2
     cin = 4 * wd if mode == 0 else 2 * wd
     g = (C.c_int * 8)()
-    old = os.environ.get('MGDT_CSP_TILE')
-    if tile:
-        os.environ['MGDT_CSP_TILE'] = f'{tile[0]},{tile[1]}'
-    try:
+    with forced_tile(tile):
         slots = _lib.lib().mgdt_csp_block_tiles(mode, n, cin, c, wd, nbtl, hw, hw, g)
-    finally:
-        if tile:
-            if old is None:
-                os.environ.pop('MGDT_CSP_TILE')
-            else:
-                os.environ['MGDT_CSP_TILE'] = old
     return slots, list(g)
 
 
@@ -87,20 +78,11 @@ def _c2f(c1, c2, n, sc, hw, B, tile):
 
 
 def _fused_vs_chain(ops, m, x, supported, tile, what):
-    old = os.environ.get('MGDT_CSP_TILE')
-    if tile:
-        os.environ['MGDT_CSP_TILE'] = f'{tile[0]},{tile[1]}'
-    try:
+    with forced_tile(tile):
         assert supported()
         with torch.no_grad():
             y_fused = m(x).float()
             torch.cuda.synchronize()
-    finally:
-        if tile:
-            if old is None:
-                os.environ.pop('MGDT_CSP_TILE')
-            else:
-                os.environ['MGDT_CSP_TILE'] = old
     with torch.no_grad():
         ops.FUSED_CSP_BLOCK = False
         try:

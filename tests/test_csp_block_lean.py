@@ -4,34 +4,13 @@ The unpaired form stays reachable (MGDT_CSP_PAIR=0, read per call, so one proces
 the same points, so y and the pool sums are compared bit for bit, and the paired form is held to ref_csp_block under the bf16 bound of
 kernel_ref._close.
 """
-import os
-from contextlib import contextmanager
-
 import pytest
 import torch
 
 from kernel_ref import BF16, ConvP, _check, _gen, _nhwc, _rand, ref_csp_block
+from knobs import knobs as _env
 
 gpu = pytest.mark.gpu
-
-
-@contextmanager
-def _env(**kv):
-    """Set (value) or unset (None) environment variables for the calls inside; restored afterwards."""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _bits(t):

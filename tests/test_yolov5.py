@@ -744,9 +744,8 @@ def test_two_captured_training_steps_equal_two_eager_steps(amp):
 
 
 # ================================================================================================ the one-launch C3 route (mode CSP_C3 of mgdt_csp_block_fwd)
-import contextlib  # noqa: E402
-
 from c3_ref import ref_c3_block, ref_c3_front  # noqa: E402
+from knobs import forced_tile as _forced_tile  # noqa: E402
 
 # (id, wd, n, shortcut, B, H, W, forced tile or None, cout, channel offset of the input view, BN form)
 C3_KERNEL_CASES = [
@@ -757,18 +756,6 @@ C3_KERNEL_CASES = [
     ('wd64-n1-8x8-tile2x2', 64, 1, True, 1, 8, 8, (2, 2), 128, 0, False),
     ('wd64-n2-6x10-cout256-B3', 64, 2, True, 3, 6, 10, None, 256, 0, True),
 ]
-
-
-@contextlib.contextmanager
-def _forced_tile(tile):
-    old = os.environ.get('MGDT_CSP_TILE')
-    if tile:
-        os.environ['MGDT_CSP_TILE'] = f'{tile[0]},{tile[1]}'
-    try:
-        yield
-    finally:
-        if tile:
-            os.environ.pop('MGDT_CSP_TILE') if old is None else os.environ.__setitem__('MGDT_CSP_TILE', old)
 
 
 def _c3_kernel_inputs(cid, wd, n, B, H, W, cout, bn, wrep=BF16):
