@@ -243,6 +243,17 @@ int mgdt_conv1x1_inject_conv_fwd(const mgdt_view* x, const void* packed_w, const
                                  const mgdt_view* gsrc, const void* packed_wg, const float* bias_g, int cmid,
                                  const void* packed_w2, const float* bias2, int act2, const mgdt_view* y2, int dtype, mgdt_stream s);
 
+/* ---- SimFusion_3in / LAF with cv2 = cv3 = Identity in one launch, bf16 (nn/modules/block.py:309-329, eval):
+ *   y = act2(cv_fuse([act1(cv1(p0)) | x1 | bilinear(x2)]))        (align_corners=False, x2 resampled to x1's size whatever its own)
+ * p0 (N, h, w, c0): the avg-pooled first input; x1 (N, h, w, oc): the second input (in the model: channel slice [oc, 2 oc) of the concat buffer);
+ * x2 (N, h2, w2, oc); y (N, h, w, oc).  All NHWC views with any 16-byte aligned pixel / row strides.  packed_w1 / bias1 = mgdt_conv_pack(c0, oc, 1,
+ * bf16) of cv1, packed_w2 / bias2 = mgdt_conv_pack(3 * oc, oc, 1, bf16) of cv_fuse.  The values are those of mgdt_conv2d_fwd into concat slot 0,
+ * mgdt_bilinear_fwd into slot 2 and mgdt_conv2d_fwd over the buffer, bit for bit; slots 0 and 2 are never written.
+ * mgdt_laf_fuse_supported: bf16, c0 % 8 == 0 and <= 64, oc in {32, 64}, oc2 == oc, activations none / SiLU / ReLU. */
+int mgdt_laf_fuse_supported(int c0, int oc, int oc2, int h, int w, int h2, int w2, int act1, int act2, int dtype);
+int mgdt_laf_fuse_fwd(const mgdt_view* p0, const mgdt_view* x1, const mgdt_view* x2, const void* packed_w1, const float* bias1, int act1,
+                      const void* packed_w2, const float* bias2, int act2, const mgdt_view* y, int dtype, mgdt_stream s);
+
 /* ---- TOODHead (nn/modules/head.py:466-572; parity unpinned: mmcv's ModulatedDeformConv2d is not shipped with the reference) --------
  * GroupNorm + activation (Conv_GN head.py:67-81, DyDCNv2's norm block.py:427-431): y = act(group_norm(x, groups, gamma, beta, eps)).
  * ws: mgdt_groupnorm_workspace_bytes(n, c) bytes, 8-byte aligned (it holds the double partial sums; MGDT_BAD_ARG otherwise); x, y: 4-aligned NHWC views,

@@ -7,6 +7,7 @@
 
 #include <type_traits>
 #include "common.h"
+#include "resample.h"
 
 #define SPR_SPLITS 16
 
@@ -934,20 +935,8 @@ __global__ void avgpool_kernel(const T* __restrict__ x, long xsn, long xsh, long
     return MGDT_OK;                                                                                                                    \
   }
 
-// F.interpolate(bilinear, align_corners=False): src = max(0, (dst+0.5)*in/out - 0.5), upper neighbour clamped
-struct Lerp { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Lerp lerp_of(int o, int isz, int osz) {
-  float scale = (float)isz / (float)osz;
-  float src = scale * ((float)o + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  int i0 = (int)src;
-  if (i0 > isz - 1) i0 = isz - 1;
-  int i1 = i0 + (i0 < isz - 1 ? 1 : 0);
-  float l1 = src - (float)i0;
-  return Lerp{i0, i1, 1.f - l1, l1};
-}
-
-template <typename T, int V, bool HSIG>
+// Lerp / lerp_of / bilerp_mix / bilerp_mix_fma: resample.h.  FMA: the written-out form (the stand-alone bilinear kernel, which fused launches reproduce)
+template <typename T, int V, bool HSIG, bool FMA = false>
 __device__ __forceinline__ void bilerp(const T* x, long sh, long sw, Lerp ly, Lerp lx, float (&o)[V]) {
   float v00[V], v01[V], v10[V], v11[V];
   ldv<T, V>(x + ly.i0 * sh + lx.i0 * sw, v00);
@@ -960,7 +949,7 @@ __device__ __forceinline__ void bilerp(const T* x, long sh, long sw, Lerp ly, Le
       v00[k] = fminf(fmaxf(v00[k] + 3.f, 0.f), 6.f) / 6.f; v01[k] = fminf(fmaxf(v01[k] + 3.f, 0.f), 6.f) / 6.f;
       v10[k] = fminf(fmaxf(v10[k] + 3.f, 0.f), 6.f) / 6.f; v11[k] = fminf(fmaxf(v11[k] + 3.f, 0.f), 6.f) / 6.f;
     }
-    o[k] = (v00[k] * lx.l0 + v01[k] * lx.l1) * ly.l0 + (v10[k] * lx.l0 + v11[k] * lx.l1) * ly.l1;
+    o[k] = FMA ? bilerp_mix_fma(v00[k], v01[k], v10[k], v11[k], ly, lx) : bilerp_mix(v00[k], v01[k], v10[k], v11[k], ly, lx);
   }
 }
 
@@ -971,7 +960,7 @@ __global__ void bilinear_kernel(const T* __restrict__ x, long xsn, long xsh, lon
     int n, oy, ox, q;
     decode_idx(i, d, n, oy, ox, q);
     float o[V];
-    bilerp<T, V, false>(x + n * xsn + q * V, xsh, xsw, lerp_of(oy, H, d.H), lerp_of(ox, W, d.W), o);
+    bilerp<T, V, false, true>(x + n * xsn + q * V, xsh, xsw, lerp_of(oy, H, d.H), lerp_of(ox, W, d.W), o);
     stv<T, V>(y + n * ysn + oy * ysh + ox * ysw + q * V, o);
   }
 }

@@ -464,6 +464,28 @@ class SimFusion_3in(HipModule):
         self.cv3 = Conv(in_channel_list[2], out_channels, act=nn.ReLU()) if in_channel_list[2] != out_channels else nn.Identity()
         self.cv_fuse = Conv(out_channels * 3, out_channels, act=nn.ReLU())
 
+    def _laf_route(self, pooled0, slot1, x2, dt):
+        """cv1 + bilinear + cv_fuse as one launch (ops.laf_fuse, bit for bit the three launches): a callable, or None when the module is not covered -
+        training, fp32 / fp8, a cv2 / cv3 convolution, anything but plain 1x1 Conv + BN + {none, SiLU, ReLU}, somebody watching the children (forward
+        hooks), or shapes the kernel does not take.  slot1: the concat buffer's view that holds (or will hold) x[1]."""
+        c1, cf = self.cv1, self.cv_fuse
+        if (self.training or not ops.FUSED_LAF or dt != torch.bfloat16 or not isinstance(self.cv2, nn.Identity) or not isinstance(self.cv3, nn.Identity)
+                or not isinstance(c1, Conv) or not isinstance(cf, Conv) or ops.Q8_CALIB is not None):
+            return None
+        for c in (c1, cf):
+            if (not c.plain_affine() or c.conv.kernel_size != (1, 1) or c.conv.stride != (1, 1) or c.conv.padding != (0, 0) or c.conv.groups != 1
+                    or not isinstance(c.act, (nn.Identity, nn.SiLU, nn.ReLU)) or c.__dict__.get('_q8') or c.out_dtype(pooled0) != dt):
+                return None
+        if self.__dict__.get('_q8') or any(m._forward_hooks for m in self.modules()):
+            return None
+        oc = cf.conv.out_channels
+        if (c1.conv.in_channels != pooled0.shape[1] or c1.conv.out_channels != slot1.shape[1] or cf.conv.in_channels != 3 * slot1.shape[1]
+                or not ops.conv_can_mfma(pooled0, c1.conv.in_channels, c1.conv.out_channels, 1, 1, 1, dt)
+                or not ops.conv_can_mfma(slot1, cf.conv.in_channels, oc, 1, 1, 1, dt)
+                or not ops.laf_fuse_supported(pooled0, slot1, x2, oc, act_code(c1.act), act_code(cf.act), dt)):
+            return None
+        return lambda: ops.laf_fuse(pooled0, slot1, x2, c1.packed(dt, direct=False), act_code(c1.act), cf.packed(dt, direct=False), act_code(cf.act))
+
     def forward(self, x, pre=None):
         """`pre` (the model's neck plan, eval only): {'out': the concat buffer, 'done': slots already in place, 'pooled0': avg-pooled x[0]}."""
         b, _, h, w = x[1].shape
@@ -482,6 +504,11 @@ class SimFusion_3in(HipModule):
         else:
             if pooled0 is None or tuple(pooled0.shape) != (b, x[0].shape[1], h, w):
                 pooled0 = ops.adaptive_avgpool(x[0], ops.new_act(b, x[0].shape[1], h, w, dt, dev))
+            fused = self._laf_route(pooled0, cat[:, oc:2 * oc], x[2], dt)
+            if fused is not None:                              # cv1, the bilinear and cv_fuse in one launch: slots 0 and 2 are never written
+                if not (1 in done and x[1].data_ptr() == cat[:, oc:2 * oc].data_ptr()):
+                    ops.copy(x[1], cat[:, oc:2 * oc])
+                return fused()
             (self.cv1.train_fwd if (self.training and hasattr(self.cv1, 'bn')) else self.cv1.run)(pooled0, out=cat[:, :oc])
         if isinstance(self.cv2, nn.Identity):
             if not (1 in done and x[1].data_ptr() == cat[:, oc:2 * oc].data_ptr()):

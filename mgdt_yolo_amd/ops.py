@@ -783,6 +783,32 @@ def conv1x1_inject(x, pk, ga, gf, out=None):
     return out
 
 
+FUSED_LAF = True        # tests flip this: SimFusion_3in's cv1, bilinear and cv_fuse in one launch vs three
+
+
+def laf_fuse_supported(p0, x1, x2, oc2, act1, act2, dtype):
+    return bool(FUSED_LAF and p0.dtype == dtype and x1.dtype == dtype and x2.dtype == dtype and is_nhwc(p0) and is_nhwc(x1) and is_nhwc(x2) and
+                x2.shape[1] == x1.shape[1] and p0.shape[0] == x1.shape[0] == x2.shape[0] and p0.shape[2:] == x1.shape[2:] and
+                all(t.stride(0) % 8 == 0 and t.stride(2) % 8 == 0 and t.stride(3) % 8 == 0 and t.data_ptr() % 16 == 0 for t in (p0, x1, x2)) and
+                L.lib().mgdt_laf_fuse_supported(p0.shape[1], x1.shape[1], oc2, x1.shape[2], x1.shape[3], x2.shape[2], x2.shape[3], int(act1), int(act2),
+                                                dtype_code(dtype)))
+
+
+def laf_fuse(p0, x1, x2, pk1, act1, pk2, act2, out=None):
+    """out = act2(conv1x1_2([act1(conv1x1_1(p0)) | x1 | bilinear(x2)])) in one launch (mgdt_laf_fuse_fwd): SimFusion_3in with cv2 = cv3 = Identity.
+    pk1 / pk2: the ordinary packed panels of cv1 (c0 -> oc) and cv_fuse (3 oc -> oc); x1 may be a channel slice of the concat buffer."""
+    b, oc, h, w = x1.shape
+    if out is None:
+        out = new_act(b, pk2.cout, h, w, pk2.dtype, x1.device)
+    _same(p0, x1, x2, out)
+    if _PROF is not None:
+        _META['laf_fuse_fwd'] = dict(shape=(b, pk1.cin, h, w, pk2.cout, 1, 1), flops=2.0 * b * h * w * (pk1.cout * pk1.cin + pk2.cout * pk2.cin),
+                                     bytes=float((b * h * w * (pk1.cin + oc + pk2.cout) + x2.numel()) * x1.element_size()))
+    _launch('laf_fuse_fwd', 'mgdt_laf_fuse_fwd', vp(p0), vp(x1), vp(x2), ptr(pk1.w), ptr(pk1.bias), int(act1), ptr(pk2.w), ptr(pk2.bias), int(act2), vp(out),
+            dtype_code(pk2.dtype), stream())
+    return out
+
+
 # ------------------------------------------------------------------ TOODHead pieces
 def groupnorm(x, gamma, beta, groups, eps, act, out=None):
     """out = act(GroupNorm(x)) on NHWC (mgdt_groupnorm_fwd)."""
