@@ -241,6 +241,8 @@ class BaseModel(nn.Module):
             F = int(red[tgt] // red[m.i])
             if F < 1 or h % F or w % F or (kind == 'main' and F != 1) or (kind == 'pool' and F == 1):
                 continue
+            if kind == 'pool' and len(pools) >= 2:
+                continue                                     # the scaling launch writes two pooled copies: a further consumer pools for itself
             th, tw = h // F, w // F
             if isinstance(cm, SimFusion_4in):
                 cs = [self.model[j].c2 for j in src]
@@ -263,7 +265,7 @@ class BaseModel(nn.Module):
             else:
                 out = view
             st['done'].add(slot)
-        return {'out': out, 'pools': pools[:2]} if (out is not None or pools) else None
+        return {'out': out, 'pools': pools} if (out is not None or pools) else None
 
     def _stem_fusable(self, x):
         """layers 0, 1 = Conv(3, 16, 3, 2) -> Conv(16, 32, 3, 2) with BN + SiLU, bf16 compute, layer 0's output used by layer 1 only, and nobody
@@ -286,6 +288,7 @@ class BaseModel(nn.Module):
         adjoint kernels and fills `.grad` of its parameters (overwrite semantics); gradients of tensors with several
         consumers (the save-list) are summed with the HIP add kernel.  `layer_done(i)` is called after layer i's kernels are queued (the
         trainer hangs its bucketed gradient all-reduce on it)."""
+        ops.refuse_inference_mode('model.backward')
         with ops.defer_wgrad():          # final sums of all weight gradients in one launch at the end (or at the all-reduce bucket boundaries)
             self._backward_layers(head_grads, layer_done)
 
@@ -372,6 +375,14 @@ class BaseModel(nn.Module):
         self.load_state_dict(csd, strict=False)
         if verbose:
             print(f'Transferred {len(csd)}/{len(self.model.state_dict())} items from pretrained weights')
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        """Parameters made under torch.inference_mode() have no version counter, so the copy into them is invisible to the packed-weight caches
+        (ops.version_of): the parameter epoch moves instead and every cache rebuilds."""
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        if any(t.is_inference() for t in list(self.parameters()) + list(self.buffers())):
+            ops.PARAM_EPOCH[0] += 1
+        return out
 
     def loss(self, batch, preds=None):
         if not hasattr(self, 'criterion'):

@@ -29,6 +29,21 @@ def _need_gpu(t):
         raise RuntimeError('mgdt_yolo_amd runs on MI355X (HIP) only: got a CPU tensor and there is no CPU/PyTorch fallback')
 
 
+def version_of(t):
+    """`t._version` as a cache key.  A tensor made under torch.inference_mode() has no version counter (reading it raises); it can only be
+    written in place inside that mode, where nothing counts the write, so its key is the constant -1 and whoever writes into such a parameter
+    moves PARAM_EPOCH (BaseModel.load_state_dict does)."""
+    return -1 if t.is_inference() else t._version
+
+
+def refuse_inference_mode(what):
+    """Training calls keep activations and gradients across calls; tensors made under torch.inference_mode() cannot be written outside it,
+    and a train-mode forward keeps nothing for the reverse pass there (autograd is off).  Refused before any launch."""
+    if torch.is_inference_mode_enabled():
+        raise RuntimeError(f'{what} under torch.inference_mode(): training calls are made outside it (the mode is for eval forwards, NMS and '
+                           'validation)')
+
+
 _PROF = None   # list collecting (name, meta, start_event, end_event) while ops.profile() is active
 
 
@@ -263,6 +278,17 @@ def repack_all():
     for o in live:
         o.epoch = PARAM_EPOCH[0]
     return live
+
+
+def fresh_epoch_for_capture():
+    """Move PARAM_EPOCH although no weight changed, and take the registered panels that were current along.  Afterwards every cache entry that
+    only the epoch keeps valid - a derived copy of the weights, a panel packed from one: nothing refreshes those in place - misses, so a graph
+    capture that follows rebuilds them with captured launches instead of reading, on every replay, what an eval forward of the same epoch left
+    in memory the graph does not own."""
+    cur = [o for o in (_PACK_REGISTRY or ()) if pack_is_current(o)]
+    PARAM_EPOCH[0] += 1
+    for o in cur:
+        o.epoch = PARAM_EPOCH[0]
 
 
 def pack_is_current(obj):
@@ -1014,13 +1040,16 @@ NMS_USE_BEST_KEYS = True      # tests flip this to compare against the scan of t
 
 def attach_best_keys(y, best):
     """The Detect tail kernel left the NMS key of every anchor's best class in `best`; remember it on the prediction tensor together with
-    the tensor's version, so that `nms(y)` can skip its own scan over the nc score rows as long as nobody wrote into y since."""
+    the tensor's version, so that `nms(y)` can skip its own scan over the nc score rows as long as nobody wrote into y since.  A prediction made
+    under torch.inference_mode() has no version counter, so a later write into it could not be seen: it carries no keys and NMS scans its rows."""
+    if y.is_inference():
+        return
     y._mgdt_best = (best, y._version)
 
 
 def _best_keys_of(pred, b, a):
     bk = getattr(pred, '_mgdt_best', None)
-    if not NMS_USE_BEST_KEYS or bk is None:
+    if not NMS_USE_BEST_KEYS or bk is None or pred.is_inference():
         return None
     best, ver = bk
     if ver != pred._version or best.shape != (b, a) or best.dtype != torch.int64 or best.device != pred.device or not best.is_contiguous():
@@ -1242,7 +1271,7 @@ _DECONV_DGRAD_PK = {}
 
 def _deconv_dgrad_panels(weight, dtype):
     """the four phase panels of `weight`, rebuilt only when the weight changed and repack_all() did not refresh them (as conv_dgrad keeps its panels)"""
-    key = (PARAM_EPOCH[0], weight._version, dtype)
+    key = (PARAM_EPOCH[0], version_of(weight), dtype)
     ck = (weight.data_ptr(), dtype)
     pks = _DECONV_DGRAD_PK.get(ck)
     if pks is not None and pks[0].owner() is weight and pks[0].key[1:] == key[1:] and all(pack_is_current(q) for q in pks):
@@ -1773,7 +1802,7 @@ def conv_dgrad(dy, weight, k, stride, dx, accumulate=False, r2=None):
     if (stride == 1 and (weight.dim() == 2 and k == 1 or weight.dim() == 4 and weight.shape[2] == k) and k in (1, 3) and dx.dtype == dy.dtype
             and is_nhwc(dx) and cin % 4 == 0
             and conv_can_mfma(dy, cout, cin, k, 1, 1, dy.dtype)):
-        key = (PARAM_EPOCH[0], weight._version, dy.dtype)
+        key = (PARAM_EPOCH[0], version_of(weight), dy.dtype)
         pk = _DGRAD_PK.get(weight.data_ptr())
         if pk is not None and pk.owner() is weight and pk.key[1:] == key[1:] and pack_is_current(pk):
             pk.key = key                                   # refreshed by repack_all() for this epoch
@@ -1783,7 +1812,7 @@ def conv_dgrad(dy, weight, k, stride, dx, accumulate=False, r2=None):
     if (stride == 2 and k == 3 and weight.dim() == 4 and weight.shape[2] == 3 and dx.dtype == dy.dtype and is_nhwc(dx) and cin % 4 == 0
             and dx.shape[2] == 2 * dy.shape[2] and dx.shape[3] == 2 * dy.shape[3] and conv_can_mfma(dy, cout, cin, 3, 1, 1, dy.dtype)):
         # four phases (input-pixel parities), each a 3x3 convolution over dy written to a strided view of dx
-        key = (PARAM_EPOCH[0], weight._version, dy.dtype)
+        key = (PARAM_EPOCH[0], version_of(weight), dy.dtype)
         pks = _DGRAD_PK.get((weight.data_ptr(), 2))
         if pks is not None and pks[0].owner() is weight and pks[0].key[1:] == key[1:] and all(pack_is_current(q) for q in pks):
             for q in pks:

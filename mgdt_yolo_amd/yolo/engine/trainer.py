@@ -420,6 +420,8 @@ class DetectionTrainer:
         if captured:
             gs = []
             torch.cuda.synchronize()
+            # an eval forward since the last step has cached derived copies of the weights under this epoch: the capture must not read them
+            ops.fresh_epoch_for_capture()
             epoch0 = ops.PARAM_EPOCH[0]
             for part in (('grad', 'update') if self.graph_split else (None,)):
                 g = torch.cuda.CUDAGraph()
@@ -433,6 +435,11 @@ class DetectionTrainer:
             ops.PARAM_EPOCH[0] = epoch0                     # ... which has not run yet: the replay below is that step
             for o in S['panels']:
                 o.epoch = epoch0
+            # A panel that became live since the earlier captures (an eval() forward of this model packs its own, BatchNorm folded) is in this
+            # graph's re-pack only: a replay of an older graph would leave it behind.  Those graphs go, and are captured again over this set
+            # when their label-slot bucket comes back.
+            ids = {id(o) for o in S['panels']}
+            self._graphs = {k: v for k, v in self._graphs.items() if {id(o) for o in v[2]} == ids}
             self._graphs[nmax] = (gs, S['out5'], list(S['panels']))
         gs, out5, panels = self._graphs[nmax]
         gs[0].replay()
@@ -440,9 +447,8 @@ class DetectionTrainer:
             parallel.all_reduce_mean_(st.grad)       # one flat message between the two replays (loss was scaled by world_size: trainer.py:337-338)
             gs[1].replay()
         ops.PARAM_EPOCH[0] += 1                     # the replay moved the weights: packed-weight caches of any eager forward are stale ...
-        for _, _, ps in self._graphs.values():      # ... except the panels the replayed re-pack just refreshed in place
-            for o in ps:
-                o.epoch = ops.PARAM_EPOCH[0]
+        for o in panels:                            # ... except the panels the replayed re-pack just refreshed in place - those and no others
+            o.epoch = ops.PARAM_EPOCH[0]
         st.steps += 1
         self.crit.epoch += 1
         self.last_opt_step = self.ni
@@ -450,6 +456,7 @@ class DetectionTrainer:
         return out5[0].clone(), out5[1:4].clone()
 
     def step(self, batch, epoch=0):
+        ops.refuse_inference_mode('DetectionTrainer.step')
         st = self.state
         self.warmup(epoch)
         if self._graph_ok():

@@ -1263,9 +1263,12 @@ def test_reference_training_call_sequence_reaches_the_hip_backward():
             np.testing.assert_allclose(p.grad.cpu().numpy(), 2 * g1[k].cpu().numpy(), rtol=1e-5, atol=1e-7, err_msg=k)
 
 
-def test_packed_weight_caches_follow_the_hip_optimizer():
+@pytest.mark.parametrize('mode', ['no_grad', 'inference_mode'])
+def test_packed_weight_caches_follow_the_hip_optimizer(mode):
     """The HIP SGD kernel updates parameters behind torch's back; every packed-weight cache must be rebuilt afterwards: the stepped
-    model must compute exactly what a freshly built model with the same state_dict computes."""
+    model must compute exactly what a freshly built model with the same state_dict computes.  `mode`: the eval forwards run under
+    torch.no_grad() or under torch.inference_mode() (panels and activations are then inference tensors, which have no version counter)."""
+    ctx = getattr(torch, mode)
     from mgdt_yolo_amd.nn.tasks import DetectionModel
     from mgdt_yolo_amd.seeding import seeded_labels
     from mgdt_yolo_amd.yolo.engine.trainer import DetectionTrainer
@@ -1277,7 +1280,7 @@ def test_packed_weight_caches_follow_the_hip_optimizer():
     batch = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in batch.items()}
     x = seeded_images(2, 96, 96, seed=5).to(DEV)
     m.eval()
-    with torch.no_grad():
+    with ctx():
         y0 = m(x)[0].clone()
     m.train()
     for _ in range(2):
@@ -1286,7 +1289,7 @@ def test_packed_weight_caches_follow_the_hip_optimizer():
     fresh = DetectionModel(cfg, verbose=False).to(DEV)
     fresh.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
     fresh.eval()
-    with torch.no_grad():
+    with ctx():
         y1, y2 = m(x)[0], fresh(x)[0]
     assert not torch.equal(y0, y1), 'two optimizer steps at lr 0.05 must change the output'
     assert torch.equal(y1, y2)
