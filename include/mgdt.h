@@ -254,6 +254,17 @@ int mgdt_laf_fuse_supported(int c0, int oc, int oc2, int h, int w, int h2, int w
 int mgdt_laf_fuse_fwd(const mgdt_view* p0, const mgdt_view* x1, const mgdt_view* x2, const void* packed_w1, const float* bias1, int act1,
                       const void* packed_w2, const float* bias2, int act2, const mgdt_view* y, int dtype, mgdt_stream s);
 
+/* ---- SPPF / SPP in one launch, bf16 (nn/modules/block.py:121-153, eval):
+ *   y = act2(cv2([x0 | y1 | y2 | y3]))        x0 = act1(cv1(x)); y1, y2, y3 = three chained MaxPool2d(5, 1, 2) of x0 (-inf padding)
+ * x (N, h, w, c1) and y (N, h, w, c2): NHWC views, x with 16-byte and y with 8-byte aligned pixel / row / image strides (either may be a channel
+ * slice of a wider buffer).  packed_w1 / bias1 = mgdt_conv_pack(c1, c1 / 2, 1, bf16) of cv1, packed_w2 / bias2 = mgdt_conv_pack(2 * c1, c2, 1, bf16)
+ * of cv2.  The values are those of mgdt_conv2d_fwd into concat slot 0, mgdt_sppf_pool_fwd into slots 1..3 and mgdt_conv2d_fwd over the buffer,
+ * bit for bit; the 2 * c1 channel buffer does not exist.
+ * mgdt_sppf_fuse_supported: bf16, cm == c1 / 2, (c1, c2) in {(64, 64), (64, 96), (256, 256)}, activations none / SiLU / ReLU. */
+int mgdt_sppf_fuse_supported(int c1, int cm, int c2, int h, int w, int act1, int act2, int dtype);
+int mgdt_sppf_fuse_fwd(const mgdt_view* x, const void* packed_w1, const float* bias1, int act1, const void* packed_w2, const float* bias2, int act2,
+                       const mgdt_view* y, int dtype, mgdt_stream s);
+
 /* ---- TOODHead (nn/modules/head.py:466-572; parity unpinned: mmcv's ModulatedDeformConv2d is not shipped with the reference) --------
  * GroupNorm + activation (Conv_GN head.py:67-81, DyDCNv2's norm block.py:427-431): y = act(group_norm(x, groups, gamma, beta, eps)).
  * ws: mgdt_groupnorm_workspace_bytes(n, c) bytes, 8-byte aligned (it holds the double partial sums; MGDT_BAD_ARG otherwise); x, y: 4-aligned NHWC views,

@@ -91,6 +91,7 @@ static inline int knob_stem_wgs() { return knob_int("MGDT_STEM_WGS", 0); }     /
  * MGDT_MLP_DBG              set = phase stamps                                                               call  mlp_chain.hip
  * MGDT_NMS_DBG              set = phase clocks                                                               call  nms.hip
  * MGDT_SPPF_CHAINED         set = the chained three-pass SPPF kernel                                         once  pointwise.hip
+ * MGDT_SPPF_DBG             set = phase stamps                                                               call  sppf_fused.hip
  * MGDT_SPR_DBG              set = phase stamps                                                               call  pointwise.hip
  * MGDT_SPR_KMAX             long, 12; workgroups per image at most                                           once  pointwise.hip
  * MGDT_SPR_VECS             long, 2048; vectors per workgroup                                                once  pointwise.hip

@@ -327,10 +327,33 @@ class SPPF(HipModule):
         self.cv2 = Conv(c_ * 4, c2, 1, 1)
         self.m = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)   # module-tree parity only
 
+    def _fused_route(self, x):
+        """cv1 + the three pools + cv2 as one launch (ops.sppf_fuse, bit for bit the three launches): a callable, or None when the module is not
+        covered - training, fp32 / fp8, anything but plain 1x1 Conv + BN + {none, SiLU, ReLU}, somebody watching the module or its convolutions
+        (forward hooks), or shapes the kernel does not take."""
+        c1, c2 = self.cv1, self.cv2
+        dt = torch.bfloat16
+        if self.training or not ops.FUSED_SPPF or x.dtype != dt or ops.Q8_CALIB is not None or not isinstance(c1, Conv) or not isinstance(c2, Conv):
+            return None
+        for c in (c1, c2):
+            if (not c.plain_affine() or c.conv.kernel_size != (1, 1) or c.conv.stride != (1, 1) or c.conv.padding != (0, 0) or c.conv.groups != 1
+                    or not isinstance(c.act, (nn.Identity, nn.SiLU, nn.ReLU)) or c.__dict__.get('_q8') or c.out_dtype(x) != dt):
+                return None
+        if self.__dict__.get('_q8') or self._forward_hooks or c1._forward_hooks or c2._forward_hooks:
+            return None
+        cm, co = c1.conv.out_channels, c2.conv.out_channels
+        if (c1.conv.in_channels != x.shape[1] or c2.conv.in_channels != 4 * cm or not ops.conv_can_mfma(x, x.shape[1], cm, 1, 1, 1, dt)
+                or not ops.sppf_fuse_supported(x, cm, co, act_code(c1.act), act_code(c2.act), dt)):
+            return None
+        return lambda: ops.sppf_fuse(x, c1.packed(dt, direct=False), act_code(c1.act), c2.packed(dt, direct=False), act_code(c2.act))
+
     def forward(self, x):
         b, _, h, w = x.shape
         c_ = self.cv1.conv.out_channels
         train = self.training and hasattr(self.cv1, 'bn')
+        fused = self._fused_route(x)
+        if fused is not None:                                  # the 4 * c_ channel concat buffer is never written
+            return fused()
         cat = ops.new_act(b, 4 * c_, h, w, self.cv1.out_dtype(x), x.device)
         (self.cv1.train_fwd if train else self.cv1.run)(x, out=cat[:, :c_])
         ops.sppf_pools(cat[:, :c_], cat[:, c_:2 * c_], cat[:, 2 * c_:3 * c_], cat[:, 3 * c_:])

@@ -835,6 +835,30 @@ def laf_fuse(p0, x1, x2, pk1, act1, pk2, act2, out=None):
     return out
 
 
+FUSED_SPPF = True       # tests flip this: SPPF's cv1, three max-pools and cv2 in one launch vs three
+
+
+def sppf_fuse_supported(x, cm, c2, act1, act2, dtype):
+    return bool(FUSED_SPPF and x.dtype == dtype and is_nhwc(x) and
+                x.stride(0) % 8 == 0 and x.stride(2) % 8 == 0 and x.stride(3) % 8 == 0 and x.data_ptr() % 16 == 0 and
+                L.lib().mgdt_sppf_fuse_supported(x.shape[1], cm, c2, x.shape[2], x.shape[3], int(act1), int(act2), dtype_code(dtype)))
+
+
+def sppf_fuse(x, pk1, act1, pk2, act2, out=None):
+    """out = act2(conv1x1_2([x0 | mp(x0) | mp(mp(x0)) | mp(mp(mp(x0)))])), x0 = act1(conv1x1_1(x)), mp = MaxPool2d(5, 1, 2), in one launch
+    (mgdt_sppf_fuse_fwd).  pk1 / pk2: the ordinary packed panels of cv1 (c1 -> c1 / 2) and cv2 (2 c1 -> c2); x and out may be channel slices."""
+    b, _, h, w = x.shape
+    if out is None:
+        out = new_act(b, pk2.cout, h, w, pk2.dtype, x.device)
+    _same(x, out)
+    if _PROF is not None:
+        _META['sppf_fuse_fwd'] = dict(shape=(b, pk1.cin, h, w, pk2.cout, 1, 1), flops=2.0 * b * h * w * (pk1.cout * pk1.cin + pk2.cout * pk2.cin),
+                                      bytes=float(b * h * w * (pk1.cin + pk2.cout) * x.element_size()))
+    _launch('sppf_fuse_fwd', 'mgdt_sppf_fuse_fwd', vp(x), ptr(pk1.w), ptr(pk1.bias), int(act1), ptr(pk2.w), ptr(pk2.bias), int(act2), vp(out),
+            dtype_code(pk2.dtype), stream())
+    return out
+
+
 # ------------------------------------------------------------------ TOODHead pieces
 def groupnorm(x, gamma, beta, groups, eps, act, out=None):
     """out = act(GroupNorm(x)) on NHWC (mgdt_groupnorm_fwd)."""
