@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from .conv import Conv, HipModule, act_code
+from .conv import EPILOGUE_ACTS, FUSED_ACTS, Conv, HipModule, act_code, fp8_claims, merged_panel, plain, watched
 from .convnextv2 import ConvNeXtV2_Block
 from .spr_module import SPRModule
 
@@ -16,22 +16,17 @@ __all__ = ('DFL', 'SPP', 'SPPF', 'C2f', 'C3', 'MSPA_C2f', 'Bottleneck', 'SimFusi
            'InjectionMultiSum_Auto_pool', 'Upsample', 'Proto')
 
 
-def _plain_block(first, last, bottlenecks):
-    """True when a CSP block is made of what mgdt_csp_block_fwd computes: 1x1 Conv+BN+act at both ends, bottlenecks of two dense 3x3 Conv+BN
-    with the same activation and one shortcut setting."""
-    def conv_ok(c, k):
-        return (isinstance(c, Conv) and c.plain_affine() and c.conv.kernel_size == (k, k) and c.conv.stride == (1, 1) and c.conv.groups == 1
-                and act_code(c.act) == a0)
-    try:
-        a0 = act_code(first.act)
-    except RuntimeError:
+def _plain_block(first, last, bottlenecks, k1=3):
+    """True when a CSP block is made of what mgdt_csp_block_fwd computes: plain 1x1 Conv + SiLU (the blocks' default activation) at both ends, bottlenecks
+    of a plain k1 x k1 and a plain 3x3 Conv + SiLU with one width and one shortcut setting.  Inner hooks are not looked at: tasks.py watches the layers."""
+    if not (plain(first, 1) and plain(last, 1)) or len(bottlenecks) == 0:
         return False
-    if a0 != ops.ACT_SILU:            # the fused block kernel is built for the blocks' default activation
-        return False
-    if not (conv_ok(first, 1) and conv_ok(last, 1)) or len(bottlenecks) == 0:
-        return False
-    return all(isinstance(m, Bottleneck) and conv_ok(m.cv1, 3) and conv_ok(m.cv2, 3) and m.add == bottlenecks[0].add
+    return all(isinstance(m, Bottleneck) and plain(m.cv1, k1) and plain(m.cv2, 3) and m.add == bottlenecks[0].add
                and m.cv1.conv.in_channels == m.cv1.conv.out_channels == m.cv2.conv.out_channels for m in bottlenecks)
+
+
+def _block_mids(bottlenecks, dt):
+    return [pk for m in bottlenecks for pk in (m.cv1.packed(dt, False), m.cv2.packed(dt, False))]
 
 
 class DFL(nn.Module):
@@ -59,11 +54,9 @@ class Bottleneck(HipModule):
 
     def run(self, x, out=None, x2=None):
         """y = [x (+x2)] + cv2(cv1(x (+x2))); `x2` is MSPA's pending `sp + spx[i]` add."""
-        if self.training and hasattr(self.cv1, 'bn'):
-            t = self.cv1.train_fwd(x, x2=x2)
-            return self.cv2.train_fwd(t, out=out, r1=x if self.add else None, r2=x2 if self.add else None)
-        t = self.cv1.run(x, x2=x2)
-        return self.cv2.run(t, out=out, r1=x if self.add else None, r2=x2 if self.add else None)
+        train = self.training and hasattr(self.cv1, 'bn')
+        t = self.cv1.fwd(train, x, x2=x2)
+        return self.cv2.fwd(train, t, out=out, r1=x if self.add else None, r2=x2 if self.add else None)
 
     def backward(self, gz, acc_into=None):
         """Returns d/d(x [+ x2]) (the same tensor is the gradient of both addends); with `acc_into` the result is ADDED to that view instead
@@ -88,35 +81,38 @@ class C2f(HipModule):
     def forward(self, x, head=None):
         """`head` (the model's plan, eval only): (injection module, its inputs) when this block's input is that injection's output and
         nobody else reads it - cv1 then runs inside the injection launch (mgdt_conv1x1_inject_conv_fwd) and `x` is None."""
-        if head is not None:
-            x_l = head[1][0]
-            dt0 = self.cv1.out_dtype(x_l)
-            ok = (not (self.training and hasattr(self.cv1, 'bn')) and _plain_block(self.cv1, self.cv2, self.m) and ops.csp_block_supported(
-                ops.CSP_C2F, ops.new_act(x_l.shape[0], 2 * self.c, x_l.shape[2], x_l.shape[3], dt0, x_l.device), self.cv2.conv.out_channels, self.c, len(self.m), dt0))
-            y01 = head[0].forward_into_conv(head[1], self.cv1) if ok else None
-            if y01 is None:
-                x = head[0](head[1])                         # not covered after all: the injection's own launch
-            else:
-                mids = [pk for m in self.m for pk in (m.cv1.packed(y01.dtype, False), m.cv2.packed(y01.dtype, False))]
-                return ops.csp_block(ops.CSP_C2F, y01, None, None, mids, self.m[0].add, self.cv2.packed(y01.dtype, False), self.c, act_code(self.cv1.act),
-                                     self.cv2.conv.out_channels, False)[0]
+        fused = self._fused_route(x if head is None else head[1][0], inject=head)
+        if fused is None and head is not None:
+            x = head[0](head[1])                             # not covered after all: the injection's own launch
+            fused = self._fused_route(x)
+        if fused is not None:
+            return fused()
         b, _, h, w = x.shape
         c, n = self.c, len(self.m)
         train = self.training and hasattr(self.cv1, 'bn')
-        dt = self.cv1.out_dtype(x)
-        if not train and x.dtype == dt and _plain_block(self.cv1, self.cv2, self.m):
-            y01 = ops.new_act(b, 2 * c, h, w, dt, x.device)
-            if ops.csp_block_supported(ops.CSP_C2F, y01, self.cv2.conv.out_channels, c, n, dt):
-                # two launches: cv1 (a wide streaming 1x1 GEMM), then the bottleneck chain on LDS-resident tiles + cv2 over the concat
-                self.cv1.run(x, out=y01)
-                mids = [pk for m in self.m for pk in (m.cv1.packed(dt, False), m.cv2.packed(dt, False))]
-                return ops.csp_block(ops.CSP_C2F, y01, None, None, mids, self.m[0].add, self.cv2.packed(dt, False), c, act_code(self.cv1.act),
-                                     self.cv2.conv.out_channels, False)[0]
-        cat = ops.new_act(b, (2 + n) * c, h, w, dt, x.device)
-        (self.cv1.train_fwd if train else self.cv1.run)(x, out=cat[:, :2 * c])
+        cat = ops.new_act(b, (2 + n) * c, h, w, self.cv1.out_dtype(x), x.device)
+        self.cv1.fwd(train, x, out=cat[:, :2 * c])
         for j, m in enumerate(self.m):
             m.run(cat[:, (1 + j) * c:(2 + j) * c], out=cat[:, (2 + j) * c:(3 + j) * c])
-        return (self.cv2.train_fwd if train else self.cv2.run)(cat)
+        return self.cv2.fwd(train, cat)
+
+    def _fused_route(self, x, inject=None):
+        """cv1 (a wide streaming 1x1 GEMM; `inject` = (injection module, its inputs), `x` its local input: inside that injection's launch), then the bottleneck
+        chain on LDS-resident tiles + cv2 over the concat (mode CSP_C2F): a callable, or None.  fp8 is not consulted: block kernels stay bf16 under quantize_fp8."""
+        c, dt = self.c, self.cv1.out_dtype(x)
+        if (self.training and hasattr(self.cv1, 'bn')) or (inject is None and x.dtype != dt) or not _plain_block(self.cv1, self.cv2, self.m):
+            return None
+        y01 = ops.new_act(x.shape[0], 2 * c, x.shape[2], x.shape[3], dt, x.device)
+        if not ops.csp_block_supported(ops.CSP_C2F, y01, self.cv2.conv.out_channels, c, len(self.m), dt):
+            return None
+
+        def block(y):
+            return ops.csp_block(ops.CSP_C2F, y, None, None, _block_mids(self.m, y.dtype), self.m[0].add, self.cv2.packed(y.dtype, False), c, act_code(self.cv1.act),
+                                 self.cv2.conv.out_channels, False)[0]
+        if inject is None:
+            return lambda: block(self.cv1.run(x, out=y01))
+        into = inject[0]._into_conv_route(inject[1], self.cv1)
+        return None if into is None else lambda: block(into())
 
     forward_split = forward
 
@@ -145,54 +141,38 @@ class C3(HipModule):
         self.cv3 = Conv(2 * c_, c2, 1)
         self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
 
-    def _plain(self):
-        """what mode CSP_C3 of mgdt_csp_block_fwd computes: 1x1 Conv + BN (or fused bias) + SiLU at both ends, bottlenecks of a dense 1x1 and a dense 3x3
-        with one shortcut setting, nobody watching the inner modules (forward hooks), no fp8 calibration or fp8 sites"""
-        convs = [self.cv1, self.cv2, self.cv3] + [c for m in self.m for c in (m.cv1, m.cv2)]
-        ks = [1, 1, 1] + [1, 3] * len(self.m)
-        if ops.Q8_CALIB is not None or len(self.m) == 0 or any(m._forward_hooks for m in self.modules() if m is not self):
-            return False
-        for c, k in zip(convs, ks):
-            if not (isinstance(c, Conv) and c.plain_affine() and isinstance(c.act, nn.SiLU) and c.conv.kernel_size == (k, k) and c.conv.stride == (1, 1)
-                    and c.conv.groups == 1 and c.conv.dilation == (1, 1) and not c.__dict__.get('_q8')):
-                return False
-        fused = not hasattr(self.cv1, 'bn')
-        if fused != (not hasattr(self.cv2, 'bn')) or (not fused and self.cv1.bn.eps != self.cv2.bn.eps):
-            return False
-        return all(isinstance(m, Bottleneck) and m.add == self.m[0].add and m.cv1.conv.in_channels == m.cv1.conv.out_channels == m.cv2.conv.out_channels == self.c
-                   for m in self.m)
-
-    def _merged_front(self, dt):
-        """PackedConv of cat(cv1, cv2) along cout (BN folded per branch): [a | b] in one launch"""
-        a, b = self.cv1, self.cv2
-        fused = not hasattr(a, 'bn')
-        cat = lambda fn: torch.cat([fn(a).detach().float(), fn(b).detach().float()])
-        zb = lambda m: m.conv.bias if m.conv.bias is not None else torch.zeros(m.conv.out_channels, device=m.conv.weight.device)
-        bn = lambda: None if fused else (cat(lambda m: m.bn.weight), cat(lambda m: m.bn.bias), cat(lambda m: m.bn.running_mean), cat(lambda m: m.bn.running_var), a.bn.eps)
-        return self._cached(('front', dt), [t for m in (a, b) for t in m.affine_tensors()],
-                            lambda: ops.PackedConv(cat(lambda m: m.conv.weight), cat(zb) if fused else None, bn(), 1, dt))
+    def _fused_route(self, x):
+        """[a | b] = [cv1 | cv2](x) over the merged panel (a wide streaming 1x1 GEMM), then the bottleneck chain on LDS-resident tiles + cv3 (mode CSP_C3): a
+        callable, or None - an unlisted (width, n) class, somebody watching the inner modules, fp8 calibration or sites, anything but plain convs of one width."""
+        c, n, dt = self.c, len(self.m), self.cv1.out_dtype(x)
+        if (self.training and hasattr(self.cv1, 'bn')) or dt != torch.bfloat16 or x.dtype != dt or not ops.c3_fused_route(c, n):
+            return None
+        if (fp8_claims(self.cv1, self.cv2, self.cv3, *(cv for m in self.m for cv in (m.cv1, m.cv2))) or watched(*(m for m in self.modules() if m is not self))
+                or not (_plain_block(self.cv1, self.cv3, self.m, k1=1) and plain(self.cv2, 1)) or any(m.cv1.conv.in_channels != c for m in self.m)
+                or not ops.conv_can_mfma(x, x.shape[1], 2 * c, 1, 1, 1, dt)):
+            return None
+        ab = ops.new_act(x.shape[0], 2 * c, x.shape[2], x.shape[3], dt, x.device)
+        if not ops.csp_block_supported(ops.CSP_C3, ab, self.cv3.conv.out_channels, c, n, dt):
+            return None
+        front = merged_panel(self, ('front',), self.cv1, self.cv2, 1, dt)
+        if front is None:
+            return None
+        return lambda: ops.csp_block(ops.CSP_C3, ops.conv2d(x, front, 1, ops.ACT_SILU, out=ab), None, None, _block_mids(self.m, dt), self.m[0].add,
+                                     self.cv3.packed(dt, False), c, ops.ACT_SILU, self.cv3.conv.out_channels, False)[0]
 
     def forward(self, x):
+        fused = self._fused_route(x)
+        if fused is not None:
+            return fused()
         b, _, h, w = x.shape
         c, n = self.c, len(self.m)
         train = self.training and hasattr(self.cv1, 'bn')
-        dt0 = self.cv1.out_dtype(x)
-        if (not train and dt0 == torch.bfloat16 and x.dtype == dt0 and ops.c3_fused_route(c, n) and self._plain()
-                and ops.conv_can_mfma(x, x.shape[1], 2 * c, 1, 1, 1, dt0)):
-            ab = ops.new_act(b, 2 * c, h, w, dt0, x.device)
-            if ops.csp_block_supported(ops.CSP_C3, ab, self.cv3.conv.out_channels, c, n, dt0):
-                # two launches: [a | b] = [cv1 | cv2](x) (a wide streaming 1x1 GEMM), then the bottleneck chain on LDS-resident tiles + cv3
-                ops.conv2d(x, self._merged_front(dt0), 1, ops.ACT_SILU, out=ab)
-                mids = [pk for m in self.m for pk in (m.cv1.packed(dt0, False), m.cv2.packed(dt0, False))]
-                return ops.csp_block(ops.CSP_C3, ab, None, None, mids, self.m[0].add, self.cv3.packed(dt0, False), c, ops.ACT_SILU,
-                                     self.cv3.conv.out_channels, False)[0]
-        f = (lambda m: m.train_fwd) if train else (lambda m: m.run)
         cat = ops.new_act(b, 2 * c, h, w, self.cv1.out_dtype(x), x.device)
-        f(self.cv2)(x, out=cat[:, c:])
-        t = f(self.cv1)(x, out=cat[:, :c] if n == 0 else None)
+        self.cv2.fwd(train, x, out=cat[:, c:])
+        t = self.cv1.fwd(train, x, out=cat[:, :c] if n == 0 else None)
         for j, m in enumerate(self.m):
             t = m.run(t, out=cat[:, :c] if j == n - 1 else None)
-        return f(self.cv3)(cat)
+        return self.cv3.fwd(train, cat)
 
     def backward(self, g):
         c = self.c
@@ -236,31 +216,26 @@ class MSPA_C2f(HipModule):
         b, _, h, w = x.shape
         wd, s, n = self.inwidth, self.nums, self.btnk_nums
         train = self.training and hasattr(self.convs[0], 'bn')
-        run = (lambda m: m.train_fwd) if train else (lambda m: m.run)
         dt = self.convs[0].out_dtype(x)
         at = self.attention
-        if (not train and s == 4 and self.inwidth == self.outwidth and self._chain_ok() and _plain_block(self.convs[0], self.convs[3], self.bottleneck)
-                and ops.csp_block_supported(ops.CSP_MSPA, x, self.convs[3].conv.out_channels, wd, n, dt)):
-            # one launch for the block (mgdt_csp_block_fwd) + one for attention MLP and scaling; the pooled sums come out of the block kernel
-            mids = [pk for m in self.bottleneck for pk in (m.cv1.packed(dt, False), m.cv2.packed(dt, False))]
-            out, pool, slots, tiles = ops.csp_block(ops.CSP_MSPA, x, self._packed_chain(dt).blob, None, mids, self.bottleneck[0].add,
-                                                    self.convs[3].packed(dt, False), wd, act_code(self.convs[0].act), self.convs[3].conv.out_channels, True)
-            return ops.spr_attention_scale(out, at.fc1.weight, at.fc1.bias, at.fc2.weight, at.fc2.bias, s, out=d_out, part=pool, nsplit=slots, tiles=tiles, pools=d_pools)
+        fused = self._fused_route(x, d_out, d_pools)
+        if fused is not None:
+            return fused()
         cat = ops.new_act(b, (s - 1 + n) * wd, h, w, dt, x.device)
         # sp_i = convs[i](sp_{i-1} + spx[i]) written straight into its concat slot (block.py:250-259)
         if not train and s == 4 and ops.pw_chain_supported(wd, cat.dtype) and x.dtype == cat.dtype and self._chain_ok():
             ops.pw_chain3(x[:, :3 * wd], self._packed_chain(cat.dtype), act_code(self.convs[0].act), cat[:, :3 * wd])   # one launch
         else:
-            run(self.convs[0])(x[:, :wd], out=cat[:, :wd])
+            self.convs[0].fwd(train, x[:, :wd], out=cat[:, :wd])
             for i in range(1, s - 1):
-                run(self.convs[i])(cat[:, (i - 1) * wd:i * wd], x2=x[:, i * wd:(i + 1) * wd], out=cat[:, i * wd:(i + 1) * wd])
+                self.convs[i].fwd(train, cat[:, (i - 1) * wd:i * wd], x2=x[:, i * wd:(i + 1) * wd], out=cat[:, i * wd:(i + 1) * wd])
         # last group: chained bottlenecks, each output kept (block.py:260-263)
         src, pending = cat[:, (s - 2) * wd:(s - 1) * wd], x[:, (s - 1) * wd:s * wd]
         for j, m in enumerate(self.bottleneck):
             dst = cat[:, (s - 1 + j) * wd:(s + j) * wd]
             m.run(src, out=dst, x2=pending)
             src, pending = dst, None
-        out = run(self.convs[s - 1])(cat)
+        out = self.convs[s - 1].fwd(train, cat)
         if train:
             attn, part = ops.spr_attention_train(out, at.fc1.weight, at.fc1.bias, at.fc2.weight, at.fc2.bias, s)
             self._save_ctx((out, attn, part, x.shape))
@@ -268,11 +243,26 @@ class MSPA_C2f(HipModule):
             return ops.spr_attention_scale(out, at.fc1.weight, at.fc1.bias, at.fc2.weight, at.fc2.bias, s, out=d_out, pools=d_pools)   # pool, then MLP + scaling in one launch
         return ops.scale_channels(out, attn)
 
+    def _fused_route(self, x, d_out=None, d_pools=()):
+        """one launch for the block (mode CSP_MSPA of mgdt_csp_block_fwd; the pooled sums come out of it) + one for attention MLP and scaling, as a
+        callable, or None when not covered.  fp8 is not consulted: the block kernels stay bf16 under quantize_fp8."""
+        wd, n, at, last = self.inwidth, self.btnk_nums, self.attention, self.convs[-1]
+        dt = self.convs[0].out_dtype(x)
+        if ((self.training and hasattr(self.convs[0], 'bn')) or self.nums != 4 or wd != self.outwidth or not self._chain_ok()
+                or not _plain_block(self.convs[0], last, self.bottleneck) or not ops.csp_block_supported(ops.CSP_MSPA, x, last.conv.out_channels, wd, n, dt)):
+            return None
+
+        def launch():
+            out, pool, slots, tiles = ops.csp_block(ops.CSP_MSPA, x, self._packed_chain(dt).blob, None, _block_mids(self.bottleneck, dt), self.bottleneck[0].add,
+                                                    last.packed(dt, False), wd, act_code(self.convs[0].act), last.conv.out_channels, True)
+            return ops.spr_attention_scale(out, at.fc1.weight, at.fc1.bias, at.fc2.weight, at.fc2.bias, 4, out=d_out, part=pool, nsplit=slots, tiles=tiles, pools=d_pools)
+        return launch
+
     def _chain_ok(self):
-        """the three front convs are plain 1x1 Conv+BN with one activation (what mgdt_pw_chain3_fwd computes)"""
+        """the three front convs are plain 1x1 convolutions of the block's width with one activation (what mgdt_pw_chain3_fwd computes)"""
         cs = list(self.convs)[:3]
-        return all(c.plain_affine() and c.conv.kernel_size == (1, 1) and c.conv.groups == 1 and c.conv.in_channels == self.inwidth
-                   and c.conv.out_channels == self.inwidth and act_code(c.act) == act_code(cs[0].act) for c in cs)
+        same = tuple(a for a in FUSED_ACTS if isinstance(cs[0].act, a))
+        return all(plain(c, 1, same, stride=None) and c.conv.in_channels == c.conv.out_channels == self.inwidth for c in cs)
 
     def _packed_chain(self, dtype):
         cs = list(self.convs)[:3]
@@ -333,13 +323,8 @@ class SPPF(HipModule):
         (forward hooks), or shapes the kernel does not take."""
         c1, c2 = self.cv1, self.cv2
         dt = torch.bfloat16
-        if self.training or not ops.FUSED_SPPF or x.dtype != dt or ops.Q8_CALIB is not None or not isinstance(c1, Conv) or not isinstance(c2, Conv):
-            return None
-        for c in (c1, c2):
-            if (not c.plain_affine() or c.conv.kernel_size != (1, 1) or c.conv.stride != (1, 1) or c.conv.padding != (0, 0) or c.conv.groups != 1
-                    or not isinstance(c.act, (nn.Identity, nn.SiLU, nn.ReLU)) or c.__dict__.get('_q8') or c.out_dtype(x) != dt):
-                return None
-        if self.__dict__.get('_q8') or self._forward_hooks or c1._forward_hooks or c2._forward_hooks:
+        if (self.training or not ops.FUSED_SPPF or x.dtype != dt or fp8_claims(self, c1, c2) or watched(self, c1, c2)
+                or not all(plain(c, 1, EPILOGUE_ACTS) and c.out_dtype(x) == dt for c in (c1, c2))):
             return None
         cm, co = c1.conv.out_channels, c2.conv.out_channels
         if (c1.conv.in_channels != x.shape[1] or c2.conv.in_channels != 4 * cm or not ops.conv_can_mfma(x, x.shape[1], cm, 1, 1, 1, dt)
@@ -355,11 +340,11 @@ class SPPF(HipModule):
         if fused is not None:                                  # the 4 * c_ channel concat buffer is never written
             return fused()
         cat = ops.new_act(b, 4 * c_, h, w, self.cv1.out_dtype(x), x.device)
-        (self.cv1.train_fwd if train else self.cv1.run)(x, out=cat[:, :c_])
+        self.cv1.fwd(train, x, out=cat[:, :c_])
         ops.sppf_pools(cat[:, :c_], cat[:, c_:2 * c_], cat[:, 2 * c_:3 * c_], cat[:, 3 * c_:])
         if train:
             self._cat = cat if ops.ctx_enabled() else None
-        return (self.cv2.train_fwd if train else self.cv2.run)(cat)
+        return self.cv2.fwd(train, cat)
 
     def backward(self, g):
         c_ = self.cv1.conv.out_channels
@@ -493,13 +478,8 @@ class SimFusion_3in(HipModule):
         hooks), or shapes the kernel does not take.  slot1: the concat buffer's view that holds (or will hold) x[1]."""
         c1, cf = self.cv1, self.cv_fuse
         if (self.training or not ops.FUSED_LAF or dt != torch.bfloat16 or not isinstance(self.cv2, nn.Identity) or not isinstance(self.cv3, nn.Identity)
-                or not isinstance(c1, Conv) or not isinstance(cf, Conv) or ops.Q8_CALIB is not None):
-            return None
-        for c in (c1, cf):
-            if (not c.plain_affine() or c.conv.kernel_size != (1, 1) or c.conv.stride != (1, 1) or c.conv.padding != (0, 0) or c.conv.groups != 1
-                    or not isinstance(c.act, (nn.Identity, nn.SiLU, nn.ReLU)) or c.__dict__.get('_q8') or c.out_dtype(pooled0) != dt):
-                return None
-        if self.__dict__.get('_q8') or any(m._forward_hooks for m in self.modules()):
+                or not all(plain(c, 1, EPILOGUE_ACTS) and c.out_dtype(pooled0) == dt for c in (c1, cf))
+                or fp8_claims(self, c1, cf) or watched(*self.modules())):
             return None
         oc = cf.conv.out_channels
         if (c1.conv.in_channels != pooled0.shape[1] or c1.conv.out_channels != slot1.shape[1] or cf.conv.in_channels != 3 * slot1.shape[1]
@@ -532,17 +512,16 @@ class SimFusion_3in(HipModule):
                 if not (1 in done and x[1].data_ptr() == cat[:, oc:2 * oc].data_ptr()):
                     ops.copy(x[1], cat[:, oc:2 * oc])
                 return fused()
-            (self.cv1.train_fwd if (self.training and hasattr(self.cv1, 'bn')) else self.cv1.run)(pooled0, out=cat[:, :oc])
+            self.cv1.fwd(self.training and hasattr(self.cv1, 'bn'), pooled0, out=cat[:, :oc])
         if isinstance(self.cv2, nn.Identity):
             if not (1 in done and x[1].data_ptr() == cat[:, oc:2 * oc].data_ptr()):
                 ops.copy(x[1], cat[:, oc:2 * oc])
         else:
-            (self.cv2.train_fwd if (self.training and hasattr(self.cv2, 'bn')) else self.cv2.run)(x[1], out=cat[:, oc:2 * oc])
+            self.cv2.fwd(self.training and hasattr(self.cv2, 'bn'), x[1], out=cat[:, oc:2 * oc])
         if isinstance(self.cv3, nn.Identity):
             ops.bilinear(x[2], cat[:, 2 * oc:])
         else:
-            (self.cv3.train_fwd if (self.training and hasattr(self.cv3, 'bn')) else self.cv3.run)(
-                ops.bilinear(x[2], ops.new_act(b, x[2].shape[1], h, w, dt, dev)), out=cat[:, 2 * oc:])
+            self.cv3.fwd(self.training and hasattr(self.cv3, 'bn'), ops.bilinear(x[2], ops.new_act(b, x[2].shape[1], h, w, dt, dev)), out=cat[:, 2 * oc:])
         return self.cv_fuse(cat)
 
     def backward(self, g):
@@ -564,10 +543,14 @@ class IFM(nn.Module):
         self.conv = nn.Sequential(Conv(inc, embed_dim_p), *[ConvNeXtV2_Block(embed_dim_p) for _ in range(fuse_block_num)],
                                   Conv(embed_dim_p, sum(ouc)))
 
+    def _tail_in_block(self):
+        """the closing 1x1 Conv may run inside the last ConvNeXt block's launch (ConvNeXtV2_Block._tail_panel): eval, nobody watching block or Sequential"""
+        mods = list(self.conv)
+        return not self.training and len(mods) >= 2 and isinstance(mods[-2], ConvNeXtV2_Block) and not watched(mods[-2], self.conv)
+
     def forward(self, x):
         mods = list(self.conv)
-        if (not self.training and len(mods) >= 2 and isinstance(mods[-2], ConvNeXtV2_Block) and not mods[-2]._forward_hooks and not self.conv._forward_hooks):
-            # the closing 1x1 Conv runs inside the last ConvNeXt block's launch when that block takes its one-launch path
+        if self._tail_in_block():
             for m in mods[:-2]:
                 x = m(x)
             r = mods[-2](x, tail=mods[-1])
@@ -601,65 +584,50 @@ class InjectionMultiSum_Auto_pool(HipModule):
         self.act = h_sigmoid()
 
     def _merged_global(self, g, xq=None):
-        """PackedConv of cat(global_act, global_embedding) along cout, or None when they are not two plain 1x1 Conv+BN(no act) layers."""
+        """PackedConv of cat(global_act, global_embedding) along cout, or None when they are not two plain 1x1 Conv (no act) layers; an fp8 site of its own (`xq`)"""
         a, b = self.global_act, self.global_embedding
-        ok = all(m.plain_affine() and act_code(m.act) == ops.ACT_NONE and m.conv.kernel_size == (1, 1) and m.conv.groups == 1 for m in (a, b))
         dt = a.out_dtype(g)
-        fused = not hasattr(a, 'bn')
-        if (not ok or fused != (not hasattr(b, 'bn')) or (not fused and a.bn.eps != b.bn.eps) or a.conv.out_channels % 8
+        if (not (plain(a, 1, nn.Identity, stride=None) and plain(b, 1, nn.Identity, stride=None)) or a.conv.out_channels % 8
                 or not ops.conv_can_mfma(g, a.conv.in_channels, a.conv.out_channels + b.conv.out_channels, 1, 1, 1, dt)):
             return None
-        tens = [t for m in (a, b) for t in m.affine_tensors()]
-        cat = lambda fn: torch.cat([fn(a).detach().float(), fn(b).detach().float()])
-        zb = lambda m: m.conv.bias if m.conv.bias is not None else torch.zeros(m.conv.out_channels, device=m.conv.weight.device)
-        bn = lambda: None if fused else (cat(lambda m: m.bn.weight), cat(lambda m: m.bn.bias), cat(lambda m: m.bn.running_mean), cat(lambda m: m.bn.running_var), a.bn.eps)
-        cb = lambda: cat(zb) if fused else None                # after fuse(): the folded biases ride on the merged conv
-        if xq is not None:      # the e4m3 panel of the same merged convolution (quantize_fp8)
-            return self._cached(('gaf', 'fp8', float(xq)), tens, lambda: ops.PackedConvFp8(cat(lambda m: m.conv.weight), cb(), bn(), 1, xq))
-        return self._cached(('gaf', dt), tens, lambda: ops.PackedConv(cat(lambda m: m.conv.weight), cb(), bn(), 1, dt))
+        return merged_panel(self, ('gaf',), a, b, 1, dt, xq)
 
-    def forward_into_conv(self, x, conv):
-        """Injection + the 1x1 Conv+BN+act `conv` that consumes it (C2f.cv1) in one launch; returns conv's output, or None when the pair is
-        not covered (the caller then runs the two modules as usual).  Eval, bf16, up-sampling branch only."""
+    def _into_conv_route(self, x, conv):
+        """Injection + the plain 1x1 `conv` that consumes it (C2f.cv1) in one launch: a callable returning conv's output, or None when the pair is not covered.
+        Eval, bf16, up-sampling branch only; fp8 takes the per-site path.  No hooks are looked at: BaseModel._injection_feeds_next watches the two layers."""
         x_l, x_g = x
         le = self.local_embedding
-        if self.training or not isinstance(conv, Conv) or not conv.plain_affine() or not le.plain_affine():
+        if self.training or fp8_claims(self, conv, le) or not plain(le, 1, nn.Identity, stride=None) or not plain(conv, 1, FUSED_ACTS):
             return None
-        if ops.Q8_CALIB is not None or self.__dict__.get('_q8') or conv.__dict__.get('_q8') or le.__dict__.get('_q8'):
-            return None                                      # fp8 calibration / fp8 operands: the per-site path
         dt = le.out_dtype(x_l)
         c0 = sum(self.global_inp[:self.flag])
         g = x_g[:, c0:c0 + self.global_inp[self.flag]]
         pk2g = self._merged_global(g)
-        if (pk2g is None or dt != torch.bfloat16 or act_code(le.act) != ops.ACT_NONE or le.conv.kernel_size != (1, 1)
-                or le.conv.groups != 1 or conv.conv.kernel_size != (1, 1) or conv.conv.stride != (1, 1) or conv.conv.groups != 1
-                or conv.conv.in_channels != le.conv.out_channels):
+        if pk2g is None or dt != torch.bfloat16 or conv.conv.in_channels != le.conv.out_channels:
             return None
-        oc = self.global_act.conv.out_channels
-        b, _, h, w = x_l.shape
-        gh, gw = g.shape[2], g.shape[3]
-        probe = ops.new_act(1, oc, gh, gw, dt, x_l.device)
-        if not ops.conv1x1_inject_conv_supported(x_l, oc, conv.conv.out_channels, probe, dt):
+        oc, co = self.global_act.conv.out_channels, conv.conv.out_channels
+        if not ops.conv1x1_inject_conv_supported(x_l, oc, co, ops.new_act(1, oc, g.shape[2], g.shape[3], dt, x_l.device), dt):
             return None
-        in_launch = g.shape[1] == 32 and oc == 256 and ops.FUSED_INJECT_GCONV        # the two global convs run inside the launch too
-        if not in_launch:
-            gaf = ops.conv2d(g, pk2g, 1, ops.ACT_NONE)
-            ga, gf = gaf[:, :oc], gaf[:, oc:]
-            if ga.stride() != gf.stride():
-                return None
-        pk2 = conv._cached(('acc_order', dt), conv.affine_tensors(), lambda: ops.PackedConv(
-            conv.conv.weight.detach()[:, ops.acc_order_index(conv.conv.in_channels, conv.conv.weight.device)], conv.conv.bias, conv.bn_tuple(), 1, dt))
-        out = ops.new_act(b, conv.conv.out_channels, h, w, dt, x_l.device)
-        if in_launch:
-            return ops.conv1x1_inject_conv(x_l, le.packed(dt, direct=False), None, None, pk2, act_code(conv.act), out, gsrc=g, pkg=pk2g)
-        return ops.conv1x1_inject_conv(x_l, le.packed(dt, direct=False), ga, gf, pk2, act_code(conv.act), out)
+
+        def launch():
+            in_launch = g.shape[1] == 32 and oc == 256 and ops.FUSED_INJECT_GCONV        # the two global convs run inside the launch too
+            gaf = None if in_launch else ops.conv2d(g, pk2g, 1, ops.ACT_NONE)
+            pk2 = conv.packed_acc_order(dt)
+            out = ops.new_act(x_l.shape[0], co, x_l.shape[2], x_l.shape[3], dt, x_l.device)
+            if in_launch:
+                return ops.conv1x1_inject_conv(x_l, le.packed(dt, direct=False), None, None, pk2, act_code(conv.act), out, gsrc=g, pkg=pk2g)
+            return ops.conv1x1_inject_conv(x_l, le.packed(dt, direct=False), gaf[:, :oc], gaf[:, oc:], pk2, act_code(conv.act), out)
+        return launch
+
+    def forward_into_conv(self, x, conv):
+        route = self._into_conv_route(x, conv)
+        return None if route is None else route()
 
     def forward(self, x):
         x_l, x_g = x
         c0 = sum(self.global_inp[:self.flag])
         g = x_g[:, c0:c0 + self.global_inp[self.flag]]      # split(...)[flag] as a channel-slice view
         train = self.training and hasattr(self.local_embedding, 'bn')
-        f = (lambda m: m.train_fwd) if train else (lambda m: m.run)
         pk2 = None if train else self._merged_global(g)
         if pk2 is not None:                                 # global_act and global_embedding read the same g: one launch, two channel ranges
             xq = self.q8_site(('gaf',), g) if pk2.dtype == torch.bfloat16 else None
@@ -667,14 +635,14 @@ class InjectionMultiSum_Auto_pool(HipModule):
             oc = self.global_act.conv.out_channels
             ga, gf = gaf[:, :oc], gaf[:, oc:]
         else:
-            ga = f(self.global_act)(g)
-            gf = f(self.global_embedding)(g)
+            ga = self.global_act.fwd(train, g)
+            gf = self.global_embedding.fwd(train, g)
         le = self.local_embedding
         dt = le.out_dtype(x_l)
-        if (not train and le.plain_affine() and act_code(le.act) == ops.ACT_NONE and le.conv.kernel_size == (1, 1) and le.conv.groups == 1
-                and ops.conv1x1_inject_supported(x_l, le.conv.out_channels, ga, dt) and ga.stride() == gf.stride()):
+        # fp8 is not consulted: the local convolution inside the injection launch stays bf16 under quantize_fp8
+        if (not train and plain(le, 1, nn.Identity, stride=None) and ops.conv1x1_inject_supported(x_l, le.conv.out_channels, ga, dt) and ga.stride() == gf.stride()):
             return ops.conv1x1_inject(x_l, le.packed(dt, direct=False), ga, gf)   # local map never leaves the chip
-        local = f(le)(x_l)
+        local = le.fwd(train, x_l)
         if train:
             self._save_ctx((local, ga, x_g.shape, c0))
         return ops.inject(local, ga, gf)                    # pool vs up-sample branch chosen from the shapes (block.py:369)

@@ -35,6 +35,42 @@ def act_code(m):
     raise RuntimeError(f'activation {type(m).__name__} has no fused HIP epilogue (SiLU, ReLU, GELU, Identity are built)')
 
 
+# -- what every fused route asks of the host (DESIGN section 3a lists, route by route, which of these it consults and why) -------------------------
+FUSED_ACTS = (nn.Identity, nn.SiLU, nn.ReLU, nn.GELU)  # the activations act_code() knows
+EPILOGUE_ACTS = FUSED_ACTS[:3]                         # ... and the ones the one-launch SPPF / LAF kernels carry
+
+
+def plain(c, k, acts=(nn.SiLU,), stride=1):
+    """Conv.plain for a slot that may hold something else (nn.Identity, a bare nn.Conv2d): those are not plain"""
+    return isinstance(c, Conv) and c.plain(k, acts, stride)
+
+
+def watched(*modules):
+    """somebody observes one of these modules (forward hooks): a fused route would skip the call the hook hangs on"""
+    return any(m._forward_hooks for m in modules)
+
+
+def fp8_claims(*modules):
+    """fp8 owns a convolution site of these modules: quantize_fp8 is calibrating (every site must see its input), or one of them carries multipliers"""
+    return ops.Q8_CALIB is not None or any(m.__dict__.get('_q8') for m in modules)
+
+
+def merged_panel(owner, key, a, b, k, dt, xq=None):
+    """Panel of two sibling convolutions concatenated along cout (BatchNorm folded per branch; after fuse() the folded biases ride on the merged conv): [a | b]
+    in one launch.  None unless both are fused or neither, with one BatchNorm eps.  `xq`: the e4m3 panel (quantize_fp8).  Cached on `owner` under key + ..."""
+    fused = not hasattr(a, 'bn')
+    if fused != (not hasattr(b, 'bn')) or (not fused and a.bn.eps != b.bn.eps):
+        return None
+    cat = lambda fn: torch.cat([fn(a).detach().float(), fn(b).detach().float()])
+    zb = lambda m: m.conv.bias if m.conv.bias is not None else torch.zeros(m.conv.out_channels, device=m.conv.weight.device)
+    bn = lambda: None if fused else (cat(lambda m: m.bn.weight), cat(lambda m: m.bn.bias), cat(lambda m: m.bn.running_mean), cat(lambda m: m.bn.running_var), a.bn.eps)
+    cb = lambda: cat(zb) if fused else None
+    tens = [t for m in (a, b) for t in m.affine_tensors()]
+    if xq is not None:
+        return owner._cached(key + ('fp8', float(xq)), tens, lambda: ops.PackedConvFp8(cat(lambda m: m.conv.weight), cb(), bn(), k, xq))
+    return owner._cached(key + (dt,), tens, lambda: ops.PackedConv(cat(lambda m: m.conv.weight), cb(), bn(), k, dt))
+
+
 class HipModule(nn.Module):
     """Base: compute dtype bookkeeping + packed-weight cache invalidated by parameter versions."""
     _cdtype = None   # set by DetectionModel.set_compute_dtype(); None -> follow the input
@@ -103,6 +139,13 @@ class Conv(HipModule):
         block kernels.)"""
         return (hasattr(self, 'bn') and self.conv.bias is None) or not hasattr(self, 'bn')
 
+    def plain(self, k, acts=(nn.SiLU,), stride=1):
+        """THE definition of a convolution a fused route may compute in this module's place: plain_affine(), a dense k x k kernel at `stride` with 'same' padding
+        and no dilation (what Conv._geometry accepts), an activation in `acts`.  Channel counts stay at the sites.  `stride=None`: not looked at."""
+        c = self.conv
+        return (self.plain_affine() and c.kernel_size == (k, k) and (stride is None or c.stride == (stride, stride)) and c.padding == (k // 2, k // 2) and c.dilation == (1, 1)
+                and c.groups == 1 and isinstance(self.act, acts))
+
     def bn_tuple(self):
         """(gamma, beta, mean, var, eps) for the pack routines, or None after fuse() (the conv then carries its bias)"""
         return (self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, self.bn.eps) if hasattr(self, 'bn') else None
@@ -158,28 +201,27 @@ class Conv(HipModule):
         return self._cached(('stem6', raw, dt, 'direct'), tens, lambda: ops.PackedConv(ops.stem6_w3(self.conv.weight, cp), cb, bn, 3, dt, direct=True))
 
     def packed(self, dtype, direct):
-        has_bn = hasattr(self, 'bn')
-        tens = [self.conv.weight, self.conv.bias] + ([self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var] if has_bn else [])
         k, _ = self._geometry()
         if k == 6:
             return self._stem6_packed(dtype, direct)
-
-        def build():
-            bn = (self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, self.bn.eps) if has_bn else None
-            return ops.PackedConv(self.conv.weight, self.conv.bias, bn, k, dtype, direct=direct, groups=self.conv.groups)
-        return self._cached((dtype, direct), tens, build)
+        return self._cached((dtype, direct), self.affine_tensors(),
+                            lambda: ops.PackedConv(self.conv.weight, self.conv.bias, self.bn_tuple(), k, dtype, direct=direct, groups=self.conv.groups))
 
     def packed_fp8(self, xq):
-        has_bn = hasattr(self, 'bn')
-        tens = [self.conv.weight, self.conv.bias] + ([self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var] if has_bn else [])
         k, _ = self._geometry()
+        return self._cached(('fp8', float(xq)), self.affine_tensors(), lambda: ops.PackedConvFp8(self.conv.weight, self.conv.bias, self.bn_tuple(), k, xq))
 
-        def build():
-            bn = (self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, self.bn.eps) if has_bn else None
-            return ops.PackedConvFp8(self.conv.weight, self.conv.bias, bn, k, xq)
-        return self._cached(('fp8', float(xq)), tens, build)
+    def packed_acc_order(self, dt):
+        """panel of this 1x1 conv with its input channels in accumulator order: it reads another kernel's accumulators in place"""
+        w = self.conv.weight
+        return self._cached(('acc_order', dt), self.affine_tensors(), lambda: ops.PackedConv(
+            w.detach()[:, ops.acc_order_index(self.conv.in_channels, w.device)], self.conv.bias, self.bn_tuple(), 1, dt))
 
     # -- compute ----------------------------------------------------------------------------------------
+    def fwd(self, train, x, out=None, x2=None, r1=None, r2=None):
+        """train_fwd or run, by the flag the enclosing block computed once (its own mode and its first conv's `bn`)"""
+        return (self.train_fwd if train else self.run)(x, out=out, x2=x2, r1=r1, r2=r2)
+
     def run(self, x, out=None, x2=None, r1=None, r2=None, in_scale=None, in_shift=None):
         if hasattr(self, 'bn'):
             self._no_train_bn(self.bn)
@@ -200,9 +242,7 @@ class Conv(HipModule):
         return ops.conv2d(x, pk, s, act_code(self.act), out=out, x2=x2, r1=r1, r2=r2, in_scale=in_scale, in_shift=in_shift)
 
     def forward(self, x):
-        if self.training and hasattr(self, 'bn'):
-            return self.train_fwd(x)
-        return self.run(x)
+        return self.fwd(self.training and hasattr(self, 'bn'), x)
 
     # -- training mode: batch-statistics BN, context for backward ---------------------------------------------
     def train_fwd(self, x, out=None, x2=None, r1=None, r2=None):

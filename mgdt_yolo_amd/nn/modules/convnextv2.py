@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from .conv import HipModule
+from .conv import FUSED_ACTS, HipModule, act_code, fp8_claims, plain, watched
 from .utils import GRN, LayerNorm
 
 __all__ = ('ConvNeXtV2_Block',)
@@ -32,18 +32,12 @@ class ConvNeXtV2_Block(HipModule):
 
     @staticmethod
     def _tail_panel(conv, dim, dt):
-        """PackedConv of a plain 1x1 Conv+BN+act over this block's `dim` channels with its input channels in accumulator order, or None"""
-        from .conv import Conv, act_code
-        if (not ops.FUSED_CNX_TAIL or not isinstance(conv, Conv) or not conv.plain_affine() or conv.conv.kernel_size != (1, 1) or conv.conv.stride != (1, 1)
-                or conv.conv.groups != 1 or conv.conv.in_channels != dim or conv.conv.out_channels > dim or conv.conv.out_channels % 4
-                or conv.__dict__.get('_q8') or ops.Q8_CALIB is not None or conv._forward_hooks):
+        """PackedConv of a plain 1x1 conv (any built activation) over this block's `dim` channels with its input channels in accumulator order, or None:
+        not plain, somebody watching it, or an fp8 site (the conv is one of its own under quantize_fp8).  IFM watches the block and the Sequential."""
+        if (not ops.FUSED_CNX_TAIL or not plain(conv, 1, FUSED_ACTS) or conv.conv.in_channels != dim or conv.conv.out_channels > dim or conv.conv.out_channels % 4
+                or fp8_claims(conv) or watched(conv)):
             return None
-        try:
-            act_code(conv.act)
-        except RuntimeError:
-            return None
-        return conv._cached(('acc_order', dt), conv.affine_tensors(), lambda: ops.PackedConv(
-            conv.conv.weight.detach()[:, ops.acc_order_index(dim, conv.conv.weight.device)], conv.conv.bias, conv.bn_tuple(), 1, dt))
+        return conv.packed_acc_order(dt)
 
     def backward(self, g):
         x, u, t1, y1, t2, t3, S, pw1, pw2, dw, gb = self._ctx.pop()
@@ -110,7 +104,6 @@ class ConvNeXtV2_Block(HipModule):
             if tail is not None:
                 pk3 = self._tail_panel(tail, dim, dt)
                 if pk3 is not None:
-                    from .conv import act_code
                     return ops.cnx_block(x, dw, vec[0], vec[1], vec[2], self.norm.eps, mlp, gb[0], gb[1], tail=pk3, tail_act=act_code(tail.act)), True
             return ops.cnx_block(x, dw, vec[0], vec[1], vec[2], self.norm.eps, mlp, gb[0], gb[1])
         t = ops.dwconv7_ln(x, dw, self.dwconv.bias.detach().float(), self.norm.weight.detach().float(), self.norm.bias.detach().float(),

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from ... import ops
 from .block import DFL, Proto
-from .conv import Conv, HipModule
+from .conv import Conv, HipModule, fp8_claims, merged_panel, plain, watched
 
 __all__ = ('Detect', 'Segment', 'Pose', 'Classify', 'RTDETRDecoder', 'TOODHead', 'Conv_GN', 'TaskDecomposition', 'DyDCNv2', 'Scale')
 
@@ -31,6 +31,11 @@ class _HeadConv(HipModule):
         pk = owner._cached((id(conv), out.dtype, mfma), [conv.weight, conv.bias],
                            lambda: ops.PackedConv(conv.weight, conv.bias, None, 1, out.dtype, direct=not mfma))
         return ops.conv2d(x, pk, 1, ops.ACT_NONE, out=out)
+
+    @staticmethod
+    def panel(owner, conv, dt):
+        """the plain MFMA panel of a final conv, as the Detect tail launch reads it"""
+        return owner._cached((id(conv), dt), [conv.weight, conv.bias], lambda: ops.PackedConv(conv.weight, conv.bias, None, 1, dt))
 
     @staticmethod
     def backward(conv, x, g, accumulate=False):
@@ -67,14 +72,13 @@ class Detect(HipModule):
         like the reference (head.py:160)."""
         shape = x[0].shape
         r4 = 4 * self.reg_max
-        y, a_off, strides = None, 0, None
+        y, a_off = None, 0
+        strides = None if self.training else self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])  # host copy, no sync per call
         tta = None if self.training else self.__dict__.get('_tta')     # one pass of DetectionModel._predict_augment
         aug = None if tta is None else tta['aug']
         if tta is not None:
-            strides = self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])
             y, best, a_off = tta['y'], tta['best'], tta['a_off']
         elif not self.training:
-            strides = self._cached('stride_list', [self.stride], lambda: [float(v) for v in self.stride.tolist()])  # host copy, no sync per call
             a_total = sum(t.shape[2] * t.shape[3] for t in x)
             y = torch.empty(shape[0], 4 + self.nc, a_total, dtype=torch.float32, device=x[0].device)
             best = torch.empty(shape[0], a_total, dtype=torch.int64, device=x[0].device)      # NMS keys of the anchors' best classes (detect tail)
@@ -97,9 +101,7 @@ class Detect(HipModule):
                 if box3 is not None:
                     # the box branch's second 3x3 conv (16 -> 16) runs inside the tail launch: its input is handed over instead of its output
                     pk3, pkb_pad = box3
-                    pkc = self._cached((id(self.cv3[i][2]), feat.dtype), [self.cv3[i][2].weight, self.cv3[i][2].bias],
-                                       lambda c=self.cv3[i][2]: ops.PackedConv(c.weight, c.bias, None, 1, feat.dtype))
-                    ops.detect_tail(t01[:, :c2], tc, pkb_pad, pkc, self.nc, strides[i], a_off, feat, y, best, pk3=pk3, aug=aug)
+                    ops.detect_tail(t01[:, :c2], tc, pkb_pad, _HeadConv.panel(self, self.cv3[i][2], feat.dtype), self.nc, strides[i], a_off, feat, y, best, pk3=pk3, aug=aug)
                     decoded[i] = True
                     a_off += h * w
                     x[i] = feat
@@ -110,11 +112,8 @@ class Detect(HipModule):
                 tc = self.cv3[i][1](self.cv3[i][0](xi))
             if not self.training and ops.detect_tail_supported(tb, tc, self.nc, self.reg_max, feat.dtype):
                 # both final 1x1 convs, the raw map and the decode in one launch (mgdt_detect_tail_fwd)
-                pkb = self._cached((id(self.cv2[i][2]), feat.dtype), [self.cv2[i][2].weight, self.cv2[i][2].bias],
-                                   lambda c=self.cv2[i][2]: ops.PackedConv(c.weight, c.bias, None, 1, feat.dtype))
-                pkc = self._cached((id(self.cv3[i][2]), feat.dtype), [self.cv3[i][2].weight, self.cv3[i][2].bias],
-                                   lambda c=self.cv3[i][2]: ops.PackedConv(c.weight, c.bias, None, 1, feat.dtype))
-                ops.detect_tail(tb, tc, pkb, pkc, self.nc, strides[i], a_off, feat, y, best, aug=aug)
+                ops.detect_tail(tb, tc, _HeadConv.panel(self, self.cv2[i][2], feat.dtype), _HeadConv.panel(self, self.cv3[i][2], feat.dtype), self.nc, strides[i], a_off,
+                                feat, y, best, aug=aug)
                 decoded[i] = True
             else:
                 _HeadConv.run(self, self.cv2[i][2], tb, feat[:, :r4])
@@ -146,12 +145,10 @@ class Detect(HipModule):
 
     def _box3_in_tail(self, i, tb_in, tc, dt):
         """(panel of cv2[i][1], zero-padded accumulator-order panel of cv2[i][2]) when the box branch's second conv can run inside the Detect tail
-        launch: eval, bf16, 16 -> 16 channels, plain 3x3 Conv + BN/bias + SiLU, reg_max 4; else None."""
+        launch: eval, bf16, 16 -> 16 channels, a plain 3x3 conv nobody watches and fp8 does not own (it is a site of its own), reg_max 4; else None."""
         m3, m1 = self.cv2[i][1], self.cv2[i][2]
-        if (self.training or not ops.FUSED_DETECT_BOX3 or dt != torch.bfloat16 or not isinstance(m3, Conv) or not m3.plain_affine() or not isinstance(m3.act, nn.SiLU)
-                or m3.conv.kernel_size != (3, 3) or m3.conv.stride != (1, 1) or m3.conv.groups != 1 or m3.conv.in_channels != 16 or m3.conv.out_channels != 16
-                or m3._forward_hooks or m3.__dict__.get('_q8') or ops.Q8_CALIB is not None or tb_in.shape[1] != 16
-                or not ops.detect_tail_supported(tb_in, tc, self.nc, self.reg_max, dt)):
+        if (self.training or not ops.FUSED_DETECT_BOX3 or dt != torch.bfloat16 or not plain(m3, 3) or m3.conv.in_channels != 16 or m3.conv.out_channels != 16
+                or watched(m3) or fp8_claims(m3) or tb_in.shape[1] != 16 or not ops.detect_tail_supported(tb_in, tc, self.nc, self.reg_max, dt)):
             return None
         pk3 = m3.packed(dt, direct=False)
 
@@ -163,23 +160,13 @@ class Detect(HipModule):
         return pk3, self._cached((id(m1), dt, 'acc32'), [m1.weight, m1.bias], pad_pack)
 
     def _merged_first(self, i, xi, dt, xq=None):
-        """PackedConv of cat(cv2[i][0], cv3[i][0]) along cout (BN folded per branch), or None when the pair is not two plain
-        3x3 Conv+BN+SiLU layers the MFMA kernel takes."""
+        """PackedConv of cat(cv2[i][0], cv3[i][0]) along cout, or None when the pair is not two plain 3x3 convolutions the MFMA kernel takes.  An fp8 site
+        of its own (`xq`: its e4m3 panel); hooks on the two are not consulted."""
         a, b = self.cv2[i][0], self.cv3[i][0]
-        ok = all(isinstance(m, Conv) and m.plain_affine() and isinstance(m.act, nn.SiLU) and m.conv.kernel_size == (3, 3) and m.conv.stride == (1, 1)
-                 and m.conv.groups == 1 for m in (a, b))
-        fused = ok and not hasattr(a, 'bn')
-        if (not ok or fused != (not hasattr(b, 'bn')) or (not fused and a.bn.eps != b.bn.eps) or a.conv.out_channels % 8
+        if (not (plain(a, 3) and plain(b, 3)) or a.conv.out_channels % 8
                 or not ops.conv_can_mfma(xi, a.conv.in_channels, a.conv.out_channels + b.conv.out_channels, 3, 1, 1, dt)):
             return None
-        tens = [t for m in (a, b) for t in m.affine_tensors()]
-        cat = lambda f: torch.cat([f(a).detach().float(), f(b).detach().float()])
-        zb = lambda m: m.conv.bias if m.conv.bias is not None else torch.zeros(m.conv.out_channels, device=m.conv.weight.device)
-        bn = lambda: None if fused else (cat(lambda m: m.bn.weight), cat(lambda m: m.bn.bias), cat(lambda m: m.bn.running_mean), cat(lambda m: m.bn.running_var), a.bn.eps)
-        cb = lambda: cat(zb) if fused else None                # after fuse(): the folded biases ride on the merged conv
-        if xq is not None:      # the e4m3 panel of the same merged convolution (quantize_fp8)
-            return self._cached(('first01', i, 'fp8', float(xq)), tens, lambda: ops.PackedConvFp8(cat(lambda m: m.conv.weight), cb(), bn(), 3, xq))
-        return self._cached(('first01', i, dt), tens, lambda: ops.PackedConv(cat(lambda m: m.conv.weight), cb(), bn(), 3, dt))
+        return merged_panel(self, ('first01', i), a, b, 3, dt, xq)
 
     def backward(self, grads):
         """grads: list of d loss / d raw head maps (one per level, NHWC).  Returns the list of input gradients."""
@@ -289,6 +276,13 @@ class Pose(Detect):
     def q8_site(self, key, x, x2=None):
         return None                                           # fp8 for the Pose head is not built: its merged first convolutions stay bf16
 
+    def _kpt_padded(self, i, xi):
+        """zero-padded panels on the MFMA convolution: two plain 3x3 convs nobody watches + a dense 1x1; fp8 is not consulted (q8_site above: the head stays bf16)"""
+        c0, c1, c2 = self.cv4[i]
+        c4, c4p = c2.in_channels, -(-c2.in_channels // 8) * 8
+        return bool(ops.POSE_PAD_MFMA and (c4p != c4 or self.nk % 4) and plain(c0, 3) and plain(c1, 3) and not watched(c0, c1) and c2.kernel_size == (1, 1)
+                    and c2.groups == 1 and ops.conv_can_mfma(xi, c0.conv.in_channels, c4p, 3, 1, 1, c0.out_dtype(xi)))
+
     def _kpt_branch(self, i, xi):
         """cv4[i](xi) as an NHWC map whose first nk channels are the raw keypoints (52 channels on the padded route for nk = 51)."""
         c0, c1, c2 = self.cv4[i]
@@ -296,10 +290,7 @@ class Pose(Detect):
         b, _, h, w = xi.shape
         c4, nk = c2.in_channels, self.nk
         c4p, nkp = -(-c4 // 8) * 8, -(-nk // 4) * 4
-        plain = lambda m: (isinstance(m, Conv) and m.plain_affine() and isinstance(m.act, nn.SiLU) and m.conv.kernel_size == (3, 3) and m.conv.stride == (1, 1)
-                           and m.conv.groups == 1 and m.conv.dilation == (1, 1) and m.conv.padding == (1, 1) and not m._forward_hooks)
-        if (ops.POSE_PAD_MFMA and (c4p != c4 or nkp != nk) and plain(c0) and plain(c1) and c2.kernel_size == (1, 1) and c2.groups == 1
-                and ops.conv_can_mfma(xi, c0.conv.in_channels, c4p, 3, 1, 1, dt)):
+        if self._kpt_padded(i, xi):
             # panels packed from padded copies are derived copies (never refreshed in place): rebuilt whenever a live tensor they depend on changes
             pk0 = self._cached(('kpt', i, 0, dt), c0.affine_tensors(), lambda: ops.PackedConv(*padded_conv_params(c0, c0.conv.in_channels, c4p), 3, dt))
             pk1 = self._cached(('kpt', i, 1, dt), c1.affine_tensors(), lambda: ops.PackedConv(*padded_conv_params(c1, c4p, c4p), 3, dt))
@@ -351,12 +342,10 @@ class Classify(HipModule):
         return None                                           # fp8 for the Classify head is not built
 
     def _fusable(self, x, dt):
-        c = self.conv
-        if self.training or c._forward_hooks or self.pool._forward_hooks or not c.plain_affine() or not isinstance(c.act, nn.SiLU):
-            return False
-        cv = c.conv
-        return (cv.stride == (1, 1) and cv.padding == (0, 0) and cv.dilation == (1, 1) and cv.kernel_size == (1, 1)
-                and ops.classify_pool_supported(x, cv.in_channels, cv.out_channels, 1, cv.groups, ops.ACT_SILU, dt))
+        """eval, a plain 1x1 conv, nobody watching conv or pool; fp8 is not consulted: the Classify head stays bf16 under quantize_fp8 (q8_site above)"""
+        cv = self.conv.conv
+        return (not self.training and not watched(self.conv, self.pool) and plain(self.conv, 1)
+                and ops.classify_pool_supported(x, cv.in_channels, cv.out_channels, 1, 1, ops.ACT_SILU, dt))
 
     def _pool_panel(self, dt):
         c = self.conv

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..yolo.utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts, make_divisible
+from .modules.conv import plain, watched
 from .modules import (C2f, C3, IFM, MSPA_C2f, SPP, SPPF, Bottleneck, Classify, Concat, Conv, ConvTranspose2d, Detect, DWConv, InjectionMultiSum_Auto_pool,
                       MaxPool2d, Pose, Repeat, RTDETRDecoder, Segment, SimFusion_3in, SimFusion_4in, TOODHead, Upsample, ZeroPad2d)
 
@@ -28,6 +29,11 @@ REGISTRY['nn.Upsample'] = Upsample
 REGISTRY['nn.ConvTranspose2d'] = ConvTranspose2d
 REGISTRY['nn.MaxPool2d'] = MaxPool2d
 REGISTRY['nn.ZeroPad2d'] = ZeroPad2d
+
+
+def layer_sources(m):
+    """absolute indices of the layers a layer reads (its `f`: an int or a list, negative = relative to its own index)"""
+    return [m.i + f if f < 0 else f for f in ([m.f] if isinstance(m.f, int) else m.f)]
 
 
 class _TrainForwardFn(torch.autograd.Function):
@@ -159,13 +165,12 @@ class BaseModel(nn.Module):
         if not ops.SIDE_STREAM:
             return None
         if '_side_branch_cache' not in self.__dict__:
-            absf = lambda m: [m.i + f if f < 0 else f for f in ([m.f] if isinstance(m.f, int) else m.f)]
             best = None
             n = len(self.model)
             for s0 in range(2, n - 1):
                 deps, s1 = set(), s0 - 1
                 for k in range(s0, n - 1):                   # the last layer (the head) stays on the main stream
-                    ext = {j for j in absf(self.model[k]) if j < s0}
+                    ext = {j for j in layer_sources(self.model[k]) if j < s0}
                     if ext and max(ext) >= s0 - 1:
                         break
                     deps |= ext
@@ -177,7 +182,7 @@ class BaseModel(nn.Module):
                     best = (s0, s1, dep)
             self.__dict__['_side_branch_cache'] = best
         best = self.__dict__['_side_branch_cache']
-        if best is None or any(self.model[k]._forward_hooks for k in range(best[2] + 1, best[1] + 1)):
+        if best is None or watched(*(self.model[k] for k in range(best[2] + 1, best[1] + 1))):
             return None
         return best
 
@@ -188,7 +193,7 @@ class BaseModel(nn.Module):
                 or m.i in self.save or m.i + 1 >= len(self.model)):
             return False
         nxt = self.model[m.i + 1]
-        return isinstance(nxt, C2f) and nxt.f == -1 and not m._forward_hooks and not nxt._forward_hooks and len(nxt.m) >= 1
+        return isinstance(nxt, C2f) and nxt.f == -1 and not watched(m, nxt) and len(nxt.m) >= 1
 
     # -- GD-neck data movement folded into the producers ------------------------------------
     def _neck_plan(self, x):
@@ -201,13 +206,12 @@ class BaseModel(nn.Module):
         plan = self.__dict__.get('_neck_plan_cache')
         if plan is None:
             prod, cons = {}, set()
-            absf = lambda m: [m.i + f if f < 0 else f for f in ([m.f] if isinstance(m.f, int) else m.f)]
             for m in self.model:
                 if isinstance(m, SimFusion_4in):
-                    src = absf(m)
+                    src = layer_sources(m)
                     kinds = ('pool', 'pool', 'main')
                 elif isinstance(m, SimFusion_3in):
-                    src = absf(m)
+                    src = layer_sources(m)
                     kinds = ('pool', 'main' if isinstance(m.cv2, nn.Identity) else None)
                 else:
                     continue
@@ -222,7 +226,7 @@ class BaseModel(nn.Module):
             plan = self.__dict__['_neck_plan_cache'] = {'producers': prod, 'consumers': cons} if prod else False
         if not plan:
             return None
-        if any(self.model[i]._forward_hooks for i in list(plan['producers']) + list(plan['consumers'])):
+        if watched(*(self.model[i] for i in list(plan['producers']) + list(plan['consumers']))):
             return None
         return plan
 
@@ -231,10 +235,9 @@ class BaseModel(nn.Module):
         b, c, h, w = x.shape
         out, pools = None, []
         red = self._reductions
-        absf = lambda mm: [mm.i + f if f < 0 else f for f in ([mm.f] if isinstance(mm.f, int) else mm.f)]
         for kind, ci, slot in plan['producers'][m.i]:
             cm = self.model[ci]
-            src = absf(cm)
+            src = layer_sources(cm)
             tgt = src[2] if isinstance(cm, SimFusion_4in) else src[1]         # the input whose size the module resamples to (block.py:294,316)
             if red[tgt] % red[m.i]:
                 continue
@@ -269,16 +272,14 @@ class BaseModel(nn.Module):
 
     def _stem_fusable(self, x):
         """layers 0, 1 = Conv(3, 16, 3, 2) -> Conv(16, 32, 3, 2) with BN + SiLU, bf16 compute, layer 0's output used by layer 1 only, and nobody
-        watching the individual layers (forward hooks)"""
+        watching the individual layers (forward hooks).  fp8 is not consulted: the stem kernel stays bf16 under quantize_fp8."""
         if not ops.FUSED_STEM or getattr(self, 'compute_dtype', None) != torch.bfloat16 or len(self.model) < 3 or 0 in self.save:
             return False
         if x.dtype not in (torch.bfloat16, torch.float32, torch.uint8) or x.dim() != 4 or x.shape[1] != 3:
             return False
         m0, m1 = self.model[0], self.model[1]
         for m, (ci, co) in ((m0, (3, 16)), (m1, (16, 32))):
-            if not (isinstance(m, Conv) and not isinstance(m, DWConv) and m.plain_affine() and isinstance(m.act, nn.SiLU) and m.f == -1 and not m._forward_hooks
-                    and m.conv.kernel_size == (3, 3) and m.conv.stride == (2, 2) and m.conv.padding == (1, 1) and m.conv.groups == 1
-                    and m.conv.in_channels == ci and m.conv.out_channels == co):
+            if not (plain(m, 3, stride=2) and not isinstance(m, DWConv) and m.f == -1 and not watched(m) and m.conv.in_channels == ci and m.conv.out_channels == co):
                 return False
         return True
 
